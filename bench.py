@@ -1,6 +1,6 @@
 """bench.py -- throughput of the CloudAAE training step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: one rank per GPU over RCCL -- either launched by torch.distributed.run, which sets
     WORLD_SIZE/RANK/LOCAL_RANK, or by bench.py itself: with WORLD_SIZE unset it starts
     `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD process before
@@ -13,22 +13,39 @@ SO(3) losses, backward, TF-Adam (+ gradient all-reduce for N > 1).  Workload at 
 BASELINE.json configs[1]: all 21 classes, batch 32, 1024 points, fp32.  For N > 1 the workload is
 BASELINE.json configs[3]'s per-GPU shape: 128 clouds per GPU (global batch 1024 on 8 GPUs), fixed as
 N grows ("weak"); `--per-gpu-batch` overrides either.  Because the N=1 line is a different (smaller)
-batch than the N>1 lines, every N>1 line also carries `one_rank_same_shape`: rank 0 alone, no
+batch than the N>1 lines, every N>1 --full line also carries `one_rank_same_shape`: rank 0 alone, no
 collectives, the same 128-cloud batch -- the honest denominator for a scaling efficiency.
 Inputs are resident in HBM before the timed region.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, and ONE JSON line (rank 0) with
+  metric, value (clouds/s over the timed steps), unit, higher_is_better, dtype, ms_per_step (wall time of the timed region
+  / K), steps, warmup, step_ms_min / _median / _max (one HIP event per timed step) and config.
+  The K-th timed step starts from the seeded initial state (weights, BN moving averages, Adam slots, step scalars: put
+  back with the clock stopped).  The backward pass adds with fp32 atomics, and Adam turns the order-dependent rounding of
+  a gradient that cancels to near zero into a different update, so the state after W + K - 1 steps differs from run to
+  run beyond rounding; the inputs are seeded and the forward pass is bit-reproducible, so the last step computes the same
+  results on every run.
+  --dump-outputs DIR : after the timed steps, what the LAST timed step returned -- every tensor of the train step's result
+                 (losses, reconstruction, pose predictions, the inputs it assembled, end_points) -- as DIR/<name>.npy,
+                 float32 (float64 where the step computes in float64, and for integer arrays); past 60 MB of data the
+                 largest arrays are cut to a fixed, seeded sample.
+
+--full adds, after the timed steps (and, for the kernel sites below, live HIP events inside the timed region):
   roofline     : the dominant kernel = the top row of the step's kernel trace: the kNN over 64 feature
                  channels (knn64_wide_kernel, three launches per step), algorithmic flops 2 B N^2 64 against the
                  fp32 matrix pipe; timed live with HIP events on the launch stream over the timed region
   roofline_agg_fwd : the dgcnn_agg forward product, algorithmic flops (frac, frac_algorithmic) kept apart
                  from the bf16 pipe's utilisation by the six issued piece products (frac_issued)
-  roofline_edgeconv: the four edge-convolution blocks, forward + backward, against HBM
-  cpu_baseline : the CPU oracle's train step timed on this box's host cores on a bounded
-                 sample (rank 0, N=1 only)
+  roofline_edgeconv: the four edge-convolution blocks, forward + backward, against HBM (eight more steps after the
+                 timed ones)
+  chamfer_kernel, chamfer_reference_microbench, fps_kernel : kernel micro-benchmarks (N=1; not with --step-only)
+  cpu_table, cpu_baseline : the CPU legs of BASELINE.md and the CPU oracle's train step timed on the host's cores on a
+                 bounded sample (rank 0, N=1 only; not with --step-only or --cpu-batch 0)
   comm (N > 1) : ranks_seen (an RCCL all-reduce of ones), allreduce_exposed_ms (HIP events on the
                  compute stream around the end-of-backward exchange: the time the step waits for
                  gradients, the early fully-connected piece having been reduced behind backward)
+  replicas_identical, loss_rank_spread (N > 1) : the replica check (exit 3 if the replicas diverged)
+  one_rank_same_shape (N > 1) : rank 0 alone on the same per-GPU batch, timed again
 """
 import argparse
 import json
@@ -335,37 +352,59 @@ def launch_children(args):
     return subprocess.call(cmd, env=env)
 
 
-def timed_steps(graph, el, steps, warmup, world, sites):
-    """W untimed steps, then exactly K steps between barrier + synchronize on both sides; max over ranks."""
+def training_state(graph):
+    """The tensors a train step updates in place: weights, BN moving averages, Adam slots and the step's scalars (global
+    step, BN decay, Adam's beta powers).  The input noise is drawn from the seed and the step's count alone."""
+    s = graph.store
+    return [s.flat_params, s.flat_state, graph.adam_m, graph.adam_v, graph.batch, graph.bn_decay, graph.beta1_power,
+            graph.beta2_power]
+
+
+def timed_steps(graph, el, steps, warmup, world, sites, before_last=None):
+    """W untimed steps, then exactly K steps between barrier + synchronize on both sides; max over ranks.  before_last():
+    run before the K-th step with the clock stopped -- the K - 1 steps before it and the K-th are timed apart and added."""
     from cloudaae_amd.utils import _functions as F
     for _ in range(warmup):
         graph.train_step(el)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
     for k in sites:
         F.TIMED_SITES[k].clear()
-    # one HIP event per step on the launch stream: the spread of the single steps (min / median / max) goes into the
-    # line next to the mean, so that a box effect on a 30 ms timed region can be told from a regression
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
-    t0 = time.perf_counter()
-    marks[0].record()
-    for i in range(steps):
-        F.TIMED_ON = i % 4 == 0          # the live kernel timings sample one step in four of the timed region
-        out = graph.train_step(el)
-        marks[i + 1].record()
-    F.TIMED_ON = True
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
+    done = [0]
+
+    def segment(n):
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        # one HIP event per step on the launch stream: the spread of the single steps (min / median / max) goes into the
+        # line next to the mean, so that a box effect on a 30 ms timed region can be told from a regression
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
+        out = None
+        t0 = time.perf_counter()
+        marks[0].record()
+        for i in range(n):
+            F.TIMED_ON = done[0] % 4 == 0    # the live kernel timings sample one step in four of the timed region
+            out = graph.train_step(el)
+            marks[i + 1].record()
+            done[0] += 1
+        F.TIMED_ON = True
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out, [marks[i].elapsed_time(marks[i + 1]) for i in range(n)]
+
+    if before_last is None:
+        elapsed, out, step_ms = segment(steps)
+    else:
+        elapsed, _, step_ms = segment(steps - 1) if steps > 1 else (0.0, None, [])
+        before_last()
+        t, out, ms = segment(1)
+        elapsed, step_ms = elapsed + t, step_ms + ms
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=graph.device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
-    per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
+    per_step = sorted(step_ms)
     spread = {"step_ms_min": round(per_step[0], 4), "step_ms_median": round(per_step[len(per_step) // 2], 4),
               "step_ms_max": round(per_step[-1], 4)} if per_step else {}
     return elapsed, out, spread
@@ -374,6 +413,43 @@ def timed_steps(graph, el, steps, warmup, world, sites):
 def site_ms(events):
     ms = [events[i].elapsed_time(events[i + 1]) for i in range(0, len(events) - 1, 2)]
     return (sum(ms) / len(ms) if ms else 0.0), len(ms)
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6      # array data: with the .npy headers, under 64 MB in all
+
+
+def step_outputs(out):
+    """What the last step returned to its caller, as host arrays: every tensor of the step's result (end_points' too).
+    float64 stays float64 and integers become float64 (exact); every other float becomes float32."""
+    items = list(out.items())
+    if isinstance(out.get("end_points"), dict):
+        items += [("end_points_" + k, v) for k, v in out["end_points"].items()]
+    arrays = {}
+    for name, v in items:
+        if isinstance(v, torch.Tensor):
+            t = v.detach()
+            t = t.to(torch.float64 if t.dtype == torch.float64 or not t.is_floating_point() else torch.float32)
+            arrays[name] = t.contiguous().cpu().numpy()
+    return arrays
+
+
+def write_outputs(path, arrays):
+    """<path>/<name>.npy for every array.  Past DUMP_BUDGET_BYTES in all, the largest arrays are cut to an equal share of
+    what the smaller ones leave: the flattened array at a fixed, seeded sample of positions (in increasing order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    sizes = sorted(a.nbytes for a in arrays.values())
+    cap, left = None, DUMP_BUDGET_BYTES
+    for i, s in enumerate(sizes):
+        if s * (len(sizes) - i) > left:
+            cap = left // (len(sizes) - i)
+            break
+        left -= s
+    for name, a in arrays.items():
+        if cap is not None and a.nbytes > cap:
+            pos = np.sort(np.random.default_rng(0).choice(a.size, cap // a.itemsize, replace=False))
+            a = a.reshape(-1)[pos]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def main():
@@ -392,14 +468,20 @@ def main():
                     "accuracy: six exact piece products, fp32 accumulate); f32: those products on the fp32 matrix cores; bf16: "
                     "BASELINE configs[2]'s arithmetic (dense-layer operands rounded to bf16, fp32 accumulate; everything else fp32)")
     ap.add_argument("--sync-bn", action="store_true", help="batch-norm moments over the GLOBAL batch (all ranks)")
-    ap.add_argument("--step-only", action="store_true", help="skip the Chamfer kernel micro-benchmarks and the CPU "
-                    "baseline (profiling runs: only the train step's kernels in the trace)")
+    ap.add_argument("--full", action="store_true", help="also everything that is not the headline: kernel rooflines "
+                    "(live HIP events in the timed region), kernel micro-benchmarks, CPU baselines; N > 1: comm, the replica "
+                    "check and the one-rank line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--step-only", action="store_true", help="with --full: skip the Chamfer kernel micro-benchmarks and "
+                    "the CPU baseline (profiling runs: only the train step's kernels in the trace)")
     ap.add_argument("--config5", action="store_true", help="BASELINE configs[4]: N=4096, k=20 and the on-line synthesis "
                     "(pose -> transform -> occluder -> spherical flip -> hidden point removal x2, train...:96-117) of "
                     "every batch INSIDE the timed loop, from synthetic 8192-point object models")
     ap.add_argument("--eager", action="store_true", help="step through Python/autograd every time instead of "
                     "replaying the recorded step (TrainGraph(replay=False))")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: become one.  Nothing in this process has initialised the GPU (importing torch does not).
@@ -435,18 +517,29 @@ def main():
         args.num_point, args.k = 4096, 20
     B = args.per_gpu_batch or (32 if world == 1 else 128)
     N = args.num_point
-    # live HIP events on the launch stream around: the dgcnn_agg forward GEMM, the three kNN launches over 64
-    # feature channels, and (N > 1) the end-of-backward gradient exchange -- host callbacks of the recorded step
-    sites = ["agg_fwd", "knn64"] + (["exchange"] if (world > 1 or force) else [])
-    for k in sites:
-        F.TIMED_SITES[k] = []
-    F.TIMED_SITES["edgeconv"] = []        # recorded with the step, switched off until the timed region is over
-    F.SITES_OFF.add("edgeconv")
+    # --full: live HIP events on the launch stream around: the dgcnn_agg forward GEMM, the three kNN launches over 64
+    # feature channels, and (N > 1) the end-of-backward gradient exchange -- host callbacks of the recorded step.  A plain
+    # run records none: its step is the bare train step
+    sites = []
+    if args.full:
+        sites = ["agg_fwd", "knn64"] + (["exchange"] if (world > 1 or force) else [])
+        for k in sites:
+            F.TIMED_SITES[k] = []
+        F.TIMED_SITES["edgeconv"] = []        # recorded with the step, switched off until the timed region is over
+        F.SITES_OFF.add("edgeconv")
     graph = T.TrainGraph({"num_point": N, "gpu": local}, {"optimizer": "adam"},
                          {"batch_size": B * world, "learning_rate": 0.0008}, replay=not args.eager,
                          gemm_dtype=args.gemm_dtype, k_neighbor=args.k, sync_bn=args.sync_bn)
     el = T.synthetic_element(B, N, graph.device, seed=123456789, rank=rank)
     graph.reuse_staged_inputs = True     # one fixed batch, resident in HBM: do not re-copy it every step
+    # the seeded initial state, put back before the last timed step (clock stopped): the backward pass adds with fp32
+    # atomics, so the state after W + K - 1 steps differs from run to run beyond rounding; the last step then computes
+    # from the seeded inputs and this state alone, the same on every run (the forward pass is bit-reproducible)
+    start = [t.clone() for t in training_state(graph)]
+
+    def restore():
+        for t, t0 in zip(training_state(graph), start):
+            t.copy_(t0)
     synth = None
     if args.config5:
         # every step draws its batch from the synthesis pipeline: poses of the synthetic element, 8192-point models
@@ -476,29 +569,35 @@ def main():
         os.dup2(stdout_fd, 1)
         os.close(stdout_fd)
 
-    elapsed, out, spread = timed_steps(synth if synth is not None else graph, el, args.steps, args.warmup, world, sites)
-    events = {k: F.TIMED_SITES.pop(k) for k in sites}
+    elapsed, out, spread = timed_steps(synth if synth is not None else graph, el, args.steps, args.warmup, world, sites,
+                                       before_last=restore)
     loss = float(out["total_loss"])
-    # the edge-convolution blocks are timed AFTER the timed region (sixteen event pairs per step would cost the
-    # headline ~1 %): eight more steps of the same replayed plan with only that site switched on
-    F.TIMED_SITES["edgeconv"].clear()
-    F.SITES_OFF.discard("edgeconv")
-    F.TIMED_ON = True
-    runner = synth if synth is not None else graph
-    for _ in range(8):
-        runner.train_step(el)
-    torch.cuda.synchronize()
-    events["edgeconv"] = F.TIMED_SITES.pop("edgeconv")
+    if args.dump_outputs and rank == 0:
+        # before anything else steps the graph: a replayed step's results live in buffers the next step overwrites
+        write_outputs(args.dump_outputs, step_outputs(out))
+
+    events = {k: F.TIMED_SITES.pop(k) for k in sites}
+    if args.full:
+        # the edge-convolution blocks are timed AFTER the timed region (sixteen event pairs per step would cost the
+        # headline ~1 %): eight more steps of the same replayed plan with only that site switched on
+        F.TIMED_SITES["edgeconv"].clear()
+        F.SITES_OFF.discard("edgeconv")
+        F.TIMED_ON = True
+        runner = synth if synth is not None else graph
+        for _ in range(8):
+            runner.train_step(el)
+        torch.cuda.synchronize()
+        events["edgeconv"] = F.TIMED_SITES.pop("edgeconv")
 
     # N > 1 (and the forced one-rank RCCL run): the replicas must be IDENTICAL after the timed steps -- same weights, same
     # post-exchange gradient buffer on every rank (a 64-bit sum of the bit patterns of each, gathered over the ranks);
     # a stream-ordering slip between the asynchronous early all-reduce and the kernels around it shows up here
     replicas = None
-    if world > 1 or force:
+    if args.full and (world > 1 or force):
         replicas = replica_check(graph, float(out["total_loss"]), world)
 
     one_rank = None
-    if world > 1:
+    if args.full and world > 1:
         # the same per-GPU batch on rank 0 ALONE (no collectives, the others wait at the barrier)
         if rank == 0:
             solo = T.TrainGraph({"num_point": N, "gpu": local}, {"optimizer": "adam"},
@@ -511,10 +610,6 @@ def main():
         dist.barrier()
 
     if rank == 0:
-        k_ms, k_n = site_ms(events["agg_fwd"])
-        M, Nn, K = B * N, 1024, 320
-        flops = 2.0 * M * Nn * K                      # algorithmic flops of one dgcnn_agg forward launch
-        achieved = flops / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
         line = {
             "metric": "point-clouds/sec (train step, N=%d)" % N,
             "value": round(B * world * args.steps / elapsed, 2),
@@ -546,100 +641,105 @@ def main():
                        "step_issue": "recorded step replay" if graph.replay else "eager",
                        "final_total_loss": round(loss, 4)},
         }
-        # `roofline`: the DOMINANT kernel = the top row of the step's kernel trace at every batch size
-        # (profiles/r0N_trainstep_*_kernel_stats.csv): the kNN over 64 feature channels, three launches per step
-        # (layers 2-4, tf_util.py:597-632).  Algorithmic flops = the N x N x 64 inner products of every cloud
-        # (2 B N^2 C) against the fp32 matrix pipe (v_mfma_f32_32x32x2_f32, 157.3 TFLOP/s); the selection
-        # that follows the products is what keeps the kernel from that bound.
-        q_ms, q_n = site_ms(events["knn64"])
-        qf = 2.0 * B * N * N * 64 / (q_ms * 1e-3) / 1e12 if q_ms > 0 else 0.0
-        line["roofline"] = {"bound": "mfma", "kernel": "knn64_wide_kernel (cloudaae_knn, C=64, k=%d) [%d x %d x %d], "
-                                                        "3 launches per step" % (args.k, B, N, N),
-                            "achieved": round(qf, 3), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                            "frac": round(qf / FP32_MFMA_PEAK_TFLOPS, 4),
-                            "traffic": measured_traffic(B, N, "knn64"),
-                            "algorithmic_flops_per_launch": int(2.0 * B * N * N * 64),
-                            "launch_ms": round(q_ms, 4), "launches_timed": q_n}
-        # second entry: the dgcnn_agg forward product [B N x 320] x [320 x 1024] (tf_util.py:161-166).  ALGORITHMIC flops
-        # 2 M N K whatever the arithmetic.  f32: on the fp32 matrix pipe.  bf16x3: six bf16 piece products are ISSUED per
-        # algorithmic product, so the line carries frac_issued (6 x flops / 2.5 PFLOP/s: how busy the bf16 pipe is -- a
-        # utilisation figure, NOT a roofline fraction) next to frac_algorithmic against both pipes (vs the bf16 pipe
-        # it runs on; vs the fp32 pipe an fp32 kernel would be bound by: > 1 means it beats every fp32-MFMA kernel).
-        agg = {"bound": "mfma", "algorithmic_tflops": round(achieved, 3), "launch_ms": round(k_ms, 4), "launches_timed": k_n,
-               "algorithmic_flops_per_launch": int(flops)}
-        if args.gemm_dtype == "f32":
-            agg.update({"kernel": "gemm_f32_kernel dgcnn_agg forward [%d x 320] x [320 x 1024]" % M,
-                        "achieved": round(achieved, 3), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                        "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4), "traffic": measured_traffic(B, N, "agg_fwd")})
-        elif args.gemm_dtype == "bf16x3":
-            agg.update({"kernel": "gemm_x3s_kernel dgcnn_agg forward [%d x 320] x [320 x 1024] as 3 x bf16 splits "
-                                  "(6 piece products issued per product)" % M,
-                        "achieved": round(achieved, 3), "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                        "frac": round(achieved / BF16_MFMA_PEAK_TFLOPS, 4),
-                        "frac_algorithmic": round(achieved / BF16_MFMA_PEAK_TFLOPS, 4),
-                        "frac_algorithmic_vs_fp32_mfma_peak": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
-                        "frac_issued": round(6.0 * achieved / BF16_MFMA_PEAK_TFLOPS, 4),
-                        "issued_tflops": round(6.0 * achieved, 2), "traffic": measured_traffic(B, N, "agg_fwd_x3")})
-        else:
-            # with bf16 operands the same product leaves the matrix pipe (2.5 PFLOP/s dense) and is bound by
-            # HBM.  Activations kept as bfloat16 (F.ACT_BF16, the default): x (M x 320) and W in as bf16, y
-            # (M x 1024) out as bf16; else fp32 tensors in and out (rounded on the way into LDS)
-            act16 = bool(F.ACT_BF16) and M % 128 == 0 and not args.sync_bn
-            esz = 2.0 if act16 else 4.0
-            nbytes = esz * (M * K + K * Nn + M * Nn) + 4.0 * Nn
-            gbs = nbytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-            kname = ("gemm_b16 (bf16 x, W in; bf16 y out)" if act16 else "gemm_bf16_kernel<128,128,2,2> (fp32 in / out)")
-            agg.update({"bound": "hbm", "kernel": kname + " dgcnn_agg forward [%d x 320] x [320 x 1024]" % M,
-                        "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(gbs / HBM_PEAK_GBS, 4), "algorithmic_bytes_per_launch": int(nbytes),
-                        "traffic": measured_traffic(B, N, "agg_fwd_b16" if act16 else "agg_fwd_bf16")})
-        line["roofline_agg_fwd"] = agg
-        # third entry: the four edge-convolution blocks, forward and backward (the calls cloudaae_edgeconv_forward /
-        # _backward: their products, statistics, finalise and apply / gather kernels; the grouped weight-gradient
-        # launch that follows backward is not inside).  HBM-bound by construction (the k-fold edge tensor never
-        # exists); algorithmic bytes = every array of a layer read or written once per pass that needs it.
-        e_ms, e_n = site_ms(events["edgeconv"])
-        if e_n:
-            P = B * N
-            tot = 0.0
-            for cin, cout in ((24, 64), (64, 64), (64, 64), (64, 128)):
-                idx, pq, out_, est = 4.0 * P * args.k, 4.0 * P * 2 * cout, 4.0 * P * cout, 4.0 * P * 3 * cout
-                fwd = 4.0 * P * cin + pq + (pq + idx) + (pq + idx + out_ + est)          # product | statistics | apply
-                bwd = (est + out_) + (est + out_ + pq + 2 * idx + pq) + (pq + 4.0 * P * cin)   # stats | apply (dpq) | dX
-                tot += fwd + bwd
-            per_call = tot / 8.0                       # eight timed calls per step (4 forward + 4 backward)
-            gbs = per_call / (e_ms * 1e-3) / 1e9
-            line["roofline_edgeconv"] = {"bound": "hbm", "kernel": "cloudaae_edgeconv_forward + _backward, 4 layers "
-                                                                   "(ec_stats / ec_apply / ec_bwd_* + their products)",
-                                         "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                         "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": None,
-                                         "step_ms_in_edgeconv": round(e_ms * 8, 4), "calls_timed": e_n,
-                                         "algorithmic_bytes_per_step": int(tot)}
-        if world > 1 or force:
-            x_ms, x_n = site_ms(events["exchange"])
-            line["comm"] = {"backend": "nccl (RCCL)", "ranks_seen": ranks_seen,
-                            "allreduce_exposed_ms": round(x_ms, 4), "exchanges_timed": x_n,
-                            "bytes_per_step": int(graph.store.flat_grads.numel()) * 4,
-                            "sync_bn": bool(args.sync_bn)}
-        if replicas is not None:
-            line["replicas_identical"] = replicas["identical"]
-            line["loss_rank_spread"] = replicas["loss_rank_spread"]
-            line["comm"]["replica_checksums"] = replicas["checksums"]
-        if one_rank is not None:
-            line["one_rank_same_shape"] = one_rank
-        if world == 1 and not args.step_only:
-            # "Chamfer kernel GB/s": the train shape (n = m = 4N) and the reference's own
-            # micro-benchmark shape (tf_nndistance.py:48-49), forward alone and the whole iteration it times
-            line["chamfer_kernel"] = [chamfer_kernel_rate(B, 4 * N, 4 * N), chamfer_kernel_rate(32, 16384, 1024),
-                                      chamfer_kernel_rate(B, 4 * N, 4 * N, distinct=N),
-                                      chamfer_kernel_rate(B, 4 * N, 4 * N, distinct=N, hint=True)]
-            line["chamfer_reference_microbench"] = chamfer_train_rate()
-            line["fps_kernel"] = [fps_kernel_rate(B, 4 * N, N), fps_kernel_rate(1, 4 * N, N)]
-            if args.cpu_batch > 0:
-                line["chamfer_kernel"][0]["cpu"] = chamfer_cpu_rate(4 * N, 4 * N)
-        if world == 1 and args.cpu_batch > 0 and not args.step_only:
-            line["cpu_table"] = cpu_table(N)
-            line["cpu_baseline"] = cpu_baseline(N, args.cpu_batch, args.cpu_steps)
+        if args.full:
+            k_ms, k_n = site_ms(events["agg_fwd"])
+            M, Nn, K = B * N, 1024, 320
+            flops = 2.0 * M * Nn * K                      # algorithmic flops of one dgcnn_agg forward launch
+            achieved = flops / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
+            # `roofline`: the DOMINANT kernel = the top row of the step's kernel trace at every batch size
+            # (profiles/r0N_trainstep_*_kernel_stats.csv): the kNN over 64 feature channels, three launches per step
+            # (layers 2-4, tf_util.py:597-632).  Algorithmic flops = the N x N x 64 inner products of every cloud
+            # (2 B N^2 C) against the fp32 matrix pipe (v_mfma_f32_32x32x2_f32, 157.3 TFLOP/s); the selection
+            # that follows the products is what keeps the kernel from that bound.
+            q_ms, q_n = site_ms(events["knn64"])
+            qf = 2.0 * B * N * N * 64 / (q_ms * 1e-3) / 1e12 if q_ms > 0 else 0.0
+            line["roofline"] = {"bound": "mfma", "kernel": "knn64_wide_kernel (cloudaae_knn, C=64, k=%d) [%d x %d x %d], "
+                                                            "3 launches per step" % (args.k, B, N, N),
+                                "achieved": round(qf, 3), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                "frac": round(qf / FP32_MFMA_PEAK_TFLOPS, 4),
+                                "traffic": measured_traffic(B, N, "knn64"),
+                                "algorithmic_flops_per_launch": int(2.0 * B * N * N * 64),
+                                "launch_ms": round(q_ms, 4), "launches_timed": q_n}
+            # second entry: the dgcnn_agg forward product [B N x 320] x [320 x 1024] (tf_util.py:161-166).  ALGORITHMIC flops
+            # 2 M N K whatever the arithmetic.  f32: on the fp32 matrix pipe.  bf16x3: six bf16 piece products are ISSUED per
+            # algorithmic product, so the line carries frac_issued (6 x flops / 2.5 PFLOP/s: how busy the bf16 pipe is -- a
+            # utilisation figure, NOT a roofline fraction) next to frac_algorithmic against both pipes (vs the bf16 pipe
+            # it runs on; vs the fp32 pipe an fp32 kernel would be bound by: > 1 means it beats every fp32-MFMA kernel).
+            agg = {"bound": "mfma", "algorithmic_tflops": round(achieved, 3), "launch_ms": round(k_ms, 4), "launches_timed": k_n,
+                   "algorithmic_flops_per_launch": int(flops)}
+            if args.gemm_dtype == "f32":
+                agg.update({"kernel": "gemm_f32_kernel dgcnn_agg forward [%d x 320] x [320 x 1024]" % M,
+                            "achieved": round(achieved, 3), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                            "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4), "traffic": measured_traffic(B, N, "agg_fwd")})
+            elif args.gemm_dtype == "bf16x3":
+                agg.update({"kernel": "gemm_x3s_kernel dgcnn_agg forward [%d x 320] x [320 x 1024] as 3 x bf16 splits "
+                                      "(6 piece products issued per product)" % M,
+                            "achieved": round(achieved, 3), "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                            "frac": round(achieved / BF16_MFMA_PEAK_TFLOPS, 4),
+                            "frac_algorithmic": round(achieved / BF16_MFMA_PEAK_TFLOPS, 4),
+                            "frac_algorithmic_vs_fp32_mfma_peak": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
+                            "frac_issued": round(6.0 * achieved / BF16_MFMA_PEAK_TFLOPS, 4),
+                            "issued_tflops": round(6.0 * achieved, 2), "traffic": measured_traffic(B, N, "agg_fwd_x3")})
+            else:
+                # with bf16 operands the same product leaves the matrix pipe (2.5 PFLOP/s dense) and is bound by
+                # HBM.  Activations kept as bfloat16 (F.ACT_BF16, the default): x (M x 320) and W in as bf16, y
+                # (M x 1024) out as bf16; else fp32 tensors in and out (rounded on the way into LDS)
+                act16 = bool(F.ACT_BF16) and M % 128 == 0 and not args.sync_bn
+                esz = 2.0 if act16 else 4.0
+                nbytes = esz * (M * K + K * Nn + M * Nn) + 4.0 * Nn
+                gbs = nbytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+                kname = ("gemm_b16 (bf16 x, W in; bf16 y out)" if act16 else "gemm_bf16_kernel<128,128,2,2> (fp32 in / out)")
+                agg.update({"bound": "hbm", "kernel": kname + " dgcnn_agg forward [%d x 320] x [320 x 1024]" % M,
+                            "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": round(gbs / HBM_PEAK_GBS, 4), "algorithmic_bytes_per_launch": int(nbytes),
+                            "traffic": measured_traffic(B, N, "agg_fwd_b16" if act16 else "agg_fwd_bf16")})
+            line["roofline_agg_fwd"] = agg
+            # third entry: the four edge-convolution blocks, forward and backward (the calls cloudaae_edgeconv_forward /
+            # _backward: their products, statistics, finalise and apply / gather kernels; the grouped weight-gradient
+            # launch that follows backward is not inside).  HBM-bound by construction (the k-fold edge tensor never
+            # exists); algorithmic bytes = every array of a layer read or written once per pass that needs it.
+            e_ms, e_n = site_ms(events["edgeconv"])
+            if e_n:
+                P = B * N
+                tot = 0.0
+                for cin, cout in ((24, 64), (64, 64), (64, 64), (64, 128)):
+                    idx, pq, out_, est = 4.0 * P * args.k, 4.0 * P * 2 * cout, 4.0 * P * cout, 4.0 * P * 3 * cout
+                    fwd = 4.0 * P * cin + pq + (pq + idx) + (pq + idx + out_ + est)          # product | statistics | apply
+                    bwd = (est + out_) + (est + out_ + pq + 2 * idx + pq) + (pq + 4.0 * P * cin)   # stats | apply (dpq) | dX
+                    tot += fwd + bwd
+                per_call = tot / 8.0                       # eight timed calls per step (4 forward + 4 backward)
+                gbs = per_call / (e_ms * 1e-3) / 1e9
+                line["roofline_edgeconv"] = {"bound": "hbm", "kernel": "cloudaae_edgeconv_forward + _backward, 4 layers "
+                                                                       "(ec_stats / ec_apply / ec_bwd_* + their products)",
+                                             "achieved": round(gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                             "frac": round(gbs / HBM_PEAK_GBS, 4), "traffic": None,
+                                             "step_ms_in_edgeconv": round(e_ms * 8, 4), "calls_timed": e_n,
+                                             "algorithmic_bytes_per_step": int(tot)}
+            if world > 1 or force:
+                x_ms, x_n = site_ms(events["exchange"])
+                line["comm"] = {"backend": "nccl (RCCL)", "ranks_seen": ranks_seen,
+                                "allreduce_exposed_ms": round(x_ms, 4), "exchanges_timed": x_n,
+                                "bytes_per_step": int(graph.store.flat_grads.numel()) * 4,
+                                "sync_bn": bool(args.sync_bn)}
+            if replicas is not None:
+                line["replicas_identical"] = replicas["identical"]
+                line["loss_rank_spread"] = replicas["loss_rank_spread"]
+                line["comm"]["replica_checksums"] = replicas["checksums"]
+            if one_rank is not None:
+                line["one_rank_same_shape"] = one_rank
+            if world == 1 and not args.step_only:
+                # "Chamfer kernel GB/s": the train shape (n = m = 4N) and the reference's own
+                # micro-benchmark shape (tf_nndistance.py:48-49), forward alone and the whole iteration it times
+                line["chamfer_kernel"] = [chamfer_kernel_rate(B, 4 * N, 4 * N), chamfer_kernel_rate(32, 16384, 1024),
+                                          chamfer_kernel_rate(B, 4 * N, 4 * N, distinct=N),
+                                          chamfer_kernel_rate(B, 4 * N, 4 * N, distinct=N, hint=True)]
+                line["chamfer_reference_microbench"] = chamfer_train_rate()
+                line["fps_kernel"] = [fps_kernel_rate(B, 4 * N, N), fps_kernel_rate(1, 4 * N, N)]
+                if args.cpu_batch > 0:
+                    line["chamfer_kernel"][0]["cpu"] = chamfer_cpu_rate(4 * N, 4 * N)
+            if world == 1 and args.cpu_batch > 0 and not args.step_only:
+                line["cpu_table"] = cpu_table(N)
+                line["cpu_baseline"] = cpu_baseline(N, args.cpu_batch, args.cpu_steps)
         print(json.dumps(line))
     diverged = replicas is not None and not replicas["identical"]
     if dist.is_initialized():

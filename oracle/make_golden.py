@@ -43,6 +43,23 @@ def prob_sample_case():
     np.savez_compressed(os.path.join(OUT, "probsample_2x8227_400.npz"), inp=p, inpr=draws, out=out, cumsum=cum)
 
 
+def chamfer_live_case():
+    """The inputs tests/test_oracle_golden.py::test_chamfer_against_live_reference_lines draws (duplicated targets,
+    ragged sizes) with the reference lines' outputs, so that the test runs where oracle/_ref was not built; own
+    generator, so adding it does not move the other fixtures."""
+    assert O.have_ref(), "build oracle/_ref first (oracle/build_ref.sh: needs the reference checkout)"
+    rng = np.random.default_rng(5)
+    a = rng.standard_normal((3, 130, 3)).astype(np.float32)
+    b = rng.standard_normal((3, 513, 3)).astype(np.float32)
+    b[:, 400:] = b[:, :113]
+    d1, i1, d2, i2 = O.ref_nn_distance(a, b)
+    g1 = rng.standard_normal((3, 130)).astype(np.float32)
+    g2 = rng.standard_normal((3, 513)).astype(np.float32)
+    gx1, gx2 = O.ref_nn_distance_grad(a, b, g1, i1, g2, i2)
+    np.savez_compressed(os.path.join(OUT, "chamfer_live_3x130x513.npz"), xyz1=a, xyz2=b, dist1=d1, idx1=i1,
+                        dist2=d2, idx2=i2, grad_dist1=g1, grad_dist2=g2, grad_xyz1=gx1, grad_xyz2=gx2)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     # (1) the reference's seeded known-answer input, tf_nndistance_cpu.py:28-46
@@ -108,6 +125,7 @@ def main():
     knn_case("knn_feat64_2x257_k10", f, 10, 64)
     knn_case("knn_feat64_2x257_k20", f, 20, 64)
     prob_sample_case()
+    chamfer_live_case()
     print("wrote", sorted(os.listdir(OUT)))
 
 

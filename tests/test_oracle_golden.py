@@ -38,20 +38,22 @@ def test_chamfer_seed0_known_answer(oracle, golden_dir):
     np.testing.assert_allclose(d2[0], D.min(0), rtol=0, atol=1e-6)
 
 
-def test_chamfer_against_live_reference_lines(oracle):
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built (no /root/reference on this box)")
-    rng = np.random.default_rng(5)
-    a = rng.standard_normal((3, 130, 3)).astype(np.float32)
-    b = rng.standard_normal((3, 513, 3)).astype(np.float32)
-    b[:, 400:] = b[:, :113]
-    ours, ref = oracle.nn_distance(a, b), oracle.ref_nn_distance(a, b)
+def test_chamfer_against_live_reference_lines(oracle, golden_dir):
+    # the reference lines' outputs for these inputs are stored (oracle/make_golden.py: chamfer_live_case); where oracle/_ref
+    # was built, the live lines must still give them
+    g = _load(golden_dir, "chamfer_live_3x130x513")
+    a, b, g1, g2 = g["xyz1"], g["xyz2"], g["grad_dist1"], g["grad_dist2"]
+    ref = (g["dist1"], g["idx1"], g["dist2"], g["idx2"])
+    rg = (g["grad_xyz1"], g["grad_xyz2"])
+    if oracle.have_ref():
+        for x, y in zip(oracle.ref_nn_distance(a, b), ref):
+            assert np.array_equal(x, y)
+        live = oracle.ref_nn_distance_grad(a, b, g1, ref[1], g2, ref[3])
+        assert np.array_equal(live[0], rg[0]) and np.array_equal(live[1], rg[1])
+    ours = oracle.nn_distance(a, b)
     for x, y in zip(ours, ref):
         assert np.array_equal(x, y)
-    g1 = rng.standard_normal((3, 130)).astype(np.float32)
-    g2 = rng.standard_normal((3, 513)).astype(np.float32)
     og = oracle.nn_distance_grad(a, b, g1, ours[1], g2, ours[3])
-    rg = oracle.ref_nn_distance_grad(a, b, g1, ours[1], g2, ours[3])
     assert np.array_equal(og[0], rg[0]) and np.array_equal(og[1], rg[1])
     # OpenMP over the batch must not change the per-cloud order
     og8 = oracle.nn_distance_grad(a, b, g1, ours[1], g2, ours[3], threads=4)

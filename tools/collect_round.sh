@@ -26,19 +26,19 @@ KNN_HINT=noisy timeout 300 bash tools/pmc_kernel.sh ${R}_knn64_wide_hinted_k20_n
 timeout 300 bash tools/pmc_kernel.sh ${R}_hull_pmc_n8593 hull_vertex -- python3 "$ROOT/tools/dev/run_hpr.py" 32 8192 1
 timeout 300 bash tools/pmc_kernel.sh ${R}_fps_pmc fps_kernel -- python3 "$ROOT/tools/bench_fps.py"
 # the bench lines (no profiler): the driver-shaped full lines of the named configurations, then the A/B lines
-python3 bench.py > "$OUT/${R}_bench_b32_n1024.json" 2> "$OUT/bench_b32.err"
-python3 bench.py --per-gpu-batch 128 > "$OUT/${R}_bench_b128_n1024.json" 2>/dev/null
-python3 bench.py --per-gpu-batch 256 --gemm-dtype bf16 > "$OUT/${R}_bench_b256_n1024_bf16.json" 2>/dev/null
-python3 bench.py --config5 --steps 20 --warmup 5 > "$OUT/${R}_bench_config5_b32_n4096_k20.json" 2>/dev/null
-python3 bench.py --gemm-dtype f32 --step-only > "$OUT/${R}_bench_b32_n1024_f32_mfma.json" 2>/dev/null
+python3 bench.py --full > "$OUT/${R}_bench_b32_n1024.json" 2> "$OUT/bench_b32.err"
+python3 bench.py --full --per-gpu-batch 128 > "$OUT/${R}_bench_b128_n1024.json" 2>/dev/null
+python3 bench.py --full --per-gpu-batch 256 --gemm-dtype bf16 > "$OUT/${R}_bench_b256_n1024_bf16.json" 2>/dev/null
+python3 bench.py --full --config5 --steps 20 --warmup 5 > "$OUT/${R}_bench_config5_b32_n4096_k20.json" 2>/dev/null
+python3 bench.py --full --gemm-dtype f32 --step-only > "$OUT/${R}_bench_b32_n1024_f32_mfma.json" 2>/dev/null
 python3 tools/bench_fps.py > "$OUT/${R}_bench_fps.txt" 2>/dev/null
 # the RCCL path with ONE rank (no second GPU on this box): the same replayed step with the gradient exchange's two
 # all-reduces (and, second line, SyncBN's 22) going through RCCL -- the `comm` block of the N > 1 bench line
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 CLOUDAAE_FORCE_COLLECTIVES=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-    --master-port 29611 bench.py --gpus 1 --per-gpu-batch 128 --step-only > "$OUT/${R}_bench_b128_one_rank_rccl.json" 2> "$OUT/rccl.err"
+    --master-port 29611 bench.py --gpus 1 --full --per-gpu-batch 128 --step-only > "$OUT/${R}_bench_b128_one_rank_rccl.json" 2> "$OUT/rccl.err"
 CLOUDAAE_FORCE_COLLECTIVES=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-    --master-port 29612 bench.py --gpus 1 --per-gpu-batch 128 --step-only --sync-bn > "$OUT/${R}_bench_b128_one_rank_rccl_syncbn.json" 2>> "$OUT/rccl.err"
+    --master-port 29612 bench.py --gpus 1 --full --per-gpu-batch 128 --step-only --sync-bn > "$OUT/${R}_bench_b128_one_rank_rccl_syncbn.json" 2>> "$OUT/rccl.err"
 # the driver's own entry points, as it runs them
 python3 -c "import __graft_entry__ as g; g.smoke()" > "$OUT/${R}_smoke.log" 2>&1
 ls -la "$OUT"

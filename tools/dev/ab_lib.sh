@@ -27,7 +27,7 @@ for rep in 1 2; do
 done
 for which in A B; do
   lib=$A; [ $which = B ] && lib=$B
-  CLOUDAAE_HIP_LIB=$ROOT/$lib python bench.py > $OUT/r06_${TAG}_full_$which.json 2>/dev/null
+  CLOUDAAE_HIP_LIB=$ROOT/$lib python bench.py --full > $OUT/r06_${TAG}_full_$which.json 2>/dev/null
   python - $OUT/r06_${TAG}_full_$which.json <<'PY' | tee -a "$LOG"
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
