@@ -16,6 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 _lib = None
 
 _P, _I, _L, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
+_D = ctypes.c_double
 _U = ctypes.c_ulonglong
 # argument types of every entry point of include/cloudaae_hip.h (stream last)
 _SIGNATURES = {
@@ -111,6 +112,9 @@ _SIGNATURES = {
     "cloudaae_spherical_flip": [_I, _I, _P, _I, _P, _P, _F, _P, _P, _P],
     "cloudaae_hidden_point_removal": [_I, _I, _P, _P, _U, _P, _P, _P, _P, _P],
     "cloudaae_hidden_point_removal_rows": [_I, _I, _P, _P, _U, _I, _P, _P, _P, _P, _P, _P],
+    "cloudaae_icp_point_to_point": [_I, _I, _P, _I, _L, _I, _P, _I, _L, _P, _P, _D, _D, _I, _I, _D, _D, _P, _P, _P,
+                                    _P, _P, _P, _P],
+    "cloudaae_f64_to_f32": [_L, _P, _P, _P],
 }
 
 
@@ -143,7 +147,7 @@ _LONGLONG_RESULTS = ["cloudaae_x3_planes_bytes", "cloudaae_loss_tail_workspace_b
                      "cloudaae_gemm_bf16_ordered_workspace"]
 
 
-ABI_VERSION = 601     # CLOUDAAE_ABI_VERSION of include/cloudaae_hip.h (tests/test_capi_symbols.py compares the two)
+ABI_VERSION = 602     # CLOUDAAE_ABI_VERSION of include/cloudaae_hip.h (tests/test_capi_symbols.py compares the two)
 
 
 class HipLibraryError(RuntimeError):

@@ -45,8 +45,8 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * revision must not call in -- check cloudaae_version() == CLOUDAAE_ABI_VERSION after loading (the Python host
  * does, cloudaae_amd/_lib.py).  500: round 5 (fully connected entry points take up to 128 rows; tickets / partials
  * queries take M; no y_zeroed argument).  600: round 6 (cloudaae_knn_hinted added; nothing else changed).
- * 601: cloudaae_selftest_div_by added. */
-#define CLOUDAAE_ABI_VERSION 601
+ * 601: cloudaae_selftest_div_by added.  602: cloudaae_icp_point_to_point and cloudaae_f64_to_f32 added. */
+#define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
 /* Development knobs (kernel A/B choices and launch shapes for tests and sweeps; none is needed in normal use):
@@ -691,6 +691,32 @@ int cloudaae_hidden_point_removal(int b, int n1, const float *flipped, const flo
 int cloudaae_hidden_point_removal_rows(int b, int n1, const float *flipped, const float *org,
                                        unsigned long long seed, int rows, float *visible, long long *num_vis,
                                        int *visible_id, int *row_src, void *workspace, cloudaae_stream_t stream);
+
+/* ---- pose refinement: point-to-point ICP (evaluate_cloudAAE_ycbv.py:606-628) ---- */
+
+/* Batched point-to-point ICP with open3d's registration_icp semantics (TransformationEstimationPointToPoint without
+ * scaling), run as a schedule of `rounds` calls whose correspondence radius starts at `radius` and is multiplied by
+ * `decay` after each call; each call starts from the previous call's transform and stops after max_iteration updates
+ * or when |d fitness| < relative_fitness and |d rmse| < relative_rmse.  All arithmetic is float64 ("Pose
+ * refinement", has the definition).  Per cloud c:
+ *   src: m points (x, y, z) at src + c*src_cloud_stride + i*src_point_stride (the object model, object frame);
+ *   dst: n points likewise (the scene, camera frame); strides in floats, >= 3 per point;
+ *   rot_axag [b,3], trans [b,3]: the initial pose (axis-angle, Rodrigues; a zero vector is the identity);
+ *   transform [b,4,4] f64 row-major (last row 0 0 0 1), rot_out [b,3] f64 (axis-angle of the result, angle in
+ *   [0, pi]), trans_out [b,3] f32 (its translation), fitness [b] and rmse [b] f64 of the last round,
+ *   iterations [b,rounds] int (updates performed in each round; may be NULL when rounds == 0).
+ * rounds == 0 returns the initial transform with the statistics of its correspondences at `radius`.
+ * Limits: 1 <= m <= 4096, 1 <= n <= 4096 (CLOUDAAE_ICP_MAX_POINTS), rounds >= 0, max_iteration >= 0, radius > 0,
+ * 0 < decay <= 1.  The result of a cloud does not depend on the rest of the batch and is bit-reproducible. */
+#define CLOUDAAE_ICP_MAX_POINTS 4096
+int cloudaae_icp_point_to_point(int b, int m, const float *src, int src_point_stride, long long src_cloud_stride,
+                                int n, const float *dst, int dst_point_stride, long long dst_cloud_stride,
+                                const float *rot_axag, const float *trans, double radius, double decay, int rounds,
+                                int max_iteration, double relative_fitness, double relative_rmse,
+                                double *transform, double *rot_out, float *trans_out, double *fitness,
+                                double *rmse, int *iterations, cloudaae_stream_t stream);
+/* y[i] = (float)x[i], round to nearest even (an f64 result handed to an fp32 consumer, e.g. a loss kernel). */
+int cloudaae_f64_to_f32(long long n, const double *x, float *y, cloudaae_stream_t stream);
 
 #ifdef __cplusplus
 }
