@@ -115,6 +115,9 @@ _SIGNATURES = {
     "cloudaae_icp_point_to_point": [_I, _I, _P, _I, _L, _I, _P, _I, _L, _P, _P, _D, _D, _I, _I, _D, _D, _P, _P, _P,
                                     _P, _P, _P, _P],
     "cloudaae_f64_to_f32": [_L, _P, _P, _P],
+    "cloudaae_frame_segments": [_I, _I, _I, _P, _P, _P, _I, _P, _P, _F, _P, _P, _P, _P, _L, _P],
+    "cloudaae_radius_outlier": [_I, _P, _P, _L, _I, _F, _I, _P, _P, _P, _P, _P, _L, _P],
+    "cloudaae_ragged_fps": [_I, _P, _P, _L, _I, _P, _P, _P, _P, _L, _P],
 }
 
 
@@ -328,6 +331,11 @@ def lib():
             getattr(cdll, fn).restype = ctypes.c_longlong
         cdll.cloudaae_hpr_workspace_bytes.restype = ctypes.c_longlong
         cdll.cloudaae_hpr_workspace_bytes.argtypes = [_I, _I]
+        for q, sig in (("cloudaae_frame_segments_workspace_bytes", [_I, _I, _I, _I]),
+                       ("cloudaae_radius_outlier_workspace_bytes", [_I, _L]),
+                       ("cloudaae_ragged_fps_workspace_bytes", [_L])):
+            getattr(cdll, q).argtypes = sig
+            getattr(cdll, q).restype = ctypes.c_longlong
         cdll.cloudaae_gemm_f32_splits.argtypes = [_I, _I, _I]
         cdll.cloudaae_gemm_f32_splits.restype = ctypes.c_int
         cdll.cloudaae_gemm_bf16_splits.argtypes = [_I, _I, _I]

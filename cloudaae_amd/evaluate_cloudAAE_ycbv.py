@@ -5,14 +5,22 @@ What is mirrored: the eval-mode forward (batch-norm statistics from the moving a
 the 4N -> N farthest point sampling of the reconstruction + gather + Chamfer against the first N
 observed points (:449-451), the translation error of the prediction and of the plain centroid
 (:455-460), the SO(3) error (:468-474), and on request the ICP refinement of the predicted pose against the first N
-inlier points (:606-628, open3d's point-to-point registration_icp; here utils/icp.py, one HIP launch).  What is NOT:
-reading the YCB-Video test frames and the result files (out of scope).
+inlier points (:606-628, open3d's point-to-point registration_icp; here utils/icp.py, one HIP launch).  The input side, from the
+YCB-Video test records (<seq>_pcnn.tfrecord) to the element, is element_from_frames (utils/segment.py on the GPU,
+:125-335); main() is the reference's command line without the visualisation.  What is NOT: the RGB channels, the
+result files.
 
     graph = T.TrainGraph(...); graph.restore("model.ckpt")
     out = evaluate_batch(graph, element)       # element: xyz_inlier, visiblePoints_org, class_id,
                                                #          translation, axisangle (device tensors)
     out = evaluate_batch(graph, element, icp=True) # + obj_batch [B,M,>=3]: adds the *_icp outputs
 """
+import argparse
+import math
+import os
+import sys
+
+import numpy as np
 import torch
 
 from . import _lib
@@ -22,6 +30,7 @@ from .tf_ops.sampling import tf_sampling
 from .train_cloudAAE_ycbv import NUM_CLASS
 from .utils import _functions as F
 from .utils import icp as icp_util
+from .utils import segment as seg_util
 
 
 def evaluate_batch(graph, element, replay=False, icp=None):
@@ -137,3 +146,136 @@ def _refine(element, scene, rot_pred, trans_pred, translation, params):
                 fitness_icp=r['fitness'], inlier_rmse_icp=r['inlier_rmse'], iterations_icp=r['iterations'],
                 trans_loss_icp=trans_loss, trans_loss_perSample_icp=trans_per, axag_loss_icp=axag_loss,
                 axag_loss_perSample_icp=axag_per)
+
+
+# ---- the input side: frames -> element (:125-335) -------------------------------------------------------------------
+
+# the test sequences of each class (:43-63)
+VALID_SEQ_ID = [[48, 51, 55, 56], [50, 54, 59], [49, 51, 54, 55, 58], [50, 51, 53, 55, 57, 59], [50, 52],
+                [48, 49, 52, 59], [58], [58], [49, 53, 59], [50, 56], [52, 56, 58], [51, 54, 55, 57], [49, 53],
+                [48, 55], [50, 54, 56, 59], [55], [51], [57, 59], [48, 54], [48, 57], [57]]
+
+
+def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, device=None):
+    """create_tfrecord_dataset (:287-335) on decoded frame records (tfrecord_io.decode_frame): the frames that hold
+    target_cls, their target_cls segment, the mean-distance filter, radius outlier removal, FPS_random of the inliers
+    and of the filtered points from seeded starts, the > 100 and >= num_point rules, quat2axangle, the object model,
+    its hidden point removal (centre 0, 0.8 pi).  obj_models: [21, 2048, 6] float32 (numpy or device tensor).
+    Returns the element evaluate_batch takes (device tensors: xyz_inlier [B,N,3], xyz, visiblePoints_org
+    [B,2049,3], class_id [B], translation [B,3], axisangle [B,3] float64, obj_batch [B,2048,6]) plus seq_id,
+    frame_id and num_valid_points_in_segment [B] (numpy); None when no segment survives."""
+    from .train_cloudAAE_ycbv import get_object_model, get_rotation_matrix, transform_object_model
+    from .utils import hidden_point_removal as hpr
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    frames = [f for f in frames if int(f["class_one_hot"][target_cls]) == 1]      # :294
+    if not frames:
+        return None
+    shapes = {f["depth"].shape for f in frames}
+    require(len(shapes) == 1, "frames of one call must share their size")
+    depth = np.stack([f["depth"] for f in frames])
+    label = np.stack([f["label"] for f in frames])
+    intr = np.array([[f["fx"], f["fy"], f["cx"], f["cy"], f["factor_depth"]] for f in frames], np.float32)
+    r = seg_util.extract_segments(depth, label, intr, classes=[[target_cls]] * len(frames),
+                                  quaternions=np.stack([f["quaternions"] for f in frames]),
+                                  translations=np.stack([f["translations"] for f in frames]), num_point=num_point,
+                                  device=device)
+    smp = seg_util.sample_segments(r, num_point, seed=seed)
+    keep = np.nonzero(r.kept)[0]
+    if len(keep) == 0:
+        return None
+    sel = torch.from_numpy(keep).to(device)
+    B = len(keep)
+    el = dict(xyz_inlier=smp["xyz_inlier"].index_select(0, sel), xyz=smp["xyz"].index_select(0, sel),
+              class_id=torch.full((B,), int(target_cls), dtype=torch.int64, device=device),
+              translation=torch.from_numpy(r.translation[keep]).to(device),
+              axisangle=torch.from_numpy(np.stack([seg_util.quat2axag(q) for q in r.quaternion[keep]])
+                                         .astype(np.float64)).to(device))
+    models = obj_models if isinstance(obj_models, torch.Tensor) else torch.from_numpy(np.asarray(obj_models, np.float32))
+    models = models.to(device=device, dtype=torch.float32).contiguous()
+    el["obj_batch"] = models.index_select(0, el["class_id"]).contiguous()
+    x = dict(class_id=el["class_id"], translation=el["translation"], axisangle=el["axisangle"].clone())
+    x = transform_object_model(get_rotation_matrix(get_object_model(x, models)))
+    x = hpr.hidden_point_removal_org(hpr.sphericalFlip_org(x, None, 0.8 * math.pi), seed=int(seed))
+    el["visiblePoints_org"] = x["visiblePoints_org"]
+    el["seq_id"] = np.array([int(frames[int(r.frame[i])]["seq_id"]) for i in keep], np.int64)
+    el["frame_id"] = np.array([int(frames[int(r.frame[i])]["frame_id"]) for i in keep], np.int64)
+    el["num_valid_points_in_segment"] = r.num_valid_points_in_segment[keep]
+    return el
+
+
+def _take(el, lo, hi):
+    return {k: v[lo:hi] for k, v in el.items()}
+
+
+def main(argv=None):
+    """evaluate_cloudAAE_ycbv.py's command line (:688-716, :356-657) without the visualisation and without RGB.
+    Reads <data_dir>/<seq>_pcnn.tfrecord of the class's test sequences (:43-63) file after file, in record order (the
+    reference interleaves them at random with sample_from_datasets), and prints the per-batch and the final loss
+    lines (:568, :652-657).  A last batch smaller than --batch_size is not evaluated (the reference's reshape to
+    BATCH_SIZE, :338, cannot take it).  --icp adds the refined pose's losses."""
+    from . import tfrecord_io
+    from . import train_cloudAAE_ycbv as T
+    p = argparse.ArgumentParser()
+    p.add_argument("--data_dir", default="ycb_video_data_tfRecords")
+    p.add_argument("--object_model", default=None,
+                   help="obj_models.tfrecords [default: <data_dir>/../object_model_tfrecord/obj_models.tfrecords]")
+    p.add_argument("--trained_model", required=True, help="checkpoint prefix (TrainGraph.restore)")
+    p.add_argument("--target_cls", type=int, default=9)
+    p.add_argument("--num_point", type=int, default=256)
+    p.add_argument("--batch_size", type=int, default=1)
+    p.add_argument("--icp", action="store_true")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--frames_per_launch", type=int, default=8)
+    p.add_argument("--gpu", type=int, default=0)
+    args = p.parse_args(argv)
+    torch.cuda.set_device(args.gpu)
+    obj_path = args.object_model or os.path.join(os.path.dirname(os.path.abspath(args.data_dir)),
+                                                 "object_model_tfrecord", "obj_models.tfrecords")
+    models, _ = tfrecord_io.read_and_decode_obj_model(obj_path)
+    graph = T.TrainGraph({"num_point": args.num_point, "gpu": args.gpu}, {}, {"batch_size": args.batch_size})
+    graph.restore(args.trained_model)
+    files = [os.path.join(args.data_dir, str(i).zfill(4) + "_pcnn.tfrecord") for i in VALID_SEQ_ID[args.target_cls]]
+    files = [f for f in files if os.path.exists(f)]
+    require(files, "no <seq>_pcnn.tfrecord of class %d under %s" % (args.target_cls, args.data_dir))
+    pending, batch_idx, tot_trans, tot_axag, n_launch = None, 0, 0.0, 0.0, 0
+
+    def frames():
+        for fn in files:
+            buf = []
+            for rec in tfrecord_io.tf_record_iterator(fn):
+                buf.append(tfrecord_io.decode_frame(rec))
+                if len(buf) == args.frames_per_launch:
+                    yield buf
+                    buf = []
+            if buf:
+                yield buf
+
+    for chunk in frames():
+        el = element_from_frames(chunk, args.target_cls, args.num_point, models, seed=args.seed + n_launch)
+        n_launch += 1
+        if el is None:
+            continue
+        pending = el if pending is None else {k: (torch.cat([pending[k], v]) if isinstance(v, torch.Tensor)
+                                                  else np.concatenate([pending[k], v])) for k, v in el.items()}
+        while len(pending["class_id"]) >= args.batch_size:
+            b = _take(pending, 0, args.batch_size)
+            pending = _take(pending, args.batch_size, len(pending["class_id"]))
+            out = evaluate_batch(graph, {k: v for k, v in b.items() if isinstance(v, torch.Tensor)}, icp=args.icp)
+            tl, al = float(out["trans_loss"]), float(out["axag_loss"])
+            tot_trans += tl
+            tot_axag += al
+            line = "Validation batch %d seq_id %d frame_id %d trans_loss %f rot_loss %f" % (
+                batch_idx, int(b["seq_id"][0]), int(b["frame_id"][0]), tl, al)
+            if args.icp:
+                line += " trans_loss_icp %f rot_loss_icp %f" % (float(out["trans_loss_icp"]), float(out["axag_loss_icp"]))
+            print(line)
+            batch_idx += 1
+    print("batch size %d" % batch_idx)
+    if batch_idx:
+        print("trans_loss %f axag_loss %f" % (tot_trans / batch_idx, tot_axag / batch_idx))
+    sys.stdout.flush()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

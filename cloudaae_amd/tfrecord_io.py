@@ -348,3 +348,85 @@ class PoseRecords(object):
             sel = order[i:i + batch_size]
             yield {"translation": self.translation[sel], "axisangle": self.axisangle[sel],
                    "class_id": self.class_id[sel]}
+
+
+# ---- YCB-Video test frames (<seq>_pcnn.tfrecord, evaluate_cloudAAE_ycbv.py:125-161) --------------------------------
+FRAME_NUM_CLASS = 21
+
+
+def decode_frame(serialized):
+    """evaluate_cloudAAE_ycbv.py:125-161: image uint8 [H,W,3] (a 4-channel image is cut to 3), depth uint16 [H,W]
+    (little endian), label uint8 [H,W], quaternions [21,4] and translations [21,3] float32, class_one_hot [21]
+    int64, seq_id / frame_id int64, fx, fy, cx, cy, factor_depth float32."""
+    ex = parse_example(serialized)
+    out = {}
+    ishape = tuple(int(v) for v in ex["image_shape"])
+    if len(ishape) != 3:
+        raise ValueError("image_shape must have 3 entries")
+    image = np.frombuffer(ex["image"][0], dtype=np.uint8).reshape(ishape)
+    out["image"] = image[:, :, :3] if ishape[2] == 4 else image
+    out["depth"] = np.frombuffer(ex["depth"][0], dtype="<u2").reshape(tuple(int(v) for v in ex["depth_shape"]))
+    out["depth"] = out["depth"].astype(np.uint16)
+    out["label"] = np.frombuffer(ex["label"][0], dtype=np.uint8).reshape(tuple(int(v) for v in ex["label_shape"]))
+    q, t, c = ex["quaternions"], ex["translations"], ex["class_one_hot"]
+    if q.size != FRAME_NUM_CLASS * 4 or t.size != FRAME_NUM_CLASS * 3 or c.size != FRAME_NUM_CLASS:
+        raise ValueError("unexpected pose feature sizes in frame record")
+    out["quaternions"] = q.reshape(FRAME_NUM_CLASS, 4).astype(np.float32)
+    out["translations"] = t.reshape(FRAME_NUM_CLASS, 3).astype(np.float32)
+    out["class_one_hot"] = c.astype(np.int64)
+    for key in ("seq_id", "frame_id"):
+        out[key] = np.int64(ex[key][0])
+    for key in ("fx", "fy", "cx", "cy", "factor_depth"):
+        out[key] = np.float32(ex[key][0])
+    return out
+
+
+def _put_varint(v):
+    v &= (1 << 64) - 1                                    # int64 two's complement, as protobuf writes negatives
+    out = bytearray()
+    while True:
+        b = v & 0x7F
+        v >>= 7
+        if v:
+            out.append(b | 0x80)
+        else:
+            out.append(b)
+            return bytes(out)
+
+
+def _put_field(num, payload):
+    return _put_varint((num << 3) | 2) + _put_varint(len(payload)) + payload
+
+
+def _encode_feature(value):
+    """bytes / list of bytes -> BytesList; float arrays or floats -> FloatList; ints -> Int64List (packed)."""
+    if isinstance(value, (bytes, bytearray)):
+        value = [bytes(value)]
+    if isinstance(value, list) and value and isinstance(value[0], (bytes, bytearray)):
+        return _put_field(1, b"".join(_put_field(1, bytes(v)) for v in value))
+    arr = np.asarray(value)
+    if arr.dtype.kind == "f":
+        return _put_field(2, _put_field(1, arr.astype("<f4").ravel().tobytes()))
+    if arr.dtype.kind in "iub":
+        return _put_field(3, _put_field(1, b"".join(_put_varint(int(v)) for v in arr.ravel())))
+    raise TypeError("cannot encode a feature of dtype %s" % arr.dtype)
+
+
+def encode_example(features):
+    """tf.train.Example bytes of {name: value} (the inverse of parse_example; see _encode_feature for the types)."""
+    entries = b"".join(_put_field(1, _put_field(1, k.encode("utf-8")) + _put_field(2, _encode_feature(v)))
+                       for k, v in features.items())
+    return _put_field(1, entries)
+
+
+def write_records(path, payloads):
+    """A TFRecord file of the given payloads, with masked CRC-32C (what tf.python_io.TFRecordWriter writes)."""
+    with open(path, "wb") as f:
+        for p in payloads:
+            head = struct.pack("<Q", len(p))
+            f.write(head + struct.pack("<I", masked_crc32c(head)) + p + struct.pack("<I", masked_crc32c(p)))
+
+
+def read_frames(path, verify=False):
+    """Every frame record of a <seq>_pcnn.tfrecord file, decoded (decode_frame), in file order."""
+    return [decode_frame(rec) for rec in tf_record_iterator(path, verify=verify)]

@@ -45,7 +45,9 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * revision must not call in -- check cloudaae_version() == CLOUDAAE_ABI_VERSION after loading (the Python host
  * does, cloudaae_amd/_lib.py).  500: round 5 (fully connected entry points take up to 128 rows; tickets / partials
  * queries take M; no y_zeroed argument).  600: round 6 (cloudaae_knn_hinted added; nothing else changed).
- * 601: cloudaae_selftest_div_by added.  602: cloudaae_icp_point_to_point and cloudaae_f64_to_f32 added. */
+ * 601: cloudaae_selftest_div_by added.  602: cloudaae_icp_point_to_point and cloudaae_f64_to_f32 added; later, still
+ * under 602 (additions only, no existing argument list or layout changed): cloudaae_frame_segments,
+ * cloudaae_radius_outlier, cloudaae_ragged_fps and their workspace queries. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -717,6 +719,42 @@ int cloudaae_icp_point_to_point(int b, int m, const float *src, int src_point_st
                                 double *rmse, int *iterations, cloudaae_stream_t stream);
 /* y[i] = (float)x[i], round to nearest even (an f64 result handed to an fp32 consumer, e.g. a loss kernel). */
 int cloudaae_f64_to_f32(long long n, const double *x, float *y, cloudaae_stream_t stream);
+
+/* ---- evaluation inputs from RGB-D frames (evaluate_cloudAAE_ycbv.py:164-271) ---- */
+
+/* The segments of F frames, as the reference's evaluation cuts them ("Frame segments", has the definition):
+ *   depth [f,h,w] uint16, label [f,h,w] uint8 (class + 1; 0 = none), intrinsics [f,5] float (fx, fy, cx, cy,
+ *   factor_depth); segment i is class seg_class[i] (0-based) of frame seg_frame[i] (a pair named twice: only its last
+ *   segment gets the points, the others are empty).
+ * Per segment: the pixels whose label - 1 is the class and whose depth is not 0, back-projected in fp32; their mean
+ * (the fp64 sum in pixel order / count, rounded to fp32) -> mean [s,3]; the points within `threshold` of it, in pixel
+ * order, packed segment after segment -> xyz [f*h*w, 3] at offsets[i] .. offsets[i+1] (offsets [s+1] int, device;
+ * num_point_after_filter = the difference).  workspace: cloudaae_frame_segments_workspace_bytes(f, h, w, s) bytes.
+ * Limits: f*h*w <= 2^28.  A memset and ten launches; bit-reproducible; a segment's result does not depend on the batch. */
+long long cloudaae_frame_segments_workspace_bytes(int f, int h, int w, int s);
+int cloudaae_frame_segments(int f, int h, int w, const uint16_t *depth, const uint8_t *label, const float *intrinsics,
+                            int s, const int *seg_frame, const int *seg_class, float threshold, int *offsets,
+                            float *xyz, float *mean, void *workspace, long long workspace_bytes,
+                            cloudaae_stream_t stream);
+/* open3d's remove_radius_outlier(nb_points, radius) on each of s packed point sets (offsets [s+1] device, the points
+ * at xyz, at most max_points in all): point j keeps when more than nb_points points of its set (itself included) lie
+ * at d^2 < r^2, d^2 = ((dx^2 + dy^2) + dz^2) in double and r = (double)radius.  A set with fewer than min_keep
+ * keepers keeps all its points.  Outputs: in_offsets [s+1], in_index [max_points] (each inlier's index within its
+ * set), in_xyz [max_points,3] (packed like the input), num_valid [s] = the inliers whose index is not 0 (numpy's
+ * count_nonzero of the index list, :280).  workspace: cloudaae_radius_outlier_workspace_bytes(s, max_points). */
+long long cloudaae_radius_outlier_workspace_bytes(int s, long long max_points);
+int cloudaae_radius_outlier(int s, const int *offsets, const float *xyz, long long max_points, int nb_points,
+                            float radius, int min_keep, int *in_offsets, int *in_index, float *in_xyz, int *num_valid,
+                            void *workspace, long long workspace_bytes, cloudaae_stream_t stream);
+/* FPS_random of the reference (:226-247) on each of s packed point sets, from starts[i] (device): idx[i,0] = start;
+ * idx[i,j] = the first index of the largest dist, then dist = min(dist, d(idx[i,j])), with
+ * d = (dx^2 + dy^2) + dz^2 in double on the widened coordinates; out_xyz [s,k,3] = the points picked.  k may exceed
+ * the set's size (the picks then repeat index 0 once every distance is 0).  A set that is empty or whose start lies
+ * outside [0, n) gives idx -1 and zeros.  workspace: cloudaae_ragged_fps_workspace_bytes(max_points). */
+long long cloudaae_ragged_fps_workspace_bytes(long long max_points);
+int cloudaae_ragged_fps(int s, const int *offsets, const float *xyz, long long max_points, int k, const int *starts,
+                        int *idx, float *out_xyz, void *workspace, long long workspace_bytes,
+                        cloudaae_stream_t stream);
 
 #ifdef __cplusplus
 }
