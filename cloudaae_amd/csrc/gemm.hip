@@ -35,23 +35,6 @@ constexpr int GEMM_BK = 16;
 constexpr int GEMM_THREADS = 256;
 #define GEMM_ATTR
 
-enum { EPI_STORE = 0, EPI_ACCUM = 1, EPI_ATOMIC = 2 };
-
-// A row-major matrix whose logical columns are FOLDED into stacked row blocks: logical (r, c) lives
-// at physical row (c >> shift) * rows + r, column c & (width - 1).  That is how the edge convolution's
-// [2*cin, cout] kernel looks when it is used as [cin, 2*cout] = [W_centre | W_neighbour]: with it the
-// P/Q products, their dX and their dW are ONE product each instead of two (edgeconv.hip).
-// shift < 0: no folding.
-struct Fold {
-    int shift, rows;
-};
-__device__ __forceinline__ size_t fold_off(int r, int c, int ld, Fold f)
-{
-    if (f.shift < 0)
-        return (size_t)r * ld + c;
-    return (size_t)((c >> f.shift) * f.rows + r) * ld + (c & ((1 << f.shift) - 1));
-}
-
 // One operand panel: ROWS "outer" indices (m for A, n for B) x BK k-values.
 // KC = true : memory is [outer][k] (k contiguous)   -> LDS [ROWS][BK+1]
 // KC = false: memory is [k][outer] (outer contiguous)-> LDS [BK][ROWS]
@@ -382,45 +365,6 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_f32_tn_group_kernel(GemmGro
                                                      (vid / j.tiles_x) * 64, (vid % j.tiles_x) * 128, slice);
 }
 
-template <int BM, int BN, int WM, int WN, bool FAST>
-static void launch_fast(bool ta, bool tb, dim3 grid, hipStream_t s, int M, int N, int K, const float *A,
-                        int lda, const float *B, int ldb, float *C, int ldc, const float *bias, int epi,
-                        int kchunk, int vecA, int vecB, Fold fb, Fold fc, double *cs, long long cslice)
-{
-    dim3 block(GEMM_THREADS);
-    if (!ta && !tb)
-        hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, false, false, FAST>), grid, block, 0, s, M, N, K,
-                           A, lda, B, ldb, C, ldc, bias, epi, kchunk, vecA, vecB, fb, fc, cs, cslice);
-    else if (!ta && tb)
-        hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, false, true, FAST>), grid, block, 0, s, M, N, K,
-                           A, lda, B, ldb, C, ldc, bias, epi, kchunk, vecA, vecB, fb, fc, cs, cslice);
-    else if (ta && !tb)
-        hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, true, false, FAST>), grid, block, 0, s, M, N, K,
-                           A, lda, B, ldb, C, ldc, bias, epi, kchunk, vecA, vecB, fb, fc, cs, cslice);
-    else
-        hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, true, true, FAST>), grid, block, 0, s, M, N, K,
-                           A, lda, B, ldb, C, ldc, bias, epi, kchunk, vecA, vecB, fb, fc, cs, cslice);
-}
-
-template <int BM, int BN, int WM, int WN>
-static void launch_cfg(bool ta, bool tb, dim3 grid, hipStream_t s, int M, int N, int K, const float *A,
-                       int lda, const float *B, int ldb, float *C, int ldc, const float *bias, int epi,
-                       int kchunk, int vecA, int vecB, Fold fb, Fold fc, double *cs, long long cslice)
-{
-    // every tile and every K-slab whole, both operands float4-loadable: the predicate-free kernel
-    const bool fast = M % BM == 0 && N % BN == 0 && K % kchunk == 0 && kchunk % GEMM_BK == 0 && vecA && vecB;
-    if (fast)
-        launch_fast<BM, BN, WM, WN, true>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk,
-                                          vecA, vecB, fb, fc, cs, cslice);
-    else
-        launch_fast<BM, BN, WM, WN, false>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk,
-                                           vecA, vecB, fb, fc, cs, cslice);
-}
-
-} // namespace cloudaae
-
-namespace cloudaae {
-
 // C[r][c] = ((ws[0][r][c] + ws[1][r][c]) + ... ) + bias[c]: the slices of a product cut over K, in slice order.
 __global__ __launch_bounds__(256) void gemm_slices_sum_kernel(long long total, int N, int splits, const float *__restrict__ ws,
                                                               float *__restrict__ C, int ldc, const float *__restrict__ bias,
@@ -439,16 +383,16 @@ __global__ __launch_bounds__(256) void gemm_slices_sum_kernel(long long total, i
 }
 
 int gemm_slices_sum(const char *name, int M, int N, int splits, const float *ws, float *C, int ldc, const float *bias,
-                    hipStream_t s, int fold_shift, int fold_rows)
+                    hipStream_t s, Fold fold)
 {
     const long long total = (long long)M * N;
     hipLaunchKernelGGL(gemm_slices_sum_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, N, splits, ws,
-                       C, ldc, bias, Fold{fold_shift, fold_rows});
+                       C, ldc, bias, fold);
     CLOUDAAE_CHECK_LAUNCH(name);
     return 0;
 }
 
-// Tile shape and split-K slice count of a product (shared by the launcher and the query below).
+// Tile shape and split-K slice count of a product (gemm_cut: shared by the launcher and the queries below).
 static void gemm_plan(int M, int N, int K, int &BM, int &BN, int &splits, bool ordered = false)
 {
     // tile shape: small-batch FC rows -> 32-row tiles; narrow outputs -> 64 columns; a dimension
@@ -498,131 +442,68 @@ static void gemm_plan(int M, int N, int K, int &BM, int &BN, int &splits, bool o
     splits = 1;
     const long long tiles = (long long)tm * tn;
     const int resident = 256 * (BM == 32 ? 2 : (BN == 64 || BM == 64) ? (BN == 64 ? 6 : 5) : 3);   // (32-row tiles: 2 measured best)
-    if (tiles < 256 && K >= 128) {
-        splits = (int)((tiles <= 4 ? 256 : resident) / tiles);
-        const int max_splits = K / 64 > 0 ? K / 64 : 1;
-        if (splits > max_splits)
-            splits = max_splits;
-        if (splits > 1024)
-            splits = 1024;
-        if (splits < 1)
-            splits = 1;
-        if (splits > 8)
-            splits = splits / 8 * 8;      // whole slices per XCD (the kernel then keeps a slice's tiles on one XCD)
-    }
+    if (tiles < 256 && K >= 128)        // (at most 1024 slices)
+        splits = whole_xcd_splits((int)((tiles <= 4 ? 256 : resident) / tiles), K / 64 < 1024 ? K / 64 : 1024);
     // deterministic mode (cloudaae_set_knob("CLOUDAAE_DETERMINISTIC", 1)): a product that would add its K slices with
     // atomics stays whole (and pays with idle CUs); the slice-ordered variant (cloudaae_gemm_f32_ordered) keeps its cut
     if (!ordered && CLOUDAAE_KNOB("CLOUDAAE_DETERMINISTIC", 0) != 0)
         splits = 1;
 }
 
+// The fp32 family of gemm.h's launcher.
+struct GemmF32 {
+    static constexpr int BK = GEMM_BK;
+    static constexpr auto plan = &gemm_plan;
+    static constexpr const char *ws_missing =
+        "this product is cut over K: workspace missing or smaller than cloudaae_gemm_f32_ordered_workspace";
+
+    // every tile and every K-slab whole, both operands float4-loadable: the predicate-free kernel
+    static bool fast(int BM, int BN, bool, const GemmArgs &g)
+    {
+        return g.M % BM == 0 && g.N % BN == 0 && g.K % g.kchunk == 0 && g.kchunk % GEMM_BK == 0 && g.vecA && g.vecB;
+    }
+
+    template <int BM, int BN, int WM, int WN, bool TA, bool TB, bool FAST>
+    static void kernel(dim3 grid, hipStream_t s, const GemmArgs &g)
+    {
+        hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, TA, TB, FAST>), grid, dim3(GEMM_THREADS), 0, s, g.M, g.N, g.K,
+                           g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.bias, g.epi, g.kchunk, g.vecA, g.vecB, g.fb, g.fc,
+                           g.colstats, g.cslice);
+    }
+
+    static void tiles(int BM, int BN, bool ta, bool tb, dim3 grid, hipStream_t s, const GemmArgs &g)
+    {
+        if (BM == 32)
+            gemm_launch_tile<GemmF32, 32, 128, 1, 4>(ta, tb, grid, s, g);
+        else if (BN == 160)
+            gemm_launch_tile<GemmF32, 128, 160, 4, 1>(ta, tb, grid, s, g);
+        else if (BM == 64 && BN == 64)
+            gemm_launch_tile<GemmF32, 64, 64, 2, 2>(ta, tb, grid, s, g);
+        else if (BN == 64)
+            gemm_launch_tile<GemmF32, 128, 64, 4, 1>(ta, tb, grid, s, g);
+        else if (BM == 64)
+            gemm_launch_tile<GemmF32, 64, 128, 2, 2>(ta, tb, grid, s, g);
+        else
+            gemm_launch_tile<GemmF32, 128, 128, 2, 2>(ta, tb, grid, s, g);
+    }
+};
+
 } // namespace cloudaae
 
 using namespace cloudaae;
 
-CLOUDAAE_API int cloudaae_gemm_f32_splits(int M, int N, int K)
-{
-    if (M <= 0 || N <= 0 || K <= 0)
-        return 1;
-    int BM, BN, splits;
-    gemm_plan(M, N, K, BM, BN, splits);
-    const int kchunk = ceil_div(ceil_div(K, splits), GEMM_BK) * GEMM_BK;
-    return ceil_div(K, kchunk);
-}
+// the cut of a product, as the launches below will make it (gemm_cut)
+CLOUDAAE_API int cloudaae_gemm_f32_splits(int M, int N, int K) { return gemm_splits<GemmF32>(M, N, K); }
+CLOUDAAE_API long long cloudaae_gemm_f32_ordered_workspace(int M, int N, int K) { return gemm_ordered_workspace<GemmF32>(M, N, K); }
+CLOUDAAE_API int cloudaae_gemm_f32_colstats_parts(int M, int N, int K) { return gemm_colstats_parts<GemmF32>(M, N, K); }
 
-// The launcher behind cloudaae_gemm_f32 and the folded products of edgeconv.hip.
-// fold_b / fold_c: 0, or the power-of-two width at which B's / C's logical columns fold into stacked
-// row blocks (see Fold); the folded matrix has leading dimension == width.
+// The launcher behind cloudaae_gemm_f32 and the folded products of edgeconv.hip (see gemm.h).
 int cloudaae::gemm_f32_launch(const char *name, int trans_a, int trans_b, int M, int N, int K, const float *A, int lda,
                               const float *B, int ldb, float *C, int ldc, const float *bias, int accumulate,
                               int fold_b, int fold_c, hipStream_t s, double *colstats, float *ordered_ws)
 {
-    CLOUDAAE_REQUIRE(M >= 0 && N >= 0 && K >= 0, name, "negative size");
-    if (M == 0 || N == 0)
-        return 0;
-    CLOUDAAE_REQUIRE(lda >= (trans_a ? M : K), name, "leading dimension too small");
-    CLOUDAAE_REQUIRE(fold_b ? ldb == fold_b : ldb >= (trans_b ? K : N), name, "leading dimension too small");
-    CLOUDAAE_REQUIRE(fold_c ? ldc == fold_c : ldc >= N, name, "leading dimension too small");
-    CLOUDAAE_REQUIRE((fold_b & (fold_b - 1)) == 0 && (fold_c & (fold_c - 1)) == 0 && fold_b % 4 == 0 &&
-                         fold_c % 4 == 0, name, "fold width must be a power of two >= 4");
-    Fold fb = {-1, 0}, fc = {-1, 0};
-    if (fold_b) {           // B's folded index: n for [K][N] storage, k for [N][K] storage
-        fb.shift = __builtin_ctz((unsigned)fold_b);
-        fb.rows = trans_b ? N : K;
-    }
-    if (fold_c) {
-        fc.shift = __builtin_ctz((unsigned)fold_c);
-        fc.rows = M;
-    }
-
-    int BM, BN, splits;
-    gemm_plan(M, N, K, BM, BN, splits, ordered_ws != nullptr);
-    const int tm = ceil_div(M, BM), tn = ceil_div(N, BN);
-    CLOUDAAE_REQUIRE(tm <= 65535, name, "M too large");
-    CLOUDAAE_REQUIRE(colstats == nullptr || (splits == 1 && accumulate == 0 && !fold_c), name,
-                     "column statistics need an unsplit, overwriting product");
-    int kchunk = K > 0 ? ceil_div(ceil_div(K, splits), GEMM_BK) * GEMM_BK : GEMM_BK;
-    splits = K > 0 ? ceil_div(K, kchunk) : 1;
-    // accumulate: 0 = overwrite C, 1 = add to C, 2 = C is known to hold zeros (the caller cleared
-    // a whole gradient buffer once): plain stores when K is not split, atomics WITHOUT the clear
-    // pass when it is
-    int epi = accumulate == 1 ? EPI_ACCUM : EPI_STORE;
-    // ordered_ws: a product cut over K keeps its slices apart -- slice s stores its [M, N] result at
-    // ordered_ws + s M N -- and a second kernel sums them in slice order (bit-reproducible, unlike the atomics)
-    const bool ordered = ordered_ws != nullptr && splits > 1;
-    CLOUDAAE_REQUIRE(ordered_ws == nullptr || (accumulate == 0 && colstats == nullptr), name,
-                     "slice-ordered products overwrite their output");
-    float *const Cout = C;
-    const int ldc_out = ldc;
-    const float *const bias_out = bias;
-    long long cslice = 0;
-    const Fold fc_out = fc;
-    if (ordered) {
-        C = ordered_ws;
-        ldc = N;
-        bias = nullptr;
-        cslice = (long long)M * N;
-        fc = Fold{-1, 0};               // the slices are plain [M, N] blocks; the sum kernel folds the output
-    } else if (splits > 1) {
-        epi = EPI_ATOMIC;
-        if (!accumulate) {  // slices add into a zeroed output
-            if (fold_c)     // the folded output is one contiguous [N/width * M][width] block
-                CLOUDAAE_CHECK_HIP(hipMemsetAsync(C, 0, sizeof(float) * (size_t)M * (size_t)N, s), name);
-            else
-                CLOUDAAE_CHECK_HIP(hipMemset2DAsync(C, sizeof(float) * (size_t)ldc, 0, sizeof(float) * (size_t)N,
-                                                    (size_t)M, s), name);
-        }
-    }
-    const bool a16 = ((uintptr_t)A & 15) == 0 && lda % 4 == 0;
-    const bool b16 = ((uintptr_t)B & 15) == 0 && ldb % 4 == 0;
-    const int vecA = a16 ? 1 : 0, vecB = b16 ? 1 : 0;
-    dim3 grid(tn, tm, splits);
-    const bool ta = trans_a != 0, tb = trans_b != 0;
-    if (BM == 32)
-        launch_cfg<32, 128, 1, 4>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk,
-                                  vecA, vecB, fb, fc, colstats, cslice);
-    else if (BN == 160)
-        launch_cfg<128, 160, 4, 1>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk,
-                                   vecA, vecB, fb, fc, colstats, cslice);
-    else if (BM == 64 && BN == 64)
-        launch_cfg<64, 64, 2, 2>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk,
-                                 vecA, vecB, fb, fc, colstats, cslice);
-    else if (BN == 64)
-        launch_cfg<128, 64, 4, 1>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk,
-                                  vecA, vecB, fb, fc, colstats, cslice);
-    else if (BM == 64)
-        launch_cfg<64, 128, 2, 2>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk,
-                                  vecA, vecB, fb, fc, colstats, cslice);
-    else
-        launch_cfg<128, 128, 2, 2>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk,
-                                   vecA, vecB, fb, fc, colstats, cslice);
-    CLOUDAAE_CHECK_LAUNCH(name);
-    if (ordered) {
-        const int rc = gemm_slices_sum(name, M, N, splits, ordered_ws, Cout, ldc_out, bias_out, s, fc_out.shift, fc_out.rows);
-        if (rc != 0)
-            return rc;
-    }
-    return 0;
+    return gemm_launch<GemmF32>(name, trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, fold_b, fold_c,
+                                s, colstats, ordered_ws);
 }
 
 CLOUDAAE_API int cloudaae_gemm_f32(int trans_a, int trans_b, int M, int N, int K, const float *A,
@@ -633,30 +514,12 @@ CLOUDAAE_API int cloudaae_gemm_f32(int trans_a, int trans_b, int M, int N, int K
                            0, 0, (hipStream_t)stream);
 }
 
-CLOUDAAE_API long long cloudaae_gemm_f32_ordered_workspace(int M, int N, int K)
-{
-    if (M <= 0 || N <= 0 || K <= 0)
-        return 0;
-    int BM, BN, splits;
-    gemm_plan(M, N, K, BM, BN, splits, true);
-    const int kchunk = ceil_div(ceil_div(K, splits), GEMM_BK) * GEMM_BK;
-    splits = ceil_div(K, kchunk);
-    return splits > 1 ? (long long)splits * M * N : 0;
-}
-
 CLOUDAAE_API int cloudaae_gemm_f32_ordered(int trans_a, int trans_b, int M, int N, int K, const float *A, int lda,
                                            const float *B, int ldb, float *C, int ldc, const float *bias,
                                            float *workspace, long long workspace_floats, cloudaae_stream_t stream)
 {
-    const char *name = "cloudaae_gemm_f32_ordered";
-    // (the cut is derived again at every launch, also from development knobs: a buffer sized by an earlier query must
-    //  still cover it)
-    CLOUDAAE_REQUIRE(workspace != nullptr ? workspace_floats >= cloudaae_gemm_f32_ordered_workspace(M, N, K)
-                                          : cloudaae_gemm_f32_ordered_workspace(M, N, K) == 0,
-                     name, "this product is cut over K: workspace missing or smaller than cloudaae_gemm_f32_ordered_workspace");
-    static float dummy_ws;      // (a product that stays whole never touches it; non-NULL selects the ordered plan)
-    return gemm_f32_launch(name, trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, bias, 0, 0, 0, (hipStream_t)stream,
-                           nullptr, workspace != nullptr ? workspace : &dummy_ws);
+    return gemm_ordered<GemmF32>("cloudaae_gemm_f32_ordered", trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, bias, 0,
+                                 workspace, workspace_floats, (hipStream_t)stream);
 }
 
 // the same with the output's logical columns folded into stacked row blocks of width fold_c (0: none; the edge convolution's
@@ -665,22 +528,8 @@ CLOUDAAE_API int cloudaae_gemm_f32_ordered_fold(int trans_a, int trans_b, int M,
                                                 const float *B, int ldb, float *C, int ldc, int fold_c, float *workspace,
                                                 long long workspace_floats, cloudaae_stream_t stream)
 {
-    const char *name = "cloudaae_gemm_f32_ordered_fold";
-    CLOUDAAE_REQUIRE(workspace != nullptr ? workspace_floats >= cloudaae_gemm_f32_ordered_workspace(M, N, K)
-                                          : cloudaae_gemm_f32_ordered_workspace(M, N, K) == 0,
-                     name, "this product is cut over K: workspace missing or smaller than cloudaae_gemm_f32_ordered_workspace");
-    static float dummy_ws;      // (a product that stays whole never touches it; non-NULL selects the ordered plan)
-    return gemm_f32_launch(name, trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, nullptr, 0, 0, fold_c,
-                           (hipStream_t)stream, nullptr, workspace != nullptr ? workspace : &dummy_ws);
-}
-
-CLOUDAAE_API int cloudaae_gemm_f32_colstats_parts(int M, int N, int K)
-{
-    if (M <= 0 || N <= 0 || K <= 0)
-        return 0;
-    int BM, BN, splits;
-    gemm_plan(M, N, K, BM, BN, splits);
-    return splits == 1 ? ceil_div(M, BM) : 0;      // one row of sums per tile row
+    return gemm_ordered<GemmF32>("cloudaae_gemm_f32_ordered_fold", trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc,
+                                 nullptr, fold_c, workspace, workspace_floats, (hipStream_t)stream);
 }
 
 CLOUDAAE_API int cloudaae_gemm_f32_colstats(int trans_a, int trans_b, int M, int N, int K, const float *A, int lda,
@@ -721,12 +570,8 @@ CLOUDAAE_API int cloudaae_gemm_f32_tn_group(int count, const cloudaae_gemm_tn_jo
         //  the chip take 53 us, 128 of 256 k 44 us (step 1.590 -> 1.582 ms); at K = 131072 320 slices of 416 k stay best:
         //  profiles/notes_gemm_f32.md)
         const int kmin = 256;
-        int splits = ((256 * 5) / count) / j.tiles;
-        if (splits > q.K / kmin)
-            splits = q.K / kmin;
-        if (splits > 8)
-            splits = splits / 8 * 8;
-        if (splits < 1 || CLOUDAAE_KNOB("CLOUDAAE_DETERMINISTIC", 0) != 0)
+        int splits = whole_xcd_splits(((256 * 5) / count) / j.tiles, q.K / kmin);
+        if (CLOUDAAE_KNOB("CLOUDAAE_DETERMINISTIC", 0) != 0)
             splits = 1;
         j.kchunk = ceil_div(ceil_div(q.K, splits), GEMM_BK) * GEMM_BK;
         j.splits = ceil_div(q.K, j.kchunk);
@@ -734,13 +579,8 @@ CLOUDAAE_API int cloudaae_gemm_f32_tn_group(int count, const cloudaae_gemm_tn_jo
         j.vecB = (((uintptr_t)q.B & 15) == 0 && q.ldb % 4 == 0) ? 1 : 0;
         j.block0 = blocks;
         blocks += ceil_div(j.tiles * j.splits, 8) * 8;      // (jobs start on a multiple of 8: see the kernel)
-        if (!q.zeroed) {
-            if (q.fold_c)
-                CLOUDAAE_CHECK_HIP(hipMemsetAsync(q.C, 0, sizeof(float) * (size_t)q.M * (size_t)q.N, s), name);
-            else
-                CLOUDAAE_CHECK_HIP(hipMemset2DAsync(q.C, sizeof(float) * (size_t)q.ldc, 0, sizeof(float) * (size_t)q.N,
-                                                    (size_t)q.M, s), name);
-        }
+        if (!q.zeroed)
+            CLOUDAAE_CHECK_HIP(gemm_zero_output(q.C, q.M, q.N, q.ldc, q.fold_c != 0, s), name);
     }
     hipLaunchKernelGGL(gemm_f32_tn_group_kernel, dim3(blocks), dim3(GEMM_THREADS), 0, s, g);
     CLOUDAAE_CHECK_LAUNCH(name);

@@ -31,8 +31,6 @@ constexpr int HB_BK = 64;            // k per slab
 constexpr int HB_LDK = 72;           // bf16 per staged row (64 + 8 pad)
 constexpr int HB_THREADS = 256;
 
-enum { HB_STORE = 0, HB_ACCUM = 1, HB_ATOMIC = 2 };
-
 __device__ __forceinline__ uint16_t to_bf16_bits(float v)
 {
     const __bf16 b = (__bf16)v;
@@ -208,7 +206,7 @@ __global__ __launch_bounds__(HB_THREADS) void gemm_b16_kernel(int M, int N, int 
     }
 
     // epilogue: lane holds column (lane & 31), rows (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-    const bool add_bias = bias != nullptr && (epilogue != HB_ATOMIC || slice == 0);
+    const bool add_bias = bias != nullptr && (epilogue != EPI_ATOMIC || slice == 0);
     if (colstats != nullptr) {
         // column sums / sums of squares of this tile in fp64, from the fp32 values (as gemm_bf16_kernel)
         __shared__ double cs[2][WM][BN];
@@ -277,9 +275,9 @@ __global__ __launch_bounds__(HB_THREADS) void gemm_b16_kernel(int M, int N, int 
                 for (int r = 0; r < 16; ++r) {
                     float *dst = c0 + (size_t)(i * 32 + (r & 3) + 8 * (r >> 2)) * ldc + j * 32;
                     const float v = acc[i][j][r] + bv;
-                    if (epilogue == HB_STORE)
+                    if (epilogue == EPI_STORE)
                         *dst = v;
-                    else if (epilogue == HB_ACCUM)
+                    else if (epilogue == EPI_ACCUM)
                         *dst = *dst + v;
                     else
                         atomicAdd(dst, v);
@@ -323,16 +321,8 @@ static bool gemm_b16_plan(int ta, int tb, int M, int N, int K, int &BM, int &BN,
         return false;
     const long long tiles = (long long)(M / BM) * (N / BN);
     splits = 1;
-    if (tiles < 256 && K >= 512) {       // as gemm_bf16_plan: fill the chip, whole slices per XCD
-        splits = (int)((tiles <= 4 ? 256 : 1024) / tiles);
-        const int max_splits = K / 256 > 0 ? K / 256 : 1;
-        if (splits > max_splits)
-            splits = max_splits;
-        if (splits < 1)
-            splits = 1;
-        if (splits > 8)
-            splits = splits / 8 * 8;
-    }
+    if (tiles < 256 && K >= 512)         // as gemm_bf16_plan: fill the chip, whole slices per XCD
+        splits = whole_xcd_splits((int)((tiles <= 4 ? 256 : 1024) / tiles), K / 256);
     return true;
 }
 
@@ -386,12 +376,11 @@ CLOUDAAE_API int cloudaae_gemm_b16(int trans_a, int trans_b, int M, int N, int K
                      "a product cut over K adds fp32 slices: no bf16 output, no column statistics");
     CLOUDAAE_REQUIRE(!c_is_bf16 || accumulate == 0, name, "a bf16 output is overwritten");
     CLOUDAAE_REQUIRE(colstats == nullptr || accumulate == 0, name, "column statistics need an overwriting product");
-    int epi = accumulate == 1 ? HB_ACCUM : HB_STORE;
+    int epi = accumulate == 1 ? EPI_ACCUM : EPI_STORE;
     if (splits > 1) {
-        epi = HB_ATOMIC;
+        epi = EPI_ATOMIC;
         if (!accumulate)
-            CLOUDAAE_CHECK_HIP(hipMemset2DAsync(C, sizeof(float) * (size_t)ldc, 0, sizeof(float) * (size_t)N, (size_t)M, s),
-                               name);
+            CLOUDAAE_CHECK_HIP(gemm_zero_output(reinterpret_cast<float *>(C), M, N, ldc, false, s), name);
     }
     dim3 grid(N / BN, M / BM, splits);
     CLOUDAAE_REQUIRE(M / BM <= 65535, name, "M too large");

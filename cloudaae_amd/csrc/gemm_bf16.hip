@@ -31,19 +31,6 @@ constexpr int GB_BK = 32;            // k per slab
 constexpr int GB_LDK = 40;           // bf16 per staged row (32 + 8 pad)
 constexpr int GB_THREADS = 256;
 
-enum { GB_STORE = 0, GB_ACCUM = 1, GB_ATOMIC = 2 };
-
-// folded row-major matrix (see gemm.hip): logical (r, c) -> row (c >> shift) * rows + r, column c & mask
-struct FoldB {
-    int shift, rows;
-};
-__device__ __forceinline__ size_t foldb_off(int r, int c, int ld, FoldB f)
-{
-    if (f.shift < 0)
-        return (size_t)r * ld + c;
-    return (size_t)((c >> f.shift) * f.rows + r) * ld + (c & ((1 << f.shift) - 1));
-}
-
 // two floats -> two bfloat16 (round to nearest even) in one 32-bit word, lo first
 __device__ __forceinline__ unsigned pack2(float lo, float hi)
 {
@@ -89,7 +76,7 @@ struct SlabB {
     }
 
     __device__ __forceinline__ void load(const float *__restrict__ P, int ld, int outer0, int nouter, int k0,
-                                         int kend, bool vec, FoldB fold)
+                                         int kend, bool vec, Fold fold)
     {
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
@@ -100,15 +87,15 @@ struct SlabB {
                     const int o = it / (GB_BK / 4), kq = it % (GB_BK / 4);
                     const int go = outer0 + o, gk = k0 + 4 * kq;
                     if (go < nouter && gk < kend)
-                        a = fetch4(P + foldb_off(go, gk, ld, fold), kend - gk, vec);
+                        a = fetch4(P + fold_off(go, gk, ld, fold), kend - gk, vec);
                 } else {
                     const int kp = item_kp(it), oq = item_oq(it);
                     const int gk = k0 + 2 * kp, go = outer0 + 4 * oq;
                     if (go < nouter) {
                         if (gk < kend)
-                            a = fetch4(P + foldb_off(gk, go, ld, fold), nouter - go, vec);
+                            a = fetch4(P + fold_off(gk, go, ld, fold), nouter - go, vec);
                         if (gk + 1 < kend)
-                            b = fetch4(P + foldb_off(gk + 1, go, ld, fold), nouter - go, vec);
+                            b = fetch4(P + fold_off(gk + 1, go, ld, fold), nouter - go, vec);
                     }
                 }
             }
@@ -124,10 +111,10 @@ struct SlabB {
     // per slab on predicates and 64-bit addresses next to 8 MFMAs: with bf16 operands the matrix pipe is 16 x faster
     // than with fp32 ones, and those instructions were what the dgcnn_agg products waited on.)
     unsigned boff[PER];
-    // fold (the B operand only; see FoldB): a k-contiguous operand folds over k and its slabs lie inside one fold block
+    // fold (the B operand only; see Fold): a k-contiguous operand folds over k and its slabs lie inside one fold block
     // (checked at launch), so the fold only moves the slab origin (fast_origin); a [k][outer] operand folds over the outer
     // index, a per-thread constant -- its offsets carry the tile origin outer0 and the slab origin is row k alone.
-    __device__ __forceinline__ void fast_init(int ld, FoldB fold, int outer0)
+    __device__ __forceinline__ void fast_init(int ld, Fold fold, int outer0)
     {
 #pragma unroll
         for (int u = 0; u < PER; ++u) {
@@ -135,13 +122,13 @@ struct SlabB {
             if (KC)
                 boff[u] = 4u * (unsigned)((it / (GB_BK / 4)) * ld + 4 * (it % (GB_BK / 4)));
             else
-                boff[u] = 4u * (unsigned)foldb_off(2 * item_kp(it), outer0 + 4 * item_oq(it), ld, fold);
+                boff[u] = 4u * (unsigned)fold_off(2 * item_kp(it), outer0 + 4 * item_oq(it), ld, fold);
         }
     }
-    static __device__ __forceinline__ const float *fast_origin(const float *__restrict__ P, int ld, FoldB fold, int outer0,
+    static __device__ __forceinline__ const float *fast_origin(const float *__restrict__ P, int ld, Fold fold, int outer0,
                                                                int k)
     {
-        return KC ? P + foldb_off(outer0, k, ld, fold) : P + (size_t)k * ld;
+        return KC ? P + fold_off(outer0, k, ld, fold) : P + (size_t)k * ld;
     }
     __device__ __forceinline__ void fast_load(const float *__restrict__ P0, int ld)
     {
@@ -196,8 +183,8 @@ __global__ __launch_bounds__(GB_THREADS) void gemm_bf16_kernel(int M, int N, int
                                                                int lda, const float *__restrict__ B, int ldb,
                                                                float *__restrict__ C, int ldc,
                                                                const float *__restrict__ bias, int epilogue,
-                                                               int kchunk, int vecA, int vecB, FoldB foldB,
-                                                               FoldB foldC, double *__restrict__ colstats,
+                                                               int kchunk, int vecA, int vecB, Fold foldB,
+                                                               Fold foldC, double *__restrict__ colstats,
                                                                long long cslice)
 {
     static_assert(WM * WN * 64 == GB_THREADS, "4 waves");
@@ -258,7 +245,7 @@ __global__ __launch_bounds__(GB_THREADS) void gemm_bf16_kernel(int M, int N, int
 
     if (FAST) {
         // wave-uniform slab origins, advanced by one slab per iteration
-        const FoldB nofold = {-1, 0};
+        const Fold nofold = {-1, 0};
         const float *pa = SA::fast_origin(A, lda, nofold, m0, kbeg);
         const float *pb = SB::fast_origin(B, ldb, foldB, n0, kbeg);
         const size_t stepa = TA ? (size_t)GB_BK * lda : (size_t)GB_BK;
@@ -284,7 +271,7 @@ __global__ __launch_bounds__(GB_THREADS) void gemm_bf16_kernel(int M, int N, int
     } else {
         SA sa;
         SB sb;
-        const FoldB nofold = {-1, 0};
+        const Fold nofold = {-1, 0};
         sa.load(A, lda, m0, M, kbeg, kend, vecA != 0, nofold);
         sb.load(B, ldb, n0, N, kbeg, kend, vecB != 0, foldB);
         for (int k0 = kbeg; k0 < kend; k0 += GB_BK) {
@@ -301,7 +288,7 @@ __global__ __launch_bounds__(GB_THREADS) void gemm_bf16_kernel(int M, int N, int
     }
 
     // epilogue: lane holds column (lane&31), rows (r&3) + 8*(r>>2) + 4*(lane>>5)
-    const bool add_bias = bias != nullptr && (epilogue != GB_ATOMIC || slice == 0);
+    const bool add_bias = bias != nullptr && (epilogue != EPI_ATOMIC || slice == 0);
     if (colstats != nullptr) {
         // column sums / sums of squares of this tile in fp64 for the batch norm that consumes C (as in
         // gemm_f32_kernel: colstats[tile row][0 | 1][col]; fixed order of summation)
@@ -347,11 +334,11 @@ __global__ __launch_bounds__(GB_THREADS) void gemm_bf16_kernel(int M, int N, int
         for (int j = 0; j < TN; ++j) {
             const int col = n0 + (wn * TN + j) * 32 + fr;
             // (a folded output keeps the rows of one column ldc apart: the fold only moves the column's origin)
-            float *c0 = C + foldb_off(m0 + wm * TM * 32 + 4 * fk, col, ldc, foldC);
+            float *c0 = C + fold_off(m0 + wm * TM * 32 + 4 * fk, col, ldc, foldC);
             const float bv = add_bias ? bias[col] : 0.0f;
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
-                if (epilogue == GB_ACCUM) {
+                if (epilogue == EPI_ACCUM) {
                     // the sixteen old values first, then the sums (see gemm.hip: per element every load waits behind the
                     // previous store)
                     float old[16];
@@ -367,7 +354,7 @@ __global__ __launch_bounds__(GB_THREADS) void gemm_bf16_kernel(int M, int N, int
                 for (int r = 0; r < 16; ++r) {
                     float *dst = c0 + (size_t)(i * 32 + (r & 3) + 8 * (r >> 2)) * ldc;
                     const float v = acc[i][j][r] + bv;
-                    if (epilogue == GB_STORE)
+                    if (epilogue == EPI_STORE)
                         *dst = v;
                     else
                         atomicAdd(dst, v);
@@ -388,11 +375,11 @@ __global__ __launch_bounds__(GB_THREADS) void gemm_bf16_kernel(int M, int N, int
             for (int r = 0; r < 16; ++r) {
                 const int row = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * fk;
                 if (row < M) {
-                    float *dst = C + foldb_off(row, col, ldc, foldC);
+                    float *dst = C + fold_off(row, col, ldc, foldC);
                     const float v = acc[i][j][r] + bv;
-                    if (epilogue == GB_STORE)
+                    if (epilogue == EPI_STORE)
                         *dst = v;
-                    else if (epilogue == GB_ACCUM)
+                    else if (epilogue == EPI_ACCUM)
                         *dst = *dst + v;
                     else
                         atomicAdd(dst, v);
@@ -400,43 +387,6 @@ __global__ __launch_bounds__(GB_THREADS) void gemm_bf16_kernel(int M, int N, int
             }
         }
     }
-}
-
-template <int BM, int BN, int WM, int WN, bool FAST>
-static void launch_bf16_as(bool ta, bool tb, dim3 grid, hipStream_t s, int M, int N, int K, const float *A, int lda,
-                           const float *B, int ldb, float *C, int ldc, const float *bias, int epi, int kchunk,
-                           int vecA, int vecB, FoldB fb, FoldB fc, double *cs, long long cslice)
-{
-    dim3 block(GB_THREADS);
-    if (!ta && !tb)
-        hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, false, false, FAST>), grid, block, 0, s, M, N, K, A, lda,
-                           B, ldb, C, ldc, bias, epi, kchunk, vecA, vecB, fb, fc, cs, cslice);
-    else if (!ta && tb)
-        hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, false, true, FAST>), grid, block, 0, s, M, N, K, A, lda,
-                           B, ldb, C, ldc, bias, epi, kchunk, vecA, vecB, fb, fc, cs, cslice);
-    else if (ta && !tb)
-        hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, true, false, FAST>), grid, block, 0, s, M, N, K, A, lda,
-                           B, ldb, C, ldc, bias, epi, kchunk, vecA, vecB, fb, fc, cs, cslice);
-    else
-        hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, true, true, FAST>), grid, block, 0, s, M, N, K, A, lda,
-                           B, ldb, C, ldc, bias, epi, kchunk, vecA, vecB, fb, fc, cs, cslice);
-}
-
-template <int BM, int BN, int WM, int WN>
-static void launch_bf16(bool ta, bool tb, dim3 grid, hipStream_t s, int M, int N, int K, const float *A, int lda,
-                        const float *B, int ldb, float *C, int ldc, const float *bias, int epi, int kchunk,
-                        int vecA, int vecB, FoldB fb, FoldB fc, double *cs, long long cslice)
-{
-    // whole tiles, whole slabs in every K slice, 16-byte aligned rows: the lean loop
-    // (a folded k-contiguous B: every 32-wide slab inside one fold block)
-    const bool fold_ok = fb.shift < 0 || !tb || (1 << fb.shift) % GB_BK == 0;
-    const bool fast = M % BM == 0 && N % BN == 0 && K % GB_BK == 0 && vecA && vecB && fold_ok;
-    if (fast)
-        launch_bf16_as<BM, BN, WM, WN, true>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk, vecA,
-                                             vecB, fb, fc, cs, cslice);
-    else
-        launch_bf16_as<BM, BN, WM, WN, false>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk, vecA,
-                                              vecB, fb, fc, cs, cslice);
 }
 
 // tile shape and K slices (same policy as gemm.hip's gemm_plan, slabs of 32)
@@ -469,116 +419,67 @@ static void gemm_bf16_plan(int M, int N, int K, int &BM, int &BN, int &splits, b
     const long long tiles = (long long)ceil_div(M, BM) * ceil_div(N, BN);
     splits = 1;
     const int resident = 256 * (BM == 32 ? 2 : 4);
-    if (tiles < 256 && K >= 256) {
-        splits = (int)((tiles <= 4 ? 256 : resident) / tiles);
-        const int max_splits = K / 128 > 0 ? K / 128 : 1;
-        if (splits > max_splits)
-            splits = max_splits;
-        if (splits < 1)
-            splits = 1;
-        if (splits > 8)
-            splits = splits / 8 * 8;      // whole slices per XCD
-    }
+    if (tiles < 256 && K >= 256)
+        splits = whole_xcd_splits((int)((tiles <= 4 ? 256 : resident) / tiles), K / 128);
     if (!ordered && CLOUDAAE_KNOB("CLOUDAAE_DETERMINISTIC", 0) != 0)     // deterministic mode: see gemm.hip
         splits = 1;
 }
+
+// The bf16-operand family of gemm.h's launcher.
+struct GemmBf16 {
+    static constexpr int BK = GB_BK;
+    static constexpr auto plan = &gemm_bf16_plan;
+    static constexpr const char *ws_missing =
+        "this product is cut over K: workspace missing or smaller than cloudaae_gemm_bf16_ordered_workspace";
+
+    // whole tiles, whole slabs in every K slice, 16-byte aligned rows: the lean loop
+    // (a folded k-contiguous B: every 32-wide slab inside one fold block)
+    static bool fast(int BM, int BN, bool tb, const GemmArgs &g)
+    {
+        const bool fold_ok = g.fb.shift < 0 || !tb || (1 << g.fb.shift) % GB_BK == 0;
+        return g.M % BM == 0 && g.N % BN == 0 && g.K % GB_BK == 0 && g.vecA && g.vecB && fold_ok;
+    }
+
+    template <int BM, int BN, int WM, int WN, bool TA, bool TB, bool FAST>
+    static void kernel(dim3 grid, hipStream_t s, const GemmArgs &g)
+    {
+        hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, TA, TB, FAST>), grid, dim3(GB_THREADS), 0, s, g.M, g.N, g.K,
+                           g.A, g.lda, g.B, g.ldb, g.C, g.ldc, g.bias, g.epi, g.kchunk, g.vecA, g.vecB, g.fb, g.fc,
+                           g.colstats, g.cslice);
+    }
+
+    static void tiles(int BM, int BN, bool ta, bool tb, dim3 grid, hipStream_t s, const GemmArgs &g)
+    {
+        if (BM == 32)
+            gemm_launch_tile<GemmBf16, 32, 128, 1, 4>(ta, tb, grid, s, g);
+        else if (BN == 160)
+            gemm_launch_tile<GemmBf16, 128, 160, 4, 1>(ta, tb, grid, s, g);
+        else if (BM == 160)
+            gemm_launch_tile<GemmBf16, 160, 128, 1, 4>(ta, tb, grid, s, g);
+        else if (BN == 64)
+            gemm_launch_tile<GemmBf16, 128, 64, 4, 1>(ta, tb, grid, s, g);
+        else if (BM == 64)
+            gemm_launch_tile<GemmBf16, 64, 128, 2, 2>(ta, tb, grid, s, g);
+        else
+            gemm_launch_tile<GemmBf16, 128, 128, 2, 2>(ta, tb, grid, s, g);
+    }
+};
 
 } // namespace cloudaae
 
 using namespace cloudaae;
 
-CLOUDAAE_API int cloudaae_gemm_bf16_splits(int M, int N, int K)
-{
-    if (M <= 0 || N <= 0 || K <= 0)
-        return 1;
-    int BM, BN, splits;
-    gemm_bf16_plan(M, N, K, BM, BN, splits);
-    const int kchunk = ceil_div(ceil_div(K, splits), GB_BK) * GB_BK;
-    return ceil_div(K, kchunk);
-}
+// the cut of a product, as the launches below will make it (gemm_cut)
+CLOUDAAE_API int cloudaae_gemm_bf16_splits(int M, int N, int K) { return gemm_splits<GemmBf16>(M, N, K); }
+CLOUDAAE_API long long cloudaae_gemm_bf16_ordered_workspace(int M, int N, int K) { return gemm_ordered_workspace<GemmBf16>(M, N, K); }
+CLOUDAAE_API int cloudaae_gemm_bf16_colstats_parts(int M, int N, int K) { return gemm_colstats_parts<GemmBf16>(M, N, K); }
 
 int cloudaae::gemm_bf16_launch(const char *name, int trans_a, int trans_b, int M, int N, int K, const float *A,
                                int lda, const float *B, int ldb, float *C, int ldc, const float *bias, int accumulate,
                                int fold_b, int fold_c, hipStream_t s, double *colstats, float *ordered_ws)
 {
-    CLOUDAAE_REQUIRE(M >= 0 && N >= 0 && K >= 0, name, "negative size");
-    if (M == 0 || N == 0)
-        return 0;
-    CLOUDAAE_REQUIRE(lda >= (trans_a ? M : K), name, "leading dimension too small");
-    CLOUDAAE_REQUIRE(fold_b ? ldb == fold_b : ldb >= (trans_b ? K : N), name, "leading dimension too small");
-    CLOUDAAE_REQUIRE(fold_c ? ldc == fold_c : ldc >= N, name, "leading dimension too small");
-    CLOUDAAE_REQUIRE((fold_b & (fold_b - 1)) == 0 && (fold_c & (fold_c - 1)) == 0 && fold_b % 4 == 0 &&
-                         fold_c % 4 == 0, name, "fold width must be a power of two >= 4");
-    FoldB fb = {-1, 0}, fc = {-1, 0};
-    if (fold_b) {
-        fb.shift = __builtin_ctz((unsigned)fold_b);
-        fb.rows = trans_b ? N : K;
-    }
-    if (fold_c) {
-        fc.shift = __builtin_ctz((unsigned)fold_c);
-        fc.rows = M;
-    }
-    int BM, BN, splits;
-    gemm_bf16_plan(M, N, K, BM, BN, splits, ordered_ws != nullptr);
-    const int tm = ceil_div(M, BM), tn = ceil_div(N, BN);
-    CLOUDAAE_REQUIRE(tm <= 65535, name, "M too large");
-    CLOUDAAE_REQUIRE(colstats == nullptr || (splits == 1 && accumulate == 0 && !fold_c), name,
-                     "column statistics need an unsplit, overwriting product");
-    int kchunk = K > 0 ? ceil_div(ceil_div(K, splits), GB_BK) * GB_BK : GB_BK;
-    splits = K > 0 ? ceil_div(K, kchunk) : 1;
-    int epi = accumulate == 1 ? GB_ACCUM : GB_STORE;
-    // ordered_ws: slices kept apart and summed in slice order by a second kernel (see gemm_f32_launch)
-    const bool ordered = ordered_ws != nullptr && splits > 1;
-    CLOUDAAE_REQUIRE(ordered_ws == nullptr || (accumulate == 0 && !fold_c && colstats == nullptr), name,
-                     "slice-ordered products overwrite an unfolded output");
-    float *const Cout = C;
-    const int ldc_out = ldc;
-    const float *const bias_out = bias;
-    long long cslice = 0;
-    if (ordered) {
-        C = ordered_ws;
-        ldc = N;
-        bias = nullptr;
-        cslice = (long long)M * N;
-    } else if (splits > 1) {
-        epi = GB_ATOMIC;
-        if (!accumulate) {
-            if (fold_c)
-                CLOUDAAE_CHECK_HIP(hipMemsetAsync(C, 0, sizeof(float) * (size_t)M * (size_t)N, s), name);
-            else
-                CLOUDAAE_CHECK_HIP(hipMemset2DAsync(C, sizeof(float) * (size_t)ldc, 0, sizeof(float) * (size_t)N,
-                                                    (size_t)M, s), name);
-        }
-    }
-    const int vecA = (((uintptr_t)A & 15) == 0 && lda % 4 == 0) ? 1 : 0;
-    const int vecB = (((uintptr_t)B & 15) == 0 && ldb % 4 == 0) ? 1 : 0;
-    dim3 grid(tn, tm, splits);
-    const bool ta = trans_a != 0, tb = trans_b != 0;
-    if (BM == 32)
-        launch_bf16<32, 128, 1, 4>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk, vecA, vecB, fb,
-                                   fc, colstats, cslice);
-    else if (BN == 160)
-        launch_bf16<128, 160, 4, 1>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk, vecA, vecB, fb,
-                                    fc, colstats, cslice);
-    else if (BM == 160)
-        launch_bf16<160, 128, 1, 4>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk, vecA, vecB, fb,
-                                    fc, colstats, cslice);
-    else if (BN == 64)
-        launch_bf16<128, 64, 4, 1>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk, vecA, vecB, fb,
-                                   fc, colstats, cslice);
-    else if (BM == 64)
-        launch_bf16<64, 128, 2, 2>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk, vecA, vecB, fb,
-                                   fc, colstats, cslice);
-    else
-        launch_bf16<128, 128, 2, 2>(ta, tb, grid, s, M, N, K, A, lda, B, ldb, C, ldc, bias, epi, kchunk, vecA, vecB,
-                                    fb, fc, colstats, cslice);
-    CLOUDAAE_CHECK_LAUNCH(name);
-    if (ordered) {
-        const int rc = gemm_slices_sum(name, M, N, splits, ordered_ws, Cout, ldc_out, bias_out, s);
-        if (rc != 0)
-            return rc;
-    }
-    return 0;
+    return gemm_launch<GemmBf16>(name, trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, fold_b,
+                                 fold_c, s, colstats, ordered_ws);
 }
 
 CLOUDAAE_API int cloudaae_gemm_bf16(int trans_a, int trans_b, int M, int N, int K, const float *A, int lda,
@@ -589,37 +490,12 @@ CLOUDAAE_API int cloudaae_gemm_bf16(int trans_a, int trans_b, int M, int N, int 
                             0, 0, (hipStream_t)stream);
 }
 
-CLOUDAAE_API long long cloudaae_gemm_bf16_ordered_workspace(int M, int N, int K)
-{
-    if (M <= 0 || N <= 0 || K <= 0)
-        return 0;
-    int BM, BN, splits;
-    gemm_bf16_plan(M, N, K, BM, BN, splits, true);
-    const int kchunk = ceil_div(ceil_div(K, splits), GB_BK) * GB_BK;
-    splits = ceil_div(K, kchunk);
-    return splits > 1 ? (long long)splits * M * N : 0;
-}
-
 CLOUDAAE_API int cloudaae_gemm_bf16_ordered(int trans_a, int trans_b, int M, int N, int K, const float *A, int lda,
                                             const float *B, int ldb, float *C, int ldc, const float *bias,
                                             float *workspace, long long workspace_floats, cloudaae_stream_t stream)
 {
-    const char *name = "cloudaae_gemm_bf16_ordered";
-    CLOUDAAE_REQUIRE(workspace != nullptr ? workspace_floats >= cloudaae_gemm_bf16_ordered_workspace(M, N, K)
-                                          : cloudaae_gemm_bf16_ordered_workspace(M, N, K) == 0,
-                     name, "this product is cut over K: workspace missing or smaller than cloudaae_gemm_bf16_ordered_workspace");
-    static float dummy_ws;      // (non-NULL selects the ordered plan; a product that stays whole never touches it)
-    return gemm_bf16_launch(name, trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, bias, 0, 0, 0, (hipStream_t)stream,
-                            nullptr, workspace != nullptr ? workspace : &dummy_ws);
-}
-
-CLOUDAAE_API int cloudaae_gemm_bf16_colstats_parts(int M, int N, int K)
-{
-    if (M <= 0 || N <= 0 || K <= 0)
-        return 0;
-    int BM, BN, splits;
-    gemm_bf16_plan(M, N, K, BM, BN, splits);
-    return splits == 1 ? ceil_div(M, BM) : 0;      // one row of sums per tile row
+    return gemm_ordered<GemmBf16>("cloudaae_gemm_bf16_ordered", trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, bias, 0,
+                                  workspace, workspace_floats, (hipStream_t)stream);
 }
 
 CLOUDAAE_API int cloudaae_gemm_bf16_colstats(int trans_a, int trans_b, int M, int N, int K, const float *A, int lda,

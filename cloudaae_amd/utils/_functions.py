@@ -142,39 +142,36 @@ SIDE_EDGE = True      # edge-convolution layers use it too (else only the dgcnn_
 SIDE_AGG = True       # the dgcnn_agg weight gradient uses it
 
 
+def _gemm_ordered(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, device, bf16):
+    """cloudaae_gemm_{f32,bf16}_ordered with the workspace its cut needs: a product cut over K keeps its slices apart
+    and sums them in slice order instead of adding them with atomics (bit-reproducible from run to run)."""
+    name = "cloudaae_gemm_%s_ordered" % ("bf16" if bf16 else "f32")
+    n = int(getattr(L(), name + "_workspace")(M, N, K))
+    ws = _lib.empty(n, dtype=torch.float32, device=device) if n else None
+    _lib.check(getattr(L(), name)(int(ta), int(tb), M, N, K, A, lda, B, ldb, C, ldc, bias, ptr(ws), n, stream()), name)
+
+
 def gemm(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias=None, accumulate=0, site=None, bf16=False, on=None, device=None):
     rec = TIMED_SITES.get(site) if site is not None else None
     if rec is not None:
         _lib.host(_mark, rec)
     if DETERMINISTIC and int(accumulate) != 1 and on is None and device is not None:
-        # deterministic mode: a product cut over K keeps its slices apart and sums them in slice order
-        # (cloudaae_gemm_*_ordered) instead of staying whole on a handful of CUs
-        wsq = L().cloudaae_gemm_bf16_ordered_workspace if bf16 else L().cloudaae_gemm_f32_ordered_workspace
-        n = int(wsq(M, N, K))
-        ws = _lib.empty(n, dtype=torch.float32, device=device) if n else None
-        fn = L().cloudaae_gemm_bf16_ordered if bf16 else L().cloudaae_gemm_f32_ordered
-        _lib.check(fn(int(ta), int(tb), M, N, K, A, lda, B, ldb, C, ldc, bias, ptr(ws), n, stream()), "cloudaae_gemm_ordered")
+        # deterministic mode: the slice-ordered product instead of one that stays whole on a handful of CUs
+        _gemm_ordered(ta, tb, M, N, K, A, lda, B, ldb, C, ldc, bias, device, bf16)
     else:
-        fn = L().cloudaae_gemm_bf16 if bf16 else L().cloudaae_gemm_f32
-        _lib.check(fn(int(ta), int(tb), M, N, K, A, lda, B, ldb, C, ldc, bias, int(accumulate),
-                      stream() if on is None else on),
-                   "cloudaae_gemm_bf16" if bf16 else "cloudaae_gemm_f32")
+        name = "cloudaae_gemm_bf16" if bf16 else "cloudaae_gemm_f32"
+        _lib.check(getattr(L(), name)(int(ta), int(tb), M, N, K, A, lda, B, ldb, C, ldc, bias, int(accumulate),
+                                      stream() if on is None else on), name)
     if rec is not None:
         _lib.host(_mark, rec)
 
 
 def gemm_forward(M, N, K, A, lda, B, ldb, C, ldc, bias, device, site=None, bf16=False):
-    """C = A B + bias for a FORWARD product: bit-reproducible from run to run (cloudaae_gemm_*_ordered: a product
-    cut over K keeps its slices apart and sums them in slice order instead of adding them with atomics)."""
+    """C = A B + bias for a FORWARD product: bit-reproducible from run to run (_gemm_ordered)."""
     rec = TIMED_SITES.get(site) if site is not None else None
     if rec is not None:
         _lib.host(_mark, rec)
-    wsq = L().cloudaae_gemm_bf16_ordered_workspace if bf16 else L().cloudaae_gemm_f32_ordered_workspace
-    n = int(wsq(M, N, K))
-    ws = _lib.empty(n, dtype=torch.float32, device=device) if n else None
-    fn = L().cloudaae_gemm_bf16_ordered if bf16 else L().cloudaae_gemm_f32_ordered
-    _lib.check(fn(0, 0, M, N, K, A, lda, B, ldb, C, ldc, bias, ptr(ws), n, stream()),
-               "cloudaae_gemm_bf16_ordered" if bf16 else "cloudaae_gemm_f32_ordered")
+    _gemm_ordered(0, 0, M, N, K, A, lda, B, ldb, C, ldc, bias, device, bf16)
     if rec is not None:
         _lib.host(_mark, rec)
 
