@@ -514,6 +514,18 @@ CLOUDAAE_API int cloudaae_gemm_f32(int trans_a, int trans_b, int M, int N, int K
                            0, 0, (hipStream_t)stream);
 }
 
+// Development / test entry: the folded-operand products of edgeconv.hip (ec_gemm there), reachable on their own.
+CLOUDAAE_API int cloudaae_dev_gemm_folded(int bf16, int trans_a, int trans_b, int M, int N, int K, const float *A, int lda,
+                                          const float *B, int ldb, float *C, int ldc, int accumulate, int fold_b, int fold_c,
+                                          cloudaae_stream_t stream)
+{
+    const char *name = "cloudaae_dev_gemm_folded";
+    return bf16 ? gemm_bf16_launch(name, trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, nullptr, accumulate, fold_b,
+                                   fold_c, (hipStream_t)stream)
+                : gemm_f32_launch(name, trans_a, trans_b, M, N, K, A, lda, B, ldb, C, ldc, nullptr, accumulate, fold_b,
+                                  fold_c, (hipStream_t)stream);
+}
+
 CLOUDAAE_API int cloudaae_gemm_f32_ordered(int trans_a, int trans_b, int M, int N, int K, const float *A, int lda,
                                            const float *B, int ldb, float *C, int ldc, const float *bias,
                                            float *workspace, long long workspace_floats, cloudaae_stream_t stream)

@@ -47,7 +47,8 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * queries take M; no y_zeroed argument).  600: round 6 (cloudaae_knn_hinted added; nothing else changed).
  * 601: cloudaae_selftest_div_by added.  602: cloudaae_icp_point_to_point and cloudaae_f64_to_f32 added; later, still
  * under 602 (additions only, no existing argument list or layout changed): cloudaae_frame_segments,
- * cloudaae_radius_outlier, cloudaae_ragged_fps and their workspace queries. */
+ * cloudaae_radius_outlier, cloudaae_ragged_fps and their workspace queries; cloudaae_dev_gemm_folded (development /
+ * test entry). */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -247,6 +248,15 @@ int cloudaae_gemm_f32_ordered_fold(int trans_a, int trans_b, int M, int N, int K
                                    const float *B, int ldb, float *C, int ldc, int fold_c, float *workspace,
                                    long long workspace_floats,
                                    cloudaae_stream_t stream);
+/* Development / test entry: cloudaae_gemm_f32 (bf16 == 0) or cloudaae_gemm_bf16 (bf16 != 0) without bias, with B and / or C
+ * FOLDED as the edge convolution's products address its [2*cin, cout] kernel (used as [cin, 2*cout]): fold_b / fold_c = 0, or
+ * the power-of-two width (>= 4) at which the logical columns fold into stacked row blocks -- logical (r, c) lives at row
+ * (c / width) * rows + r, column c % width, rows = the logical row count (for B: of the matrix as stored, [K][N] or [N][K]);
+ * the folded matrix has leading dimension == width.  Forwards to the launcher the edge convolution uses; no product code
+ * calls it. */
+int cloudaae_dev_gemm_folded(int bf16, int trans_a, int trans_b, int M, int N, int K, const float *A, int lda,
+                             const float *B, int ldb, float *C, int ldc, int accumulate, int fold_b, int fold_c,
+                             cloudaae_stream_t stream);
 /* The same product with both operands rounded to bfloat16 (round to nearest even) on their way
  * to the matrix cores (v_mfma_f32_32x32x16_bf16), fp32 accumulate; A, B, C, bias stay fp32 in
  * memory, so the call is interchangeable with cloudaae_gemm_f32 (BASELINE configs[2]: bf16 MLPs). */

@@ -21,24 +21,29 @@ def tools_present():
     return all(os.path.exists(os.path.join(LLVM_BIN, t)) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-objdump"))
 
 
+def _code_objects(lib_path, tmp):
+    """yields the path of every gfx950 code object of the library (one per translation unit), extracted into tmp"""
+    fat = os.path.join(tmp, "fat.bin")
+    subprocess.run([os.path.join(LLVM_BIN, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", lib_path, fat],
+                   check=True)
+    data = open(fat, "rb").read()
+    starts = [m.start() for m in re.finditer(re.escape(_MAGIC), data)]
+    assert starts, "no offload bundle in " + lib_path
+    for n, (a, b) in enumerate(zip(starts, starts[1:] + [len(data)])):
+        piece = os.path.join(tmp, "bundle%d.bin" % n)
+        co = os.path.join(tmp, "dev%d.co" % n)
+        open(piece, "wb").write(data[a:b])
+        subprocess.run([os.path.join(LLVM_BIN, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + piece,
+                        "--targets=" + _TARGET, "--output=" + co], check=True, capture_output=True)
+        if os.path.exists(co) and os.path.getsize(co) > 0:
+            yield co
+
+
 def disassemble(lib_path):
     """-> list of (kernel name, instruction text) over every gfx950 code object of the library (one per translation unit)"""
     out = []
     with tempfile.TemporaryDirectory() as tmp:
-        fat = os.path.join(tmp, "fat.bin")
-        subprocess.run([os.path.join(LLVM_BIN, "llvm-objcopy"), "-O", "binary", "--only-section=.hip_fatbin", lib_path, fat],
-                       check=True)
-        data = open(fat, "rb").read()
-        starts = [m.start() for m in re.finditer(re.escape(_MAGIC), data)]
-        assert starts, "no offload bundle in " + lib_path
-        for n, (a, b) in enumerate(zip(starts, starts[1:] + [len(data)])):
-            piece = os.path.join(tmp, "bundle%d.bin" % n)
-            co = os.path.join(tmp, "dev%d.co" % n)
-            open(piece, "wb").write(data[a:b])
-            subprocess.run([os.path.join(LLVM_BIN, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + piece,
-                            "--targets=" + _TARGET, "--output=" + co], check=True, capture_output=True)
-            if not os.path.exists(co) or os.path.getsize(co) == 0:
-                continue
+        for co in _code_objects(lib_path, tmp):
             text = subprocess.run([os.path.join(LLVM_BIN, "llvm-objdump"), "-d", "--no-show-raw-insn", co], check=True,
                                   capture_output=True, text=True).stdout
             fn = "?"
@@ -51,6 +56,45 @@ def disassemble(lib_path):
                 if ins and not ins.startswith(("Disassembly", dev_prefix(co))):
                     out.append((fn, re.sub(r"\s*//.*$", "", ins)))
     return out
+
+
+def kernel_symbols(lib_path):
+    """-> sorted mangled names of the functions the gfx950 code objects of the library define (llvm-objdump -t)"""
+    names = set()
+    with tempfile.TemporaryDirectory() as tmp:
+        for co in _code_objects(lib_path, tmp):
+            text = subprocess.run([os.path.join(LLVM_BIN, "llvm-objdump"), "-t", co], check=True, capture_output=True,
+                                  text=True).stdout
+            for line in text.splitlines():
+                # "0000000000001a00 g     F .text  0000000000000d3c .protected _Z...": value, flags, section, size, name
+                m = re.match(r"^[0-9a-f]+\s+\S.*\sF\s+\.text\s+[0-9a-f]+\s+(?:\.\w+\s+)?(\S+)$", line)
+                if m:
+                    names.add(m.group(1))
+    return sorted(names)
+
+
+_TEMPLATE_ARG = re.compile(r"L([ib])(n?\d+)E")
+
+
+def template_instances(symbols, kernel):
+    """The instantiations of the function template `kernel` among mangled names, read from the Itanium mangling
+    (`...gemm_f32_kernelILi128ELi128ELi2ELi2ELb0ELb1ELb1E...` = <128, 128, 2, 2, false, true, true>; there is no llvm-cxxfilt
+    next to the other tools): -> sorted tuples of the leading integer / bool template arguments."""
+    out = set()
+    for sym in symbols:
+        at = sym.find(kernel + "I")
+        if at < 0:
+            continue
+        rest, args = sym[at + len(kernel) + 1:], []
+        while True:
+            m = _TEMPLATE_ARG.match(rest)
+            if not m:
+                break
+            v = int(m.group(2).replace("n", "-"))
+            args.append(bool(v) if m.group(1) == "b" else v)
+            rest = rest[m.end():]
+        out.add(tuple(args))
+    return sorted(out)
 
 
 def dev_prefix(path):
