@@ -17,6 +17,7 @@
 // a wave reads 64 consecutive channels of a row (256 B), four rows in flight per
 // workgroup.
 #include "bn_common.h"
+#include "gemm.h"
 #include "../../include/cloudaae_hip.h"
 
 namespace cloudaae {
@@ -343,7 +344,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnBwdArgs a, const fl
                 float z = v[u] * sc + sh;
                 if (a.relu)
                     z = fmaxf(z, 0.0f);
-                const float dz = hoist ? ((a.relu && !(z > 0.0f)) ? 0.0f : gconst) : bn_upstream(a, r, c, z);
+                if (hoist) {        // (the map of one element: shared with the product that forms dy itself)
+                    dy[(size_t)r * lddy + c] = bn_bwd_dy_hoisted(v[u], sc, sh, mean, rstd, m2, gr, 0.0f - m1, gconst - m1, a.relu != 0);
+                    continue;
+                }
+                const float dz = bn_upstream(a, r, c, z);
                 const float xh = (v[u] - mean) * rstd;
                 dy[(size_t)r * lddy + c] = gr * ((dz - m1) - xh * m2);
             }
@@ -638,8 +643,10 @@ static int bn_backward_impl(const char *name, int M, int C, const float *y, int 
                             const float *tie_count, float *dy, int lddy, float *dgamma,
                             float *dbeta, float *dbias, int accumulate_param_grads,
                             const double *pool_stats, void *workspace, const cloudaae_bn_sync *sync,
-                            cloudaae_stream_t stream)
+                            cloudaae_stream_t stream, float *dy_consts = nullptr)
 {
+    // dy_consts != nullptr (mean pool, no other upstream, no SyncBN): the apply pass is left to the caller's product -- the
+    // finalise writes the table of its constants instead (bn_common.h: bn_bwd_write_dy_consts)
     CLOUDAAE_REQUIRE(M > 0 && C > 0 && ldy >= C, name, "bad size");
     CLOUDAAE_REQUIRE(workspace && gamma && beta && save_mean && save_var && dy, name, "null argument");
     CLOUDAAE_REQUIRE(pool_mode >= 0 && pool_mode <= 2, name, "bad pool_mode");
@@ -677,7 +684,7 @@ static int bn_backward_impl(const char *name, int M, int C, const float *y, int 
             // no exchange between the rows and their sums: the finalise forms the rows itself (one launch, same bits)
             hipLaunchKernelGGL(bn_bwd_finalize_pool_kernel, dim3(ceil_div(C, BN_FIN_CH)), dim3(BN_FIN_THREADS), 0, s, C, groups,
                                pool_rows, parts, dpooled, pool_stats, (double)M, training, dgamma, dbeta,
-                               accumulate_param_grads, m12, dbias, gamma, save_var);
+                               accumulate_param_grads, m12, dbias, gamma, save_var, dy_consts, beta, save_mean);
             finalised = true;
         } else {
             hipLaunchKernelGGL(bn_bwd_pool_partials_kernel, dim3(ceil_div(C, 256), parts), dim3(256), 0, s, C, groups,
@@ -697,7 +704,11 @@ static int bn_backward_impl(const char *name, int M, int C, const float *y, int 
     if (!finalised)
         hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(C, BN_FIN_CH)), dim3(BN_FIN_THREADS), 0, s, C, partial, parts,
                            (double)M, training, dgamma, dbeta, accumulate_param_grads, m12, dbias, gamma, save_var, gsums,
-                           gcount);
+                           gcount, dy_consts, groups, pool_rows, dpooled, beta, save_mean);
+    if (dy_consts != nullptr) {
+        CLOUDAAE_CHECK_LAUNCH(name);
+        return 0;
+    }
     const int slab = 64;
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(cb, ceil_div(M, slab)), dim3(256), 0, s, a, m12, dy, lddy,
                        slab);
@@ -730,6 +741,43 @@ CLOUDAAE_API int cloudaae_bn_backward_sync(int M, int C, const float *y, int ldy
     return bn_backward_impl("cloudaae_bn_backward_sync", M, C, y, ldy, gamma, beta, save_mean, save_var, training, relu,
                             dout, lddo, pool_rows, pool_mode, dpooled, pooled, tie_count, dy, lddy, dgamma, dbeta, dbias,
                             accumulate_param_grads, pool_stats, workspace, sync, stream);
+}
+
+CLOUDAAE_API int cloudaae_bn_backward_dx_bf16x3_supported(int M, int C, int N, int pool_rows)
+{
+    return pool_rows > 0 && M > 0 && M % pool_rows == 0 && M / pool_rows <= 65535 && C % 32 == 0 &&
+                   gemm_x3s_bnbwd_served(M, N, C, pool_rows) ? 1 : 0;
+}
+
+CLOUDAAE_API long long cloudaae_bn_backward_dx_bf16x3_consts_bytes(int M, int C, int pool_rows)
+{
+    return pool_rows > 0 && M > 0 && M % pool_rows == 0 ? (long long)(bn_dyc_floats(C, M / pool_rows) * sizeof(float)) : 0;
+}
+
+CLOUDAAE_API int cloudaae_bn_backward_dx_bf16x3(int M, int C, const float *y, int ldy, const float *gamma, const float *beta,
+                                                const float *save_mean, const float *save_var, int training, int relu,
+                                                int pool_rows, const float *dpooled, float *dy, int lddy, float *dgamma,
+                                                float *dbeta, float *dbias, int accumulate_param_grads,
+                                                const double *pool_stats, void *workspace, void *consts, int N,
+                                                const void *planes, float *dx, int lddx, cloudaae_stream_t stream)
+{
+    const char *name = "cloudaae_bn_backward_dx_bf16x3";
+    CLOUDAAE_REQUIRE(cloudaae_bn_backward_dx_bf16x3_supported(M, C, N, pool_rows), name,
+                     "layer not served (see cloudaae_bn_backward_dx_bf16x3_supported): take cloudaae_bn_backward and "
+                     "cloudaae_gemm_bf16x3p");
+    CLOUDAAE_REQUIRE(consts && planes && dx && dy && y && dpooled, name, "null argument");
+    CLOUDAAE_REQUIRE(lddy >= C && lddx >= N, name, "leading dimension too small");
+    CLOUDAAE_REQUIRE(ldy % 4 == 0 && lddy % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)dy & 15) == 0 &&
+                         ((uintptr_t)planes & 15) == 0 && ((uintptr_t)consts & 15) == 0, name,
+                     "rows of y and dy, the planes and the table must be 16-byte aligned");
+    CLOUDAAE_REQUIRE((long long)128 * lddy * 4 < (1ll << 31), name, "lddy too large");
+    int rc = bn_backward_impl(name, M, C, y, ldy, gamma, beta, save_mean, save_var, training, relu, nullptr, 0, pool_rows, 1,
+                              dpooled, nullptr, nullptr, dy, lddy, dgamma, dbeta, dbias, accumulate_param_grads, pool_stats,
+                              workspace, nullptr, stream, reinterpret_cast<float *>(consts));
+    if (rc != 0)
+        return rc;
+    return gemm_x3s_bnbwd_launch(name, M, N, C, y, ldy, planes, dx, lddx, reinterpret_cast<const float *>(consts), pool_rows,
+                                 relu, dy, lddy, (hipStream_t)stream);
 }
 
 CLOUDAAE_API int cloudaae_colsum_f32(int M, int C, const float *x, int ldx, float *out, int accumulate,

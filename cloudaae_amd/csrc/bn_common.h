@@ -163,6 +163,63 @@ static __global__ __launch_bounds__(BN_FIN_THREADS) void bn_finalize_kernel(
     bn_finalize_channel(C, c, s, s2, count, training, decay, ema_mean, ema_var, gamma, beta, save_mean, save_var, scale_shift);
 }
 
+// ---- the backward apply pass as a map of one element, for a mean pool's hoisted upstream gradient --------------------
+// dz = (relu && !(z > 0)) ? 0 : gconst and dy = gr * ((dz - m1) - xh * m2): (dz - m1) takes one of two values per
+// (group, channel), a0 = 0 - m1 and a1 = gconst - m1, formed by the same subtraction.  bn_bwd_apply_kernel and the input-gradient
+// product that forms dy on its way into the matrix cores (gemm_x3.hip: gemm_x3s_kernel<.., true>) both call this, so the
+// two cannot drift: same fp32 operations in the same order, nothing contracted (the library is built with -ffp-contract=off).
+__device__ __forceinline__ float bn_bwd_dy_hoisted(float y, float sc, float sh, float mean, float rstd, float m2, float gr,
+                                                   float a0, float a1, bool relu)
+{
+    float z = y * sc + sh;
+    if (relu)
+        z = fmaxf(z, 0.0f);
+    const float a = (relu && !(z > 0.0f)) ? a0 : a1;
+    const float xh = (y - mean) * rstd;
+    return gr * (a - xh * m2);
+}
+
+// The eight constants of that map as a table the product streams beside its operand: per group and per slab of 32 channels
+// one linear 1 KB piece [constant][32 channels] (a slab of the product's K = one piece).
+constexpr int BN_DYC = 8;
+enum { BN_DYC_SC = 0, BN_DYC_SH, BN_DYC_MEAN, BN_DYC_RSTD, BN_DYC_M2, BN_DYC_GR, BN_DYC_A0, BN_DYC_A1 };
+__host__ __device__ inline size_t bn_dyc_floats(int C, int groups) { return (size_t)groups * C * BN_DYC; }
+__host__ __device__ inline size_t bn_dyc_index(int C, int g, int c, int q)
+{
+    return (((size_t)g * (C / 32) + c / 32) * BN_DYC + q) * 32 + (c & 31);
+}
+
+// Written by the backward finalise kernels (every thread of the block calls this after the block's channels were
+// finalised): thread (channel c, part-lane pl) takes the groups pl, pl + 32, ...  C % 32 == 0.
+__device__ __forceinline__ void bn_bwd_write_dy_consts(int C, int c, int pl, int groups, int rows,
+                                                       const float *__restrict__ dpooled, const float *__restrict__ gamma,
+                                                       const float *__restrict__ beta, const float *__restrict__ save_mean,
+                                                       const float *__restrict__ save_var, const float *m12,
+                                                       float *__restrict__ table)
+{
+    __syncthreads();        // m12 of this block's channels is written
+    if (c >= C)
+        return;
+    float sc, sh;
+    bn_scale_shift_of(gamma, beta, save_mean, save_var, c, sc, sh);
+    const float mean = save_mean[c], rstd = bn_rsqrt(save_var[c] + BN_EPS);
+    const float m1 = m12[c], m2 = m12[C + c];
+    const float gr = gamma[c] * rstd;
+    const float a0 = 0.0f - m1;
+    for (int g = pl; g < groups; g += BN_FIN_LANES) {
+        const float gconst = dpooled[(size_t)g * C + c] / (float)rows;
+        float *t = table + bn_dyc_index(C, g, c, 0);
+        t[32 * BN_DYC_SC] = sc;
+        t[32 * BN_DYC_SH] = sh;
+        t[32 * BN_DYC_MEAN] = mean;
+        t[32 * BN_DYC_RSTD] = rstd;
+        t[32 * BN_DYC_M2] = m2;
+        t[32 * BN_DYC_GR] = gr;
+        t[32 * BN_DYC_A0] = a0;
+        t[32 * BN_DYC_A1] = gconst - m1;
+    }
+}
+
 // what one channel's backward finalise writes, from its three sums
 __device__ __forceinline__ void bn_bwd_finalize_channel(int C, int c, double s, double s2, double s3, double count, int training,
                                                         float *__restrict__ dgamma, float *__restrict__ dbeta, int accumulate,
@@ -192,18 +249,22 @@ static __global__ __launch_bounds__(BN_FIN_THREADS) void bn_bwd_finalize_kernel(
     int C, const double *__restrict__ partial, int parts, double count, int training,
     float *__restrict__ dgamma, float *__restrict__ dbeta, int accumulate, float *__restrict__ m12,
     float *__restrict__ dbias, const float *__restrict__ gamma, const float *__restrict__ save_var,
-    const double *__restrict__ gsums = nullptr, double gcount = 0.0)
+    const double *__restrict__ gsums = nullptr, double gcount = 0.0, float *__restrict__ dy_consts = nullptr, int groups = 0,
+    int rows = 0, const float *__restrict__ dpooled = nullptr, const float *__restrict__ beta = nullptr,
+    const float *__restrict__ save_mean = nullptr)
 {
     // gsums != nullptr (SyncBN): gsums[2][C] = the two sums over ALL ranks' rows, gcount = their row count;
     // the means the input gradient needs come from those, dgamma / dbeta / dbias stay this rank's sums
+    // dy_consts != nullptr: the table of bn_bwd_dy_hoisted's constants for `groups` groups of `rows` rows is written too
     const int c = bn_fin_channel(), pl = bn_fin_lane();
     double s, s2, s3 = 0.0;
     bn_reduce_partials(partial, parts, C, c, pl, s, s2,
                        dbias != nullptr ? partial + (size_t)BN_MAX_PARTS * 2 * C : nullptr, &s3);
-    if (c >= C || pl != 0)
-        return;
-    bn_bwd_finalize_channel(C, c, s, s2, s3, count, training, dgamma, dbeta, accumulate, m12, dbias, gamma, save_var, gsums,
-                            gcount);
+    if (c < C && pl == 0)
+        bn_bwd_finalize_channel(C, c, s, s2, s3, count, training, dgamma, dbeta, accumulate, m12, dbias, gamma, save_var, gsums,
+                                gcount);
+    if (dy_consts != nullptr)
+        bn_bwd_write_dy_consts(C, c, pl, groups, rows, dpooled, gamma, beta, save_mean, save_var, m12, dy_consts);
 }
 
 // Mean pool over groups of `rows` rows with nothing else consuming the activation: the upstream gradient
@@ -242,8 +303,10 @@ static __global__ __launch_bounds__(256) void bn_bwd_pool_partials_kernel(int C,
 static __global__ __launch_bounds__(BN_FIN_THREADS) void bn_bwd_finalize_pool_kernel(
     int C, int groups, int rows, int parts, const float *__restrict__ dpooled, const double *__restrict__ pool_stats,
     double count, int training, float *__restrict__ dgamma, float *__restrict__ dbeta, int accumulate,
-    float *__restrict__ m12, float *__restrict__ dbias, const float *__restrict__ gamma, const float *__restrict__ save_var)
+    float *__restrict__ m12, float *__restrict__ dbias, const float *__restrict__ gamma, const float *__restrict__ save_var,
+    float *__restrict__ dy_consts = nullptr, const float *__restrict__ beta = nullptr, const float *__restrict__ save_mean = nullptr)
 {
+    // dy_consts != nullptr: as bn_bwd_finalize_kernel
     const int c = bn_fin_channel(), pl = bn_fin_lane(), l = threadIdx.x % BN_FIN_CH;
     auto A = [&](int p) {
         double acc = 0.0;
@@ -268,10 +331,11 @@ static __global__ __launch_bounds__(BN_FIN_THREADS) void bn_bwd_finalize_pool_ke
         bn_reduce_rows<true>(parts, c < C, pl, l, A, B, C3, s, s2, s3);
     else
         bn_reduce_rows<false>(parts, c < C, pl, l, A, B, C3, s, s2, s3);
-    if (c >= C || pl != 0)
-        return;
-    bn_bwd_finalize_channel(C, c, s, s2, s3, count, training, dgamma, dbeta, accumulate, m12, dbias, gamma, save_var, nullptr,
-                            0.0);
+    if (c < C && pl == 0)
+        bn_bwd_finalize_channel(C, c, s, s2, s3, count, training, dgamma, dbeta, accumulate, m12, dbias, gamma, save_var, nullptr,
+                                0.0);
+    if (dy_consts != nullptr)
+        bn_bwd_write_dy_consts(C, c, pl, groups, rows, dpooled, gamma, beta, save_mean, save_var, m12, dy_consts);
 }
 
 // ---- SyncBN: the sums of a layer leave for the other ranks between its statistics pass and its finalise ----

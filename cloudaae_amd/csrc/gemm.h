@@ -39,6 +39,14 @@ int gemm_bf16_launch(const char *name, int trans_a, int trans_b, int M, int N, i
 int gemm_slices_sum(const char *name, int M, int N, int splits, const float *ws, float *C, int ldc, const float *bias,
                     hipStream_t stream, Fold fold);
 
+// gemm_x3.hip: dx[M,N] = dy[M,K] P^T as cloudaae_gemm_bf16x3p, with dy formed from y[M,K] on its way into the matrix cores
+// (bn_common.h: bn_bwd_dy_hoisted on the table `consts` of bn_dyc_floats(K, M / rows) floats) and stored to dy by the
+// workgroups of the first column tile.  Served: a streamed product with 160-column tiles whose 128-row tiles lie inside one
+// group of `rows` rows.
+bool gemm_x3s_bnbwd_served(int M, int N, int K, int rows);
+int gemm_x3s_bnbwd_launch(const char *name, int M, int N, int K, const float *y, int ldy, const void *planes, float *dx, int lddx,
+                          const float *consts, int rows, int relu, float *dy, int lddy, hipStream_t stream);
+
 // K slices for a product that asks for `want`: at most max_splits (K over the fewest k a slice may get), at least one,
 // and above 8 a multiple of 8 -- whole slices per XCD (the kernels then keep a slice's tiles on one XCD)
 inline int whole_xcd_splits(int want, int max_splits)

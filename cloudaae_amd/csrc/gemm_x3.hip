@@ -17,6 +17,7 @@
 // slab is prefetched through registers as fp32 and split on its way into LDS.
 #include "common.h"
 #include "gemm.h"
+#include "bn_common.h"
 #include "../../include/cloudaae_hip.h"
 
 namespace cloudaae {
@@ -24,6 +25,7 @@ namespace cloudaae {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
 
 constexpr int X3_BK = 32;
 constexpr int X3_LDK = 40;
@@ -465,15 +467,27 @@ struct X3S {
     static constexpr int P_PIECES = 3 * TN;             // 1 KB DMA pieces per step: [plane][32 rows]
     static constexpr int LDS = A_BYTES + 3 * P_STAGE;
     static constexpr int JB = (TN - 1) / 2;             // the step's barrier sits behind the MFMAs of tile JB
+    static constexpr int T_STAGE = BN_DYC * 32 * 4;     // BNB: the constants of one slab's 32 channels, one stage per A stage
+    static constexpr int LDS_BNB = LDS + AS * T_STAGE;
+};
+
+// BNB: the big operand in memory is a batch-norm layer's y, and the operand multiplied is dy = bn_bwd_dy_hoisted(y) -- the
+// backward apply pass of a mean-pooled layer (bn.hip: bn_bwd_apply_kernel) folded into the input-gradient product that
+// consumed its output.  k of the product is the channel, a row tile lies inside one pooling group, so the map's constants
+// are one 1 KB piece per slab (bn_common.h: bn_dyc_index), brought in beside the slab of y.
+struct X3BnBwd {
+    const float *consts;      // [M / rows][K / 32][BN_DYC][32]
+    float *dy;                // [M][lddy]: written by the workgroups of column tile 0
+    int lddy, rows, relu;
 };
 
 // C[M,N] (+)= A[M,K] * P^T (+ bias[N]); P = x3_split_kernel planes of the [N][K] operand.  M % (128 TM) == 0, N % (32 TN) == 0,
 // K % 32 == 0.  grid.x = tiles.
-template <int TM, int TN, int AS>
+template <int TM, int TN, int AS, bool BNB>
 __global__ __launch_bounds__(256, 2) void gemm_x3s_kernel(int M, int N, int K, const float *__restrict__ A, int lda,
                                                           const __bf16 *__restrict__ P, float *__restrict__ C, int ldc,
                                                           const float *__restrict__ bias, int accumulate,
-                                                          double *__restrict__ colstats)
+                                                          double *__restrict__ colstats, X3BnBwd f)
 {
     typedef X3S<TM, TN, AS> G;
     extern __shared__ __attribute__((aligned(16))) unsigned char x3_lds[];
@@ -490,13 +504,26 @@ __global__ __launch_bounds__(256, 2) void gemm_x3s_kernel(int M, int N, int K, c
     const float *asrc = A + (size_t)(m0 + wave * 32 * TM + (lane >> 3)) * lda + 4 * ((lane & 7) ^ (lane >> 4));
     const size_t a8 = (size_t)8 * lda;
     unsigned char *lds_a = x3_lds + wave * G::A_WAVE;
+    // BNB: with every slab of A its piece of the constants, a quarter (two constants x 32 channels, 4 bytes per lane) per wave;
+    // read by all four waves, so it becomes visible at the barrier behind which the slab itself is first read
+    const float *tsrc = BNB ? f.consts + (size_t)(m0 / f.rows) * (size_t)(K >> 5) * (BN_DYC * 32) + wave * 64 + lane : nullptr;
+    unsigned char *lds_t = x3_lds + G::LDS + wave * 256;
     auto dma_a = [&](int slab, int stage) {
         const float *ga = asrc + (size_t)slab * 32;
         unsigned char *la = lds_a + stage * G::A_STAGE;
 #pragma unroll
         for (int t = 0; t < 4 * TM; ++t)
             __builtin_amdgcn_global_load_lds(ga + t * a8 + ((t & 1) ? ((lane & 4) ? -16 : 16) : 0), la + t * 1024, 16, 0, 0);
+        if (BNB)
+            __builtin_amdgcn_global_load_lds(tsrc + (size_t)slab * (BN_DYC * 32), lds_t + stage * G::T_STAGE, 4, 0, 0);
     };
+    // BNB: dy leaves through a buffer descriptor over this workgroup's rows that holds no bytes for column tiles other than
+    // the first (their stores are dropped by the range check: no branch in the step)
+    const int dybytes = (BNB && n0 == 0) ? (int)(((size_t)(G::BM - 1) * f.lddy + K) * sizeof(float)) : 0;
+    const __amdgpu_buffer_rsrc_t dyrs = __builtin_amdgcn_make_buffer_rsrc(
+        f.dy + (size_t)__builtin_amdgcn_readfirstlane(m0) * f.lddy, 0, __builtin_amdgcn_readfirstlane(dybytes), 0x00020000);
+    const unsigned dyoff = (unsigned)((wave * 32 * TM + fr) * f.lddy + 8 * fk) * 4u;
+    const bool relu = BNB && f.relu != 0;
     // P: piece pc (1 KB, linear) = plane pc / TN, rows 32 (pc % TN) ..; this wave takes pc = wave, wave + 4, ...
     const __bf16 *psrc = P + (size_t)n0 * 16 + 8 * lane;
     const size_t pplane = (size_t)N * 16, pstep = 3 * pplane;
@@ -533,12 +560,35 @@ __global__ __launch_bounds__(256, 2) void gemm_x3s_kernel(int M, int N, int K, c
                 acc[i][j][r] = 0.0f;
 
     bf16x8 af[2][3][TM], bp[2][3];
-    // the wave's operands of half ss of the slab in the A buffer -> register set buf
-    auto prepare_a = [&](int buf, int ss, int stage) {
+    // the wave's operands of half ss of the slab in the A buffer -> register set buf (BNB: `slab` = the slab staged there)
+    auto prepare_a = [&](int buf, int ss, int stage, int slab) {
+        float4v cst[BN_DYC][2];
+        if (BNB) {
+#pragma unroll
+            for (int q = 0; q < BN_DYC; ++q)
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh)
+                    cst[q][hh] = *reinterpret_cast<const float4v *>(x3_lds + G::LDS + stage * G::T_STAGE + q * 128 +
+                                                                    (16 * ss + 8 * fk + 4 * hh) * 4);
+        }
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-            const float4v x = *reinterpret_cast<const float4v *>(x3_lds + offa[ss][0] + i * 4096 + stage * G::A_STAGE);
-            const float4v y = *reinterpret_cast<const float4v *>(x3_lds + offa[ss][1] + i * 4096 + stage * G::A_STAGE);
+            float4v x = *reinterpret_cast<const float4v *>(x3_lds + offa[ss][0] + i * 4096 + stage * G::A_STAGE);
+            float4v y = *reinterpret_cast<const float4v *>(x3_lds + offa[ss][1] + i * 4096 + stage * G::A_STAGE);
+            if (BNB) {
+                float4v *v[2] = {&x, &y};
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        (*v[hh])[e] = bn_bwd_dy_hoisted((*v[hh])[e], cst[BN_DYC_SC][hh][e], cst[BN_DYC_SH][hh][e],
+                                                        cst[BN_DYC_MEAN][hh][e], cst[BN_DYC_RSTD][hh][e], cst[BN_DYC_M2][hh][e],
+                                                        cst[BN_DYC_GR][hh][e], cst[BN_DYC_A0][hh][e], cst[BN_DYC_A1][hh][e], relu);
+                // (past the last slab the last one is prepared again: the same values to the same place)
+                const unsigned o = dyoff + (unsigned)(i * 32 * f.lddy + slab * 32 + 16 * ss) * 4u;
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, x), dyrs, o, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, y), dyrs, o + 16u, 0, 0);
+            }
             split8(x, y, af[buf][0][i], af[buf][1][i], af[buf][2][i]);
         }
     };
@@ -564,7 +614,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3s_kernel(int M, int N, int K, c
         const int ring1 = ring == 2 ? 0 : ring + 1, ring2 = ring == 0 ? 2 : ring - 1;
         const int slab = g >> 1, ast = AS == 2 ? (slab & 1) : 0;
         if (!second_half)
-            prepare_a(abuf ^ 1, 1, ast);                   // (first half of the slab: the second half is there already)
+            prepare_a(abuf ^ 1, 1, ast, slab);             // (first half of the slab: the second half is there already)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int pb = (pb0 + j) & 1;
@@ -577,8 +627,9 @@ __global__ __launch_bounds__(256, 2) void gemm_x3s_kernel(int M, int N, int K, c
                 // planes of step g + 1 (and, in a slab's second half, the next slab of A): this wave's pieces have landed
                 // (vmcnt), everyone's (barrier); every wave is past step g - 1, whose ring slot the DMA below refills.
                 // AS == 2: the slab of A requested one step ago (behind the planes awaited here) may stay in flight.
+                // (BNB: the stores of dy were issued before that slab's request, so they are awaited here too)
                 if (AS == 2 && second_half)
-                    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(4 * TM) : "memory");
+                    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(4 * TM + (BNB ? 1 : 0)) : "memory");
                 else
                     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
@@ -587,7 +638,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3s_kernel(int M, int N, int K, c
                 if (!second_half)          // this wave has read both halves of its rows: refill that buffer
                     dma_a(min(slab + AS, nslab - 1), ast);
                 else
-                    prepare_a(abuf ^ 1, 0, AS == 2 ? (ast ^ 1) : 0);
+                    prepare_a(abuf ^ 1, 0, AS == 2 ? (ast ^ 1) : 0, min(slab + 1, nslab - 1));
             }
         }
     };
@@ -599,7 +650,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3s_kernel(int M, int N, int K, c
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     dma_p(min(1, nstep - 1), 1);
-    prepare_a(0, 0, 0);
+    prepare_a(0, 0, 0, 0);
     read_p(0, 0, 0);
     int ring = 0;
     for (int s = 0; s < nslab; ++s) {
@@ -659,22 +710,24 @@ __global__ __launch_bounds__(256, 2) void gemm_x3s_kernel(int M, int N, int K, c
     }
 }
 
-template <int TM, int TN, int AS>
+template <int TM, int TN, int AS, bool BNB = false>
 static int launch_x3s(const char *name, hipStream_t s, int M, int N, int K, const float *A, int lda, const void *planes, float *C,
-                      int ldc, const float *bias, int accumulate, double *cs)
+                      int ldc, const float *bias, int accumulate, double *cs, X3BnBwd f = X3BnBwd{nullptr, nullptr, 0, 1, 0})
 {
     typedef X3S<TM, TN, AS> G;
+    constexpr int bytes = BNB ? G::LDS_BNB : G::LDS;
+    static_assert(bytes <= 80 * 1024, "two workgroups per CU");
     static bool raised[64] = {};
     int dev = 0;
     CLOUDAAE_CHECK_HIP(hipGetDevice(&dev), name);
     if (dev >= 0 && dev < 64 && !raised[dev]) {
-        CLOUDAAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_x3s_kernel<TM, TN, AS>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS), name);
+        CLOUDAAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_x3s_kernel<TM, TN, AS, BNB>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, bytes), name);
         raised[dev] = true;
     }
     const int tiles = (M / G::BM) * (N / G::BN);
-    hipLaunchKernelGGL((gemm_x3s_kernel<TM, TN, AS>), dim3(tiles), dim3(256), G::LDS, s, M, N, K, A, lda,
-                       reinterpret_cast<const __bf16 *>(planes), C, ldc, bias, accumulate, cs);
+    hipLaunchKernelGGL((gemm_x3s_kernel<TM, TN, AS, BNB>), dim3(tiles), dim3(256), bytes, s, M, N, K, A, lda,
+                       reinterpret_cast<const __bf16 *>(planes), C, ldc, bias, accumulate, cs, f);
     return 0;
 }
 
@@ -690,6 +743,25 @@ static bool gemm_x3s_plan(int M, int N, int K, int &TM, int &TN)
     // every CU its two workgroups; 160-column tiles keep 128 rows (five accumulator tiles per row tile: 256 registers)
     TM = (TN == 4 && M % 256 == 0 && (long long)(M / 256) * (N / 128) >= 512) ? 2 : 1;
     return true;
+}
+
+bool gemm_x3s_bnbwd_served(int M, int N, int K, int rows)
+{
+    int TM, TN;
+    return gemm_x3s_plan(M, N, K, TM, TN) && TM == 1 && TN == 5 && rows > 0 && rows % 128 == 0 && M % rows == 0;
+}
+
+int gemm_x3s_bnbwd_launch(const char *name, int M, int N, int K, const float *y, int ldy, const void *planes, float *dx, int lddx,
+                          const float *consts, int rows, int relu, float *dy, int lddy, hipStream_t stream)
+{
+    CLOUDAAE_REQUIRE(gemm_x3s_bnbwd_served(M, N, K, rows), name, "product not served");
+    CLOUDAAE_REQUIRE(ldy >= K && lddy >= K && lddx >= N && ldy % 4 == 0 && lddy % 4 == 0, name, "bad leading dimension");
+    const int rc = launch_x3s<1, 5, 2, true>(name, stream, M, N, K, y, ldy, planes, dx, lddx, nullptr, 0, nullptr,
+                                             X3BnBwd{consts, dy, lddy, rows, relu});
+    if (rc != 0)
+        return rc;
+    CLOUDAAE_CHECK_LAUNCH(name);
+    return 0;
 }
 
 } // namespace cloudaae

@@ -500,6 +500,21 @@ def drop_deferred_dw():
     del _PENDING_DW[:]
 
 
+# gemm_dtype "bf16x3": the batch norm behind dgcnn_agg forms dy INSIDE the layer's input-gradient product
+# (cloudaae_bn_backward_dx_bf16x3: no pass that reads y and writes dy).  Same bits; False takes the two calls.
+AGG_BWD_FUSED = True
+
+
+class _AggBwdLink(object):
+    """What ConcatLinearFn's split-product forward leaves on its output for the batch norm that consumes it: the
+    planes of W for dx = dy W^T.  BatchNormFn.backward computes dx with them and leaves it here for
+    ConcatLinearFn.backward, which runs next."""
+
+    def __init__(self, planes_bwd, Ktot, want_dx):
+        self.planes_bwd, self.Ktot, self.want_dx = planes_bwd, Ktot, want_dx
+        self.dcat = self.dy = None
+
+
 class ConcatLinearFn(torch.autograd.Function):
     """Linear over the channel-concatenation of several [M,Ci] inputs
     (models/pointnet_ycb_23_decoder_4.py:410: conv2d(tf.concat([net1..net4], -1))).
@@ -585,6 +600,9 @@ class ConcatLinearFn(torch.autograd.Function):
                 _lib.host(_mark, rec)
             if parts > 0:
                 y._cloudaae_colstats = (ws, parts, M, N)
+            ctx.link = None
+            if AGG_BWD_FUSED and BN_SYNC is None:
+                ctx.link = y._cloudaae_agg_bwd = _AggBwdLink(ctx.planes_bwd, Ktot, any(t.requires_grad for t in nets))
             ctx.save_for_backward(w, *nets)
             ctx.widths, ctx.xp, ctx.bvar = widths, xp, b
             return y
@@ -622,12 +640,18 @@ class ConcatLinearFn(torch.autograd.Function):
         xp = ctx.cat.data_ptr() if ctx.cat is not None else ctx.xp
         dcat = None
         if any(ctx.needs_input_grad[4:]):
-            dcat = _lib.empty((M, Ktot), dtype=torch.float32, device=w.device)
-            if ctx.x3:
-                _lib.check(L().cloudaae_gemm_bf16x3p(M, Ktot, N, ptr(dy), N, ptr(ctx.planes_bwd), ptr(dcat), Ktot, None, 0, None,
-                                                     stream()), "cloudaae_gemm_bf16x3p")
+            link = ctx.link if ctx.x3 else None
+            if link is not None and link.dcat is not None and link.dy is not None and link.dy.data_ptr() == dy.data_ptr():
+                dcat = link.dcat        # the batch norm's backward formed dy inside this product already
             else:
-                gemm(0, 1, M, Ktot, N, ptr(dy), N, ptr(w), N, ptr(dcat), Ktot, bf16=ctx.bf16, device=w.device)
+                dcat = _lib.empty((M, Ktot), dtype=torch.float32, device=w.device)
+                if ctx.x3:
+                    _lib.check(L().cloudaae_gemm_bf16x3p(M, Ktot, N, ptr(dy), N, ptr(ctx.planes_bwd), ptr(dcat), Ktot, None, 0, None,
+                                                         stream()), "cloudaae_gemm_bf16x3p")
+                else:
+                    gemm(0, 1, M, Ktot, N, ptr(dy), N, ptr(w), N, ptr(dcat), Ktot, bf16=ctx.bf16, device=w.device)
+            if link is not None:
+                link.dcat = link.dy = None
             if ctx.slot is not None and ctx.cat is None:
                 ctx.slot.dcat = dcat
         gw = _ParamGrad(w, ctx.needs_input_grad[1])
@@ -696,6 +720,7 @@ class BatchNormFn(torch.autograd.Function):
         # written by this function's backward (see LinearFn.forward: bias_grad_by_bn)
         ctx.set_materialize_grads(False)
         ctx.lin_bias = lin_bias
+        ctx.agg_link = getattr(y, "_cloudaae_agg_bwd", None)      # (ConcatLinearFn: the product that made y can form dy itself)
         yp, ldy = rows_ptr(y)
         M, C = y.shape
         dev = y.device
@@ -799,6 +824,18 @@ class BatchNormFn(torch.autograd.Function):
                 pool_rows, pool_mode, ptr(dpooled), ptr(pooled), ptr(ties), ptr(dy), C, ptr(gg.buf), ptr(gb.buf),
                 ptr(glb.buf), acc, ptr(ctx.pstats) if dout is None else None, ptr(ws), ctx.sync.arg(C, y.device),
                 stream()), "cloudaae_bn_backward_sync")
+        elif (ctx.agg_link is not None and ctx.agg_link.want_dx and dout is None and pool_mode == 1 and yp % 16 == 0 and
+              ldy % 4 == 0 and L().cloudaae_bn_backward_dx_bf16x3_supported(M, C, ctx.agg_link.Ktot, pool_rows)):
+            # dgcnn_agg with split products: dy is formed inside dx = dy W^T, no pass of its own over y (same bits)
+            link = ctx.agg_link
+            consts = _lib.empty(int(L().cloudaae_bn_backward_dx_bf16x3_consts_bytes(M, C, pool_rows)) // 4, dtype=torch.float32,
+                                device=y.device)
+            dcat = _lib.empty((M, link.Ktot), dtype=torch.float32, device=y.device)
+            _lib.check(L().cloudaae_bn_backward_dx_bf16x3(
+                M, C, yp, ldy, ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_var), training, relu, pool_rows, ptr(dpooled),
+                ptr(dy), C, ptr(gg.buf), ptr(gb.buf), ptr(glb.buf), acc, ptr(ctx.pstats), ptr(ws), ptr(consts), link.Ktot,
+                ptr(link.planes_bwd), ptr(dcat), link.Ktot, stream()), "cloudaae_bn_backward_dx_bf16x3")
+            link.dcat, link.dy = dcat, dy
         else:
             _lib.check(L().cloudaae_bn_backward(
                 M, C, yp, ldy, ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_var), training, relu, ptr(dout), C,

@@ -48,7 +48,7 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * 601: cloudaae_selftest_div_by added.  602: cloudaae_icp_point_to_point and cloudaae_f64_to_f32 added; later, still
  * under 602 (additions only, no existing argument list or layout changed): cloudaae_frame_segments,
  * cloudaae_radius_outlier, cloudaae_ragged_fps and their workspace queries; cloudaae_dev_gemm_folded (development /
- * test entry). */
+ * test entry); cloudaae_bn_backward_dx_bf16x3 and its two queries. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -308,6 +308,22 @@ int cloudaae_gemm_bf16x3p_supported(int M, int N, int K);
 int cloudaae_gemm_bf16x3p_colstats_parts(int M, int N, int K);
 int cloudaae_gemm_bf16x3p(int M, int N, int K, const float *A, int lda, const void *planes, float *C, int ldc,
                           const float *bias, int accumulate, double *colstats, cloudaae_stream_t stream);
+
+/* Batch-norm backward of a mean-pooled layer (cloudaae_bn_backward with pool_mode 1 and no dout) AND the input-gradient
+ * product of the linear layer in front of it, dx[M,N] = dy[M,C] P^T (cloudaae_gemm_bf16x3p with the planes of the [N][C]
+ * weight), as one call: the per-channel sums are finalised as ever, but the pass that would read y and write dy is gone --
+ * the product reads y, forms every dy element in registers (the same fp32 operations in the same order) on its way into the
+ * matrix cores, and its first column tile stores dy for the weight-gradient product.  dy, dx, dgamma, dbeta, dbias are
+ * bit-identical to the two calls.  Served (cloudaae_bn_backward_dx_bf16x3_supported): C % 32 == 0, N % 160 == 0 and
+ * N % 128 != 0, M % 128 == 0, pool_rows % 128 == 0 (a 128-row tile inside one pooling group); anything else is refused.
+ * consts: scratch of cloudaae_bn_backward_dx_bf16x3_consts_bytes(M, C, pool_rows) bytes, 16-byte aligned. */
+int cloudaae_bn_backward_dx_bf16x3_supported(int M, int C, int N, int pool_rows);
+long long cloudaae_bn_backward_dx_bf16x3_consts_bytes(int M, int C, int pool_rows);
+int cloudaae_bn_backward_dx_bf16x3(int M, int C, const float *y, int ldy, const float *gamma, const float *beta,
+                                   const float *save_mean, const float *save_var, int training, int relu, int pool_rows,
+                                   const float *dpooled, float *dy, int lddy, float *dgamma, float *dbeta, float *dbias,
+                                   int accumulate_param_grads, const double *pool_stats, void *workspace, void *consts,
+                                   int N, const void *planes, float *dx, int lddx, cloudaae_stream_t stream);
 
 /* ---- activations kept as bfloat16 in HBM (BASELINE configs[2]: "bf16 MLPs") --------------------------------------
  * The same products as cloudaae_gemm_bf16 (conv2d 1x1 and its two gradient products, utils/tf_util.py:161-166) with
