@@ -118,6 +118,10 @@ _SIGNATURES = {
     "cloudaae_icp_point_to_point": [_I, _I, _P, _I, _L, _I, _P, _I, _L, _P, _P, _D, _D, _I, _I, _D, _D, _P, _P, _P,
                                     _P, _P, _P, _P],
     "cloudaae_f64_to_f32": [_L, _P, _P, _P],
+    "cloudaae_pose_score": [_I, _I, _I, _P, _I, _L, _P, _P, _P, _P, _P, _P, _P],
+    "cloudaae_pose_matrix": [_I, _P, _I, _P, _P, _P],
+    "cloudaae_pose_stack": [_I, _P, _P, _P, _P],
+    "cloudaae_cloud_diameter": [_I, _I, _P, _I, _L, _P, _P, _P],
     "cloudaae_frame_segments": [_I, _I, _I, _P, _P, _P, _I, _P, _P, _F, _P, _P, _P, _P, _L, _P],
     "cloudaae_radius_outlier": [_I, _P, _P, _L, _I, _F, _I, _P, _P, _P, _P, _P, _L, _P],
     "cloudaae_ragged_fps": [_I, _P, _P, _L, _I, _P, _P, _P, _P, _L, _P],
@@ -336,7 +340,9 @@ def lib():
         cdll.cloudaae_hpr_workspace_bytes.argtypes = [_I, _I]
         for q, sig in (("cloudaae_frame_segments_workspace_bytes", [_I, _I, _I, _I]),
                        ("cloudaae_radius_outlier_workspace_bytes", [_I, _L]),
-                       ("cloudaae_ragged_fps_workspace_bytes", [_L])):
+                       ("cloudaae_ragged_fps_workspace_bytes", [_L]),
+                       ("cloudaae_pose_score_workspace_bytes", [_I, _I, _I]),
+                       ("cloudaae_cloud_diameter_workspace_bytes", [_I, _I])):
             getattr(cdll, q).argtypes = sig
             getattr(cdll, q).restype = ctypes.c_longlong
         cdll.cloudaae_gemm_f32_splits.argtypes = [_I, _I, _I]

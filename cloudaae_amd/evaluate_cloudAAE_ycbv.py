@@ -5,7 +5,9 @@ What is mirrored: the eval-mode forward (batch-norm statistics from the moving a
 the 4N -> N farthest point sampling of the reconstruction + gather + Chamfer against the first N
 observed points (:449-451), the translation error of the prediction and of the plain centroid
 (:455-460), the SO(3) error (:468-474), and on request the ICP refinement of the predicted pose against the first N
-inlier points (:606-628, open3d's point-to-point registration_icp; here utils/icp.py, one HIP launch).  The input side, from the
+inlier points (:606-628, open3d's point-to-point registration_icp; here utils/icp.py, one HIP launch).  On request the
+predicted and the refined pose are scored with ADD and ADD-S (utils/pose_score.py: not in the reference, which prints
+mean translation and rotation errors only; DESIGN.md "Pose scores").  The input side, from the
 YCB-Video test records (<seq>_pcnn.tfrecord) to the element, is element_from_frames (utils/segment.py on the GPU,
 :125-335); main() is the reference's command line without the visualisation.  What is NOT: the RGB channels, the
 result files.
@@ -14,6 +16,7 @@ result files.
     out = evaluate_batch(graph, element)       # element: xyz_inlier, visiblePoints_org, class_id,
                                                #          translation, axisangle (device tensors)
     out = evaluate_batch(graph, element, icp=True) # + obj_batch [B,M,>=3]: adds the *_icp outputs
+    out = evaluate_batch(graph, element, icp=True, score=True)   # adds add_pred, adds_pred, add_icp, adds_icp [B]
 """
 import argparse
 import math
@@ -30,10 +33,11 @@ from .tf_ops.sampling import tf_sampling
 from .train_cloudAAE_ycbv import NUM_CLASS
 from .utils import _functions as F
 from .utils import icp as icp_util
+from .utils import pose_score as score_util
 from .utils import segment as seg_util
 
 
-def evaluate_batch(graph, element, replay=False, icp=None):
+def evaluate_batch(graph, element, replay=False, icp=None, score=None):
     """One pass of evaluate_cloudAAE_ycbv.py:421-477 on a batch.  Returns the tensors its loop
     fetches (:546-560): xyz_recon [B,4N,3], xyz_recon_FPS [B,N,3], rot_pred, trans_pred, the three
     losses with their per-sample values, mean_dist_loss, element_mean.
@@ -44,11 +48,16 @@ def evaluate_batch(graph, element, replay=False, icp=None):
     refined against the network's input points; needs element['obj_batch'] [B,M,>=3] float32 (the class's object
     model) and adds rot_icp, trans_icp, transformation_icp, fitness_icp, inlier_rmse_icp, iterations_icp and the
     errors of the refined pose, trans_loss_icp / axag_loss_icp with their per-sample values.  The other outputs
-    are those of icp=None."""
+    are those of icp=None.
+    score=True: the predicted pose [rot_pred | trans_pred] and, with icp, the refined one (transformation_icp) are
+    scored against [axisangle | translation] on element['obj_batch'] by one cloudaae_pose_score launch: adds add_pred,
+    adds_pred and, with icp, add_icp, adds_icp [B] float64 (ADD and ADD-S in metres).  The other outputs are those of
+    score=None."""
     icp = _icp_params(icp)
+    score = bool(score)
     if replay:
-        return _replayed(graph, element, icp)
-    return _evaluate(graph, element, icp)
+        return _replayed(graph, element, icp, score)
+    return _evaluate(graph, element, icp, score)
 
 
 def _icp_params(icp):
@@ -60,17 +69,20 @@ def _icp_params(icp):
     return dict(icp)
 
 
-def _replayed(graph, element, icp=None):
+def _replayed(graph, element, icp=None, score=False):
     N = graph.NUM_POINT
     src = {'xyz_inlier': (element['xyz_inlier'], torch.float32),
            'visiblePoints_org': (element['visiblePoints_org'][:, 0:N, :], torch.float32),
            'class_id': (element['class_id'], torch.int64), 'translation': (element['translation'], torch.float32),
            'axisangle': (element['axisangle'], torch.float64)}
-    if icp is not None:
+    if icp is not None or score:
+        require(element.get('obj_batch') is not None, "icp and score need element['obj_batch'] [B, M, >=3]")
         src['obj_batch'] = (element['obj_batch'], torch.float32)
     key = tuple((k, tuple(v.shape)) for k, (v, _) in src.items())
     if icp is not None:
         key += (('icp', tuple(sorted(icp.items()))),)
+    if score:
+        key += (('score',),)
     plans = graph.__dict__.setdefault('_eval_plans', {})
     if key not in plans:
         static = {k: torch.empty(tuple(v.shape), dtype=dt, device=graph.device) for k, (v, dt) in src.items()}
@@ -83,7 +95,7 @@ def _replayed(graph, element, icp=None):
     if plan is None:
         plan = _lib.StepPlan(graph.device)
         with _lib.record(plan):
-            out = _evaluate(graph, static, icp)
+            out = _evaluate(graph, static, icp, score)
         if plan.foreign_ops:
             import warnings
             warnings.warn("evaluation pass not replayable (torch kernels inside: %s)" % sorted(set(plan.foreign_ops)))
@@ -95,7 +107,7 @@ def _replayed(graph, element, icp=None):
     return out
 
 
-def _evaluate(graph, element, icp=None):
+def _evaluate(graph, element, icp=None, score=False):
     N = graph.NUM_POINT
     xyz = element['xyz_inlier']
     require(xyz.dim() == 3 and xyz.shape[1] >= N and xyz.shape[2] == 3, "xyz_inlier must be [B, >=num_point, 3]")
@@ -126,6 +138,28 @@ def _evaluate(graph, element, icp=None):
                element_mean=element_mean, end_points=end_points)
     if icp is not None:
         out.update(_refine(element, xyz[:, 0:N, :], rot_pred, trans_pred, translation, icp))
+    if score:
+        out.update(_score(element, rot_pred, trans_pred, translation, out.get('transformation_icp')))
+    return out
+
+
+def _score(element, rot_pred, trans_pred, translation, transformation_icp):
+    """ADD and ADD-S of the predicted pose and, when given, of the refined one against the ground-truth pose."""
+    obj = element.get('obj_batch')
+    require(obj is not None, "score needs element['obj_batch'] [B, M, >=3] (the object model of each sample's class)")
+    require(obj.dim() == 3 and obj.shape[0] == rot_pred.shape[0] and obj.shape[2] >= 3 and obj.dtype == torch.float32,
+            "obj_batch must be a float32 [B, M, >=3] tensor")
+    axisangle = element['axisangle']
+    require(axisangle.dtype in (torch.float32, torch.float64), "axisangle must be float32 or float64")
+    with torch.no_grad():
+        gt = score_util.pose_matrix(axisangle, translation.contiguous())
+        est = score_util.pose_matrix(rot_pred.contiguous(), trans_pred.contiguous())
+        if transformation_icp is not None:
+            est = score_util.stack_poses(est, transformation_icp)
+        r = score_util.score_poses(obj, est, gt)
+    out = dict(add_pred=r['add'][:, 0], adds_pred=r['adds'][:, 0])
+    if transformation_icp is not None:
+        out.update(add_icp=r['add'][:, 1], adds_icp=r['adds'][:, 1])
     return out
 
 
@@ -212,7 +246,8 @@ def main(argv=None):
     Reads <data_dir>/<seq>_pcnn.tfrecord of the class's test sequences (:43-63) file after file, in record order (the
     reference interleaves them at random with sample_from_datasets), and prints the per-batch and the final loss
     lines (:568, :652-657).  A last batch smaller than --batch_size is not evaluated (the reference's reshape to
-    BATCH_SIZE, :338, cannot take it).  --icp adds the refined pose's losses."""
+    BATCH_SIZE, :338, cannot take it).  --icp adds the refined pose's losses.  --score prints, after the final line,
+    the ADD / ADD-S summary of the predicted (and refined) poses per class and over all (PoseScoreLog.lines)."""
     from . import tfrecord_io
     from . import train_cloudAAE_ycbv as T
     p = argparse.ArgumentParser()
@@ -224,6 +259,7 @@ def main(argv=None):
     p.add_argument("--num_point", type=int, default=256)
     p.add_argument("--batch_size", type=int, default=1)
     p.add_argument("--icp", action="store_true")
+    p.add_argument("--score", action="store_true", help="ADD / ADD-S, AUC and accuracy summary of the scored poses")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--frames_per_launch", type=int, default=8)
     p.add_argument("--gpu", type=int, default=0)
@@ -238,6 +274,10 @@ def main(argv=None):
     files = [f for f in files if os.path.exists(f)]
     require(files, "no <seq>_pcnn.tfrecord of class %d under %s" % (args.target_cls, args.data_dir))
     pending, batch_idx, tot_trans, tot_axag, n_launch = None, 0, 0.0, 0.0, 0
+    log = None
+    if args.score:
+        diam = score_util.model_diameter(torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda())
+        log = score_util.PoseScoreLog(("pred", "icp") if args.icp else ("pred",), diameters=diam)
 
     def frames():
         for fn in files:
@@ -260,7 +300,11 @@ def main(argv=None):
         while len(pending["class_id"]) >= args.batch_size:
             b = _take(pending, 0, args.batch_size)
             pending = _take(pending, args.batch_size, len(pending["class_id"]))
-            out = evaluate_batch(graph, {k: v for k, v in b.items() if isinstance(v, torch.Tensor)}, icp=args.icp)
+            out = evaluate_batch(graph, {k: v for k, v in b.items() if isinstance(v, torch.Tensor)}, icp=args.icp,
+                                 score=args.score)
+            if log is not None:
+                log.append(b["class_id"], torch.stack([out["add_" + n] for n in log.poses], dim=1),
+                           torch.stack([out["adds_" + n] for n in log.poses], dim=1), seq=b["seq_id"], frame=b["frame_id"])
             tl, al = float(out["trans_loss"]), float(out["axag_loss"])
             tot_trans += tl
             tot_axag += al
@@ -273,6 +317,9 @@ def main(argv=None):
     print("batch size %d" % batch_idx)
     if batch_idx:
         print("trans_loss %f axag_loss %f" % (tot_trans / batch_idx, tot_axag / batch_idx))
+    if log is not None:
+        for line in log.lines():
+            print(line)
     sys.stdout.flush()
     return 0
 

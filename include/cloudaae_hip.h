@@ -48,7 +48,8 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * 601: cloudaae_selftest_div_by added.  602: cloudaae_icp_point_to_point and cloudaae_f64_to_f32 added; later, still
  * under 602 (additions only, no existing argument list or layout changed): cloudaae_frame_segments,
  * cloudaae_radius_outlier, cloudaae_ragged_fps and their workspace queries; cloudaae_dev_gemm_folded (development /
- * test entry); cloudaae_bn_backward_dx_bf16x3 and its two queries. */
+ * test entry); cloudaae_bn_backward_dx_bf16x3 and its two queries; cloudaae_pose_score, cloudaae_cloud_diameter (each with
+ * a workspace query), cloudaae_pose_matrix and cloudaae_pose_stack. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -745,6 +746,40 @@ int cloudaae_icp_point_to_point(int b, int m, const float *src, int src_point_st
                                 double *rmse, int *iterations, cloudaae_stream_t stream);
 /* y[i] = (float)x[i], round to nearest even (an f64 result handed to an fp32 consumer, e.g. a loss kernel). */
 int cloudaae_f64_to_f32(long long n, const double *x, float *y, cloudaae_stream_t stream);
+
+/* ---- pose scores: ADD, ADD-S, model diameter ("Pose scores", has the definition) ---- */
+
+/* ADD and ADD-S of p estimated poses per sample against the sample's ground truth, in float64 on the exactly promoted
+ * float32 model.  Per sample s:
+ *   model: m points (x, y, z) at model + s*cloud_stride + i*point_stride (strides in floats, >= 3 per point: obj_batch
+ *   [b,2048,6] goes in unsliced); est [b,p,4,4] and gt [b,4,4] float64 row-major (only the top three rows are read).
+ * With g_i = gt x_i and e_i = est x_i (((R00 x + R01 y) + R02 z) + t0 row by row, no fma):
+ *   add [b,p]  = (1/m) sum_i |g_i - e_i|;
+ *   nn_d2 [b,p,m] (optional, may be NULL) = min_j |g_i - e_j|^2, |d|^2 = (dx^2 + dy^2) + dz^2;
+ *   adds [b,p] = (1/m) sum_i sqrt(nn_d2[i]).
+ * Both sums: blocks of 64 consecutive points, each added as a binary tree (halves folded: 64 -> 32 -> ... -> 1), the
+ * blocks' sums added in ascending order.  Exact fp64 brute force over ceil(m/64) workgroups per sample and pose plus a
+ * one-lane-per-result finishing launch; no floating-point atomics: the result does not depend on b, p or the run.
+ * workspace: cloudaae_pose_score_workspace_bytes(b, p, m) bytes (-1 for a bad argument), need not be initialised.
+ * Limits: b, p, m >= 1; b * p * ceil(m/64) <= 2^31 - 1. */
+long long cloudaae_pose_score_workspace_bytes(int b, int p, int m);
+int cloudaae_pose_score(int b, int p, int m, const float *model, int point_stride, long long cloud_stride,
+                        const double *est, const double *gt, double *add, double *adds, double *nn_d2,
+                        void *workspace, cloudaae_stream_t stream);
+/* T0 of "Pose refinement": out [b,4,4] float64 row-major = [Rodrigues(rot) | trans; 0 0 0 1] from an axis-angle
+ * rot [b,3], float32 (rot_is_f64 = 0: the network's) or float64 (rot_is_f64 = 1: the ground truth's), and a float32
+ * translation [b,3].  A zero rot gives the identity rotation. */
+int cloudaae_pose_matrix(int b, const void *rot, int rot_is_f64, const float *trans, double *out,
+                         cloudaae_stream_t stream);
+/* out [b,2,4,4] = (first [b,4,4], second [b,4,4]) sample by sample: two pose sets as the est of one
+ * cloudaae_pose_score launch with p = 2. */
+int cloudaae_pose_stack(int b, const double *first, const double *second, double *out, cloudaae_stream_t stream);
+/* diam [c] float64 = sqrt(max_{i<j} ((dx^2 + dy^2) + dz^2)) over the m points of each of c clouds (0 for m = 1), read
+ * with strides as above.  The same tile loop as cloudaae_pose_score with max in place of min; max is exact, so no order
+ * matters.  workspace: cloudaae_cloud_diameter_workspace_bytes(c, m) bytes.  Limit: c * ceil(m/64) <= 2^31 - 1. */
+long long cloudaae_cloud_diameter_workspace_bytes(int c, int m);
+int cloudaae_cloud_diameter(int c, int m, const float *model, int point_stride, long long cloud_stride, double *diam,
+                            void *workspace, cloudaae_stream_t stream);
 
 /* ---- evaluation inputs from RGB-D frames (evaluate_cloudAAE_ycbv.py:164-271) ---- */
 
