@@ -117,6 +117,9 @@ _SIGNATURES = {
     "cloudaae_hidden_point_removal_rows": [_I, _I, _P, _P, _U, _I, _P, _P, _P, _P, _P, _P],
     "cloudaae_icp_point_to_point": [_I, _I, _P, _I, _L, _I, _P, _I, _L, _P, _P, _D, _D, _I, _I, _D, _D, _P, _P, _P,
                                     _P, _P, _P, _P],
+    "cloudaae_icp_point_to_plane": [_I, _I, _P, _I, _L, _I, _P, _I, _L, _P, _I, _P, _P, _D, _D, _I, _I, _D, _D, _P, _P,
+                                    _P, _P, _P, _P, _P],
+    "cloudaae_estimate_normals": [_I, _P, _P, _I, _L, _I, _P, _I, _L, _F, _I, _P, _P, _P, _P, _P, _L, _P],
     "cloudaae_f64_to_f32": [_L, _P, _P, _P],
     "cloudaae_pose_score": [_I, _I, _I, _P, _I, _L, _P, _P, _P, _P, _P, _P, _P],
     "cloudaae_pose_matrix": [_I, _P, _I, _P, _P, _P],
@@ -342,6 +345,7 @@ def lib():
                        ("cloudaae_radius_outlier_workspace_bytes", [_I, _L]),
                        ("cloudaae_ragged_fps_workspace_bytes", [_L]),
                        ("cloudaae_pose_score_workspace_bytes", [_I, _I, _I]),
+                       ("cloudaae_estimate_normals_workspace_bytes", [_I, _L]),
                        ("cloudaae_cloud_diameter_workspace_bytes", [_I, _I])):
             getattr(cdll, q).argtypes = sig
             getattr(cdll, q).restype = ctypes.c_longlong

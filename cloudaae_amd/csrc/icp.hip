@@ -18,6 +18,12 @@
 //   - thread 0 solves the 3x3 orthogonal Procrustes problem by Horn's quaternion method (the proper rotation that
 //     maximises tr(R^T Sigma): Umeyama's answer with the reflection fix) with a cyclic Jacobi eigen-solver on the
 //     4x4 symmetric matrix, and broadcasts the update and the convergence decision through LDS.
+//
+// cloudaae_icp_point_to_plane is the same kernel template with another estimator (PLANE = true): the same hash grid,
+// matching, tie rule, statistics and stopping rule; the sums of an update are the 21 + 6 entries of A = sum J J^T and
+// b = sum J r (J = [p x n; n], r = (p - q) . n, n the matched target point's normal, read from global memory by the
+// match's index), taken in the same order; thread 0 solves the 6x6 system by LDL^T.  The point-to-point instantiation
+// keeps its arithmetic statement for statement.
 #include "common.h"
 #include "../../include/cloudaae_hip.h"
 #include "pose_math.h"   // icp_rodrigues, icp_apply: shared with pose_score.hip
@@ -41,7 +47,8 @@ constexpr int ICP_WAVES = ICP_THREADS / 64;
 constexpr int ICP_PER_LANE = 8;
 constexpr int ICP_MAX_M = ICP_THREADS * ICP_PER_LANE;     // source points of a cloud (CLOUDAAE_ICP_MAX_POINTS)
 constexpr int ICP_MAX_N = 4096;                           // target points of a cloud (CLOUDAAE_ICP_MAX_POINTS)
-constexpr int ICP_SUMS = 17;
+constexpr int ICP_SUMS = 17;                              // point to point: count, sum p, sum q, sum q p^T, sum d^2
+constexpr int ICP_PLANE_SUMS = 29;                        // point to plane: count, sum d^2, A's upper triangle, b
 constexpr int ICP_JACOBI_SWEEPS = 16;
 constexpr double ICP_CELL_CLAMP = 268435456.0;            // 2^28: cell coordinates (and their neighbours) fit an int
 constexpr double ICP_REACH_MARGIN = 1e-6;                 // cell units; rounding of p * (1/h) is far below it
@@ -55,9 +62,9 @@ static int icp_hash_bits(int n)
     return bits;
 }
 
-static size_t icp_lds_bytes(int n, int hbits)
+static size_t icp_lds_bytes(int n, int hbits, int sums)
 {
-    return sizeof(double) * (ICP_WAVES * ICP_SUMS + 64) + sizeof(float4) * (size_t)n +
+    return sizeof(double) * (ICP_WAVES * sums + 64) + sizeof(float4) * (size_t)n +
            sizeof(int) * ((size_t)(1 << hbits) + 1 + ICP_WAVES);
 }
 
@@ -205,21 +212,26 @@ __host__ __device__ inline void icp_procrustes(const double *S, double *R)
 namespace {
 
 struct IcpShared {
-    double *red;      // [ICP_WAVES][ICP_SUMS] per-wave partial sums
-    double *bc;       // [0..11] T (3x4), [12..23] update U (3x4), [24] continue flag, [25] apply flag, [32..48] sums
+    double *red;      // [ICP_WAVES][NS] per-wave partial sums
+    double *bc;       // [0..11] T (3x4), [12..23] update U (3x4), [24] continue flag, [25] apply flag, [32..32+NS) sums
     float4 *tgt;      // [n] target points sorted by bucket, .w = the point's index (int bits)
     int *start;       // [H + 1] bucket starts
     int *wsum;        // [ICP_WAVES] scan totals
 };
 
-// Correspondences of this lane's points at rho and the workgroup's 17 sums (thread 0 leaves them in L.bc[32..48]).
+// Correspondences of this lane's points at rho and the workgroup's sums (thread 0 leaves them in L.bc[32..32+NS)):
+// the 17 of the point-to-point update, or (PLANE, nrm = the cloud's target normals [n,3]) count, sum d^2, the upper
+// triangle of sum J J^T row by row and sum J r.
+template <bool PLANE>
 __device__ __forceinline__ void icp_match(const IcpShared &L, const double (&P)[ICP_PER_LANE][3], int m, double rho2,
-                                          double inv_h, double reach, unsigned mask, const double *ctr)
+                                          double inv_h, double reach, unsigned mask, const double *ctr,
+                                          const double *__restrict__ nrm)
 {
+    constexpr int NS = PLANE ? ICP_PLANE_SUMS : ICP_SUMS;
     const int tid = threadIdx.x;
-    double acc[ICP_SUMS];
+    double acc[NS];
 #pragma unroll
-    for (int k = 0; k < ICP_SUMS; ++k)
+    for (int k = 0; k < NS; ++k)
         acc[k] = 0.0;
 #pragma unroll
     for (int k = 0; k < ICP_PER_LANE; ++k) {
@@ -257,7 +269,26 @@ __device__ __forceinline__ void icp_match(const IcpShared &L, const double (&P)[
                         }
                     }
                 }
-        if (bj >= 0) {
+        if constexpr (PLANE) {
+            if (bj >= 0) {
+                const double *nq = nrm + 3LL * bj;
+                const double n0 = nq[0], n1 = nq[1], n2 = nq[2];
+                const double ex = px - (double)bq.x, ey = py - (double)bq.y, ez = pz - (double)bq.z;
+                const double res = (ex * n0 + ey * n1) + ez * n2;
+                const double J[6] = {py * n2 - pz * n1, pz * n0 - px * n2, px * n1 - py * n0, n0, n1, n2};
+                acc[0] += 1.0;
+                acc[1] += best;
+                int t = 2;
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int b = a; b < 6; ++b)
+                        acc[t++] += J[a] * J[b];
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+                    acc[23 + a] += J[a] * res;
+            }
+        } else if (bj >= 0) {
             const double ax = px - ctr[0], ay = py - ctr[1], az = pz - ctr[2];
             const double bx = (double)bq.x - ctr[0], by = (double)bq.y - ctr[1], bz = (double)bq.z - ctr[2];
             acc[0] += 1.0;
@@ -280,21 +311,21 @@ __device__ __forceinline__ void icp_match(const IcpShared &L, const double (&P)[
         }
     }
 #pragma unroll
-    for (int k = 0; k < ICP_SUMS; ++k)
+    for (int k = 0; k < NS; ++k)
         acc[k] = wave_sum(acc[k]);
     const int w = tid >> 6;
     if ((tid & 63) == 0) {
 #pragma unroll
-        for (int k = 0; k < ICP_SUMS; ++k)
-            L.red[w * ICP_SUMS + k] = acc[k];
+        for (int k = 0; k < NS; ++k)
+            L.red[w * NS + k] = acc[k];
     }
     __syncthreads();
     if (tid == 0) {
         #pragma unroll
-        for (int k = 0; k < ICP_SUMS; ++k) {
+        for (int k = 0; k < NS; ++k) {
             double v = L.red[k];
             for (int i = 1; i < ICP_WAVES; ++i)
-                v += L.red[i * ICP_SUMS + k];
+                v += L.red[i * NS + k];
             L.bc[32 + k] = v;
         }
     }
@@ -322,6 +353,78 @@ __device__ inline void icp_update(const double *s, const double *ctr, double *U)
     }
 }
 
+// Thread 0: the point-to-plane update U (3x4) from the sums s = (count, sum d^2, A's upper triangle row by row, b).
+// A x = -b by LDL^T; x = (alpha, beta, gamma, t); U = [Rz(gamma) Ry(beta) Rx(alpha) | t].  false (U = I: the caller
+// leaves T and P alone) with fewer than six correspondences, a pivot that is not a finite number > 0, or a solution
+// that is not finite.
+__host__ __device__ inline bool icp_plane_update(const double *s, double *U)
+{
+    if (!(s[0] >= 6.0))
+        return false;
+    double A[6][6], Lm[6][6], d[6], x[6];
+    int t = 2;
+    for (int a = 0; a < 6; ++a)
+        for (int b = a; b < 6; ++b)
+            A[a][b] = A[b][a] = s[t++];
+    for (int j = 0; j < 6; ++j) {
+        double dj = A[j][j];
+        for (int k = 0; k < j; ++k)
+            dj -= (Lm[j][k] * Lm[j][k]) * d[k];
+        if (!(dj > 0.0) || !isfinite(dj))
+            return false;
+        d[j] = dj;
+        for (int i = j + 1; i < 6; ++i) {
+            double v = A[i][j];
+            for (int k = 0; k < j; ++k)
+                v -= (Lm[i][k] * Lm[j][k]) * d[k];
+            Lm[i][j] = v / dj;
+        }
+    }
+    for (int i = 0; i < 6; ++i) {                      // L y = -b
+        double v = -s[23 + i];
+        for (int k = 0; k < i; ++k)
+            v -= Lm[i][k] * x[k];
+        x[i] = v;
+    }
+    for (int i = 0; i < 6; ++i)                        // D z = y
+        x[i] = x[i] / d[i];
+    for (int i = 5; i >= 0; --i) {                     // L^T x = z
+        double v = x[i];
+        for (int k = i + 1; k < 6; ++k)
+            v -= Lm[k][i] * x[k];
+        x[i] = v;
+    }
+    for (int i = 0; i < 6; ++i)
+        if (!isfinite(x[i]))
+            return false;
+    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
+    U[0] = cg * cb;
+    U[1] = (cg * sb) * sa - sg * ca;
+    U[2] = (cg * sb) * ca + sg * sa;
+    U[3] = x[3];
+    U[4] = sg * cb;
+    U[5] = (sg * sb) * sa + cg * ca;
+    U[6] = (sg * sb) * ca - cg * sa;
+    U[7] = x[4];
+    U[8] = -sb;
+    U[9] = cb * sa;
+    U[10] = cb * ca;
+    U[11] = x[5];
+    return true;
+}
+
+// T <- T^-1 for a rigid T (3x4): (R^T, -R^T t), the translation as -((R0i t0 + R1i t1) + R2i t2)
+__host__ __device__ inline void icp_invert(double *T)
+{
+    const double R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]}, t[3] = {T[3], T[7], T[11]};
+    for (int i = 0; i < 3; ++i) {
+        T[4 * i] = R[i];
+        T[4 * i + 1] = R[3 + i];
+        T[4 * i + 2] = R[6 + i];
+        T[4 * i + 3] = -((R[i] * t[0] + R[3 + i] * t[1]) + R[6 + i] * t[2]);
+    }
+}
+
 // T <- U T (both 3x4 with the implied last row 0 0 0 1): ((U_i0 T_0j + U_i1 T_1j) + U_i2 T_2j) + U_i3 T_3j
 __device__ inline void icp_compose(const double *U, double *T)
 {
@@ -337,24 +440,42 @@ __device__ inline void icp_compose(const double *U, double *T)
         T[k] = N[k];
 }
 
+// Thread 0: the estimator's update U from the sums; false = no update (U = I)
+template <bool PLANE>
+__device__ __forceinline__ bool icp_estimate(const double *sums, const double *ctr, double *U)
+{
+    if constexpr (PLANE) {
+        return icp_plane_update(sums, U);
+    } else {
+        icp_update(sums, ctr, U);
+        return true;
+    }
+}
+
+// PLANE: nrm [b,n,3] = the target points' normals; inverse != 0: rot / trans and the results are the target -> source
+// pose (inverted on entry and on exit).  Point to point takes nrm = nullptr, inverse = 0.
+template <bool PLANE>
 __global__ void __launch_bounds__(ICP_THREADS) ICP_NO_PACKED_FP32
-icp_p2p_kernel(int m, const float *__restrict__ src, int sps, long long scs, int n, const float *__restrict__ dst,
+icp_kernel(const double *__restrict__ nrm_all, int inverse, int m, const float *__restrict__ src, int sps, long long scs, int n, const float *__restrict__ dst,
                int dps, long long dcs, const float *__restrict__ rot, const float *__restrict__ trans, double radius,
                double decay, int rounds, int max_it, double rel_fit, double rel_rmse, int hbits,
                double *__restrict__ T_out, double *__restrict__ rot_out, float *__restrict__ trans_out,
                double *__restrict__ fit_out, double *__restrict__ rmse_out, int *__restrict__ it_out)
 {
     extern __shared__ double icp_lds[];
+    constexpr int NS = PLANE ? ICP_PLANE_SUMS : ICP_SUMS;
+    constexpr int D2 = PLANE ? 1 : 16;               // where the sums hold sum d^2
     const int H = 1 << hbits;
     IcpShared L;
     L.red = icp_lds;
-    L.bc = L.red + ICP_WAVES * ICP_SUMS;
+    L.bc = L.red + ICP_WAVES * NS;
     L.tgt = reinterpret_cast<float4 *>(L.bc + 64);
     L.start = reinterpret_cast<int *>(L.tgt + n);
     L.wsum = L.start + H + 1;
     const int tid = threadIdx.x, c = blockIdx.x;
     const float *S = src + (long long)c * scs;
     const float *D = dst + (long long)c * dcs;
+    const double *nrm = PLANE ? nrm_all + 3LL * (long long)c * n : nullptr;
     const double h = radius * (1.0 + 0x1p-20), inv_h = 1.0 / h;
     const unsigned mask = (unsigned)H - 1u;
 
@@ -410,6 +531,8 @@ icp_p2p_kernel(int m, const float *__restrict__ src, int sps, long long scs, int
             L.bc[4 * a + 2] = R[3 * a + 2];
             L.bc[4 * a + 3] = (double)trans[3 * c + a];
         }
+        if (PLANE && inverse)
+            icp_invert(L.bc);
     }
     __syncthreads();
 
@@ -430,16 +553,15 @@ icp_p2p_kernel(int m, const float *__restrict__ src, int sps, long long scs, int
                 icp_apply(L.bc, (double)x[0], (double)x[1], (double)x[2], P[k][0], P[k][1], P[k][2]);
             }
         }
-        icp_match(L, P, m, rho2, inv_h, reach, mask, ctr);
+        icp_match<PLANE>(L, P, m, rho2, inv_h, reach, mask, ctr, nrm);
         int its = 0;
         if (tid == 0) {
             fit = sums[0] / (double)m;
-            rmse = sums[0] > 0.0 ? sqrt(sums[16] / sums[0]) : 0.0;
+            rmse = sums[0] > 0.0 ? sqrt(sums[D2] / sums[0]) : 0.0;
             const bool cont = rounds > 0 && max_it > 0;
             L.bc[24] = cont ? 1.0 : 0.0;
             L.bc[25] = 0.0;
-            if (cont && sums[0] > 0.0) {
-                icp_update(sums, ctr, L.bc + 12);
+            if (cont && sums[0] > 0.0 && icp_estimate<PLANE>(sums, ctr, L.bc + 12)) {
                 icp_compose(L.bc + 12, L.bc);
                 L.bc[25] = 1.0;
             }
@@ -453,19 +575,18 @@ icp_p2p_kernel(int m, const float *__restrict__ src, int sps, long long scs, int
                 for (int k = 0; k < ICP_PER_LANE; ++k)
                     icp_apply(L.bc + 12, P[k][0], P[k][1], P[k][2], P[k][0], P[k][1], P[k][2]);
             }
-            icp_match(L, P, m, rho2, inv_h, reach, mask, ctr);
+            icp_match<PLANE>(L, P, m, rho2, inv_h, reach, mask, ctr, nrm);
             ++its;
             if (tid == 0) {
                 const double f = sums[0] / (double)m;
-                const double e = sums[0] > 0.0 ? sqrt(sums[16] / sums[0]) : 0.0;
+                const double e = sums[0] > 0.0 ? sqrt(sums[D2] / sums[0]) : 0.0;
                 const bool converged = fabs(fit - f) < rel_fit && fabs(rmse - e) < rel_rmse;
                 fit = f;
                 rmse = e;
                 const bool cont = !converged && its < max_it;
                 L.bc[24] = cont ? 1.0 : 0.0;
                 L.bc[25] = 0.0;
-                if (cont && sums[0] > 0.0) {
-                    icp_update(sums, ctr, L.bc + 12);
+                if (cont && sums[0] > 0.0 && icp_estimate<PLANE>(sums, ctr, L.bc + 12)) {
                     icp_compose(L.bc + 12, L.bc);
                     L.bc[25] = 1.0;
                 }
@@ -480,6 +601,8 @@ icp_p2p_kernel(int m, const float *__restrict__ src, int sps, long long scs, int
     if (tid == 0) {
         double *To = T_out + 16LL * c;
         double T[12];
+        if (PLANE && inverse)
+            icp_invert(L.bc);
 #pragma unroll
         for (int k = 0; k < 12; ++k)
             To[k] = T[k] = L.bc[k];
@@ -504,15 +627,17 @@ __global__ void ICP_NO_PACKED_FP32 f64_to_f32_kernel(long long n, const double *
 
 }  // namespace
 
-CLOUDAAE_API int cloudaae_icp_point_to_point(int b, int m, const float *src, int src_point_stride,
-                                             long long src_cloud_stride, int n, const float *dst, int dst_point_stride,
-                                             long long dst_cloud_stride, const float *rot_axag, const float *trans,
-                                             double radius, double decay, int rounds, int max_iteration,
-                                             double relative_fitness, double relative_rmse, double *transform,
-                                             double *rot_out, float *trans_out, double *fitness, double *rmse,
-                                             int *iterations, cloudaae_stream_t stream)
+namespace {
+
+// the argument checks and the launch shared by the two estimators
+template <bool PLANE>
+int icp_launch(const char *name, const double *tgt_normals, int inverse, int b, int m, const float *src,
+               int src_point_stride, long long src_cloud_stride, int n, const float *dst, int dst_point_stride,
+               long long dst_cloud_stride, const float *rot_axag, const float *trans, double radius, double decay,
+               int rounds, int max_iteration, double relative_fitness, double relative_rmse, double *transform,
+               double *rot_out, float *trans_out, double *fitness, double *rmse, int *iterations,
+               cloudaae_stream_t stream)
 {
-    const char *name = "cloudaae_icp_point_to_point";
     CLOUDAAE_REQUIRE(b >= 1 && m >= 1 && n >= 1, name, "b, m and n must be >= 1");
     CLOUDAAE_REQUIRE(m <= ICP_MAX_M, name, "m above the kernel's limit of 4096 source points per cloud");
     CLOUDAAE_REQUIRE(n <= ICP_MAX_N, name, "n above the kernel's limit of 4096 target points per cloud");
@@ -526,28 +651,61 @@ CLOUDAAE_API int cloudaae_icp_point_to_point(int b, int m, const float *src, int
                          (b == 1 || dst_cloud_stride >= (long long)(n - 1) * dst_point_stride + 3),
                      name, "cloud strides must not make clouds overlap");
     CLOUDAAE_REQUIRE(src && dst && rot_axag && trans && transform && rot_out && trans_out && fitness && rmse &&
-                         (iterations || rounds == 0),
+                         (iterations || rounds == 0) && (tgt_normals || !PLANE),
                      name, "null pointer");
+    constexpr int NS = PLANE ? ICP_PLANE_SUMS : ICP_SUMS;
     const int hbits = icp_hash_bits(n);
-    const size_t lds = icp_lds_bytes(n, hbits);
+    const size_t lds = icp_lds_bytes(n, hbits, NS);
     if (lds > 64 * 1024) {
-        static bool raised[64] = {};
+        static bool raised[64] = {};                       // one per instantiation
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
             dev = 0;
         if (!raised[dev]) {
-            CLOUDAAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&icp_p2p_kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)icp_lds_bytes(ICP_MAX_N, icp_hash_bits(ICP_MAX_N))),
+            CLOUDAAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&icp_kernel<PLANE>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)icp_lds_bytes(ICP_MAX_N, icp_hash_bits(ICP_MAX_N), NS)),
                                name);
             raised[dev] = true;
         }
     }
-    hipLaunchKernelGGL(icp_p2p_kernel, dim3(b), dim3(ICP_THREADS), lds, (hipStream_t)stream, m, src, src_point_stride,
-                       src_cloud_stride, n, dst, dst_point_stride, dst_cloud_stride, rot_axag, trans, radius, decay,
-                       rounds, max_iteration, relative_fitness, relative_rmse, hbits, transform, rot_out, trans_out,
-                       fitness, rmse, iterations);
+    hipLaunchKernelGGL(icp_kernel<PLANE>, dim3(b), dim3(ICP_THREADS), lds, (hipStream_t)stream, tgt_normals, inverse, m,
+                       src, src_point_stride, src_cloud_stride, n, dst, dst_point_stride, dst_cloud_stride, rot_axag,
+                       trans, radius, decay, rounds, max_iteration, relative_fitness, relative_rmse, hbits, transform,
+                       rot_out, trans_out, fitness, rmse, iterations);
     CLOUDAAE_CHECK_LAUNCH(name);
     return 0;
+}
+
+}  // namespace
+
+CLOUDAAE_API int cloudaae_icp_point_to_point(int b, int m, const float *src, int src_point_stride,
+                                             long long src_cloud_stride, int n, const float *dst, int dst_point_stride,
+                                             long long dst_cloud_stride, const float *rot_axag, const float *trans,
+                                             double radius, double decay, int rounds, int max_iteration,
+                                             double relative_fitness, double relative_rmse, double *transform,
+                                             double *rot_out, float *trans_out, double *fitness, double *rmse,
+                                             int *iterations, cloudaae_stream_t stream)
+{
+    return icp_launch<false>("cloudaae_icp_point_to_point", nullptr, 0, b, m, src, src_point_stride, src_cloud_stride, n,
+                             dst, dst_point_stride, dst_cloud_stride, rot_axag, trans, radius, decay, rounds,
+                             max_iteration, relative_fitness, relative_rmse, transform, rot_out, trans_out, fitness,
+                             rmse, iterations, stream);
+}
+
+CLOUDAAE_API int cloudaae_icp_point_to_plane(int b, int m, const float *src, int src_point_stride,
+                                             long long src_cloud_stride, int n, const float *dst, int dst_point_stride,
+                                             long long dst_cloud_stride, const double *tgt_normals,
+                                             int pose_maps_target_to_source, const float *rot_axag, const float *trans,
+                                             double radius, double decay, int rounds, int max_iteration,
+                                             double relative_fitness, double relative_rmse, double *transform,
+                                             double *rot_out, float *trans_out, double *fitness, double *rmse,
+                                             int *iterations, cloudaae_stream_t stream)
+{
+    return icp_launch<true>("cloudaae_icp_point_to_plane", tgt_normals, pose_maps_target_to_source ? 1 : 0, b, m, src,
+                            src_point_stride, src_cloud_stride, n, dst, dst_point_stride, dst_cloud_stride, rot_axag,
+                            trans, radius, decay, rounds, max_iteration, relative_fitness, relative_rmse, transform,
+                            rot_out, trans_out, fitness, rmse, iterations, stream);
 }
 
 CLOUDAAE_API int cloudaae_f64_to_f32(long long n, const double *x, float *y, cloudaae_stream_t stream)

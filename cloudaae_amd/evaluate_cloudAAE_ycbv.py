@@ -33,6 +33,7 @@ from .tf_ops.sampling import tf_sampling
 from .train_cloudAAE_ycbv import NUM_CLASS
 from .utils import _functions as F
 from .utils import icp as icp_util
+from .utils import normals as normals_util
 from .utils import pose_score as score_util
 from .utils import segment as seg_util
 
@@ -49,6 +50,11 @@ def evaluate_batch(graph, element, replay=False, icp=None, score=None):
     model) and adds rot_icp, trans_icp, transformation_icp, fitness_icp, inlier_rmse_icp, iterations_icp and the
     errors of the refined pose, trans_loss_icp / axag_loss_icp with their per-sample values.  The other outputs
     are those of icp=None.
+    icp={'estimation': 'point_to_plane', ...}: point-to-plane ICP of the network's N input points (source) onto the
+    object model (target) along the model's normals: element['obj_normals'] [B,M,3] float64 when present, otherwise
+    utils.normals.estimate_normals(obj_batch, radius=normal_radius) (a key of the dict, default 0.015 m).  The
+    outputs keep their names and are model -> camera poses as before; fitness_icp and inlier_rmse_icp are then those
+    of the scene points (the share of the N input points with a model point within the radius), not of the model's.
     score=True: the predicted pose [rot_pred | trans_pred] and, with icp, the refined one (transformation_icp) are
     scored against [axisangle | translation] on element['obj_batch'] by one cloudaae_pose_score launch: adds add_pred,
     adds_pred and, with icp, add_icp, adds_icp [B] float64 (ADD and ADD-S in metres).  The other outputs are those of
@@ -58,6 +64,9 @@ def evaluate_batch(graph, element, replay=False, icp=None, score=None):
     if replay:
         return _replayed(graph, element, icp, score)
     return _evaluate(graph, element, icp, score)
+
+
+NORMAL_RADIUS = 0.015     # neighbourhood of the class models' normals, metres (profiles/notes_icp_plane.md)
 
 
 def _icp_params(icp):
@@ -78,6 +87,8 @@ def _replayed(graph, element, icp=None, score=False):
     if icp is not None or score:
         require(element.get('obj_batch') is not None, "icp and score need element['obj_batch'] [B, M, >=3]")
         src['obj_batch'] = (element['obj_batch'], torch.float32)
+    if icp is not None and icp.get('estimation') == 'point_to_plane' and element.get('obj_normals') is not None:
+        src['obj_normals'] = (element['obj_normals'], torch.float64)
     key = tuple((k, tuple(v.shape)) for k, (v, _) in src.items())
     if icp is not None:
         key += (('icp', tuple(sorted(icp.items()))),)
@@ -171,7 +182,18 @@ def _refine(element, scene, rot_pred, trans_pred, translation, params):
     require(obj.dim() == 3 and obj.shape[0] == scene.shape[0] and obj.shape[2] >= 3 and obj.dtype == torch.float32,
             "obj_batch must be a float32 [B, M, >=3] tensor")
     with torch.no_grad():
-        r = icp_util.refine_pose_icp(obj, scene, rot_pred.contiguous(), trans_pred.contiguous(), **params)
+        if params.get('estimation', 'point_to_point') == 'point_to_plane':
+            # scene -> model along the model's normals; the poses given and returned stay model -> camera
+            params = dict(params)
+            normal_radius = params.pop('normal_radius', NORMAL_RADIUS)
+            params.pop('pose_maps_target_to_source', None)
+            normals = element.get('obj_normals')
+            if normals is None:
+                normals = normals_util.estimate_normals(obj, radius=normal_radius)[0]
+            r = icp_util.refine_pose_icp(scene, obj, rot_pred.contiguous(), trans_pred.contiguous(), normals=normals,
+                                         pose_maps_target_to_source=True, **params)
+        else:
+            r = icp_util.refine_pose_icp(obj, scene, rot_pred.contiguous(), trans_pred.contiguous(), **params)
         trans_loss, trans_per = trans_distance.get_translation_error(r['trans'], translation)
         # the rotation error kernel takes an fp32 prediction, as for the network's output
         axag_loss, axag_per = angular_distance_taylor.get_rotation_error(icp_util.to_float32(r['rot_axag']),
@@ -246,7 +268,8 @@ def main(argv=None):
     Reads <data_dir>/<seq>_pcnn.tfrecord of the class's test sequences (:43-63) file after file, in record order (the
     reference interleaves them at random with sample_from_datasets), and prints the per-batch and the final loss
     lines (:568, :652-657).  A last batch smaller than --batch_size is not evaluated (the reference's reshape to
-    BATCH_SIZE, :338, cannot take it).  --icp adds the refined pose's losses.  --score prints, after the final line,
+    BATCH_SIZE, :338, cannot take it).  --icp adds the refined pose's losses; --icp_plane refines by point-to-plane ICP
+    on the class models' normals instead (computed once, before the loop).  --score prints, after the final line,
     the ADD / ADD-S summary of the predicted (and refined) poses per class and over all (PoseScoreLog.lines)."""
     from . import tfrecord_io
     from . import train_cloudAAE_ycbv as T
@@ -259,11 +282,14 @@ def main(argv=None):
     p.add_argument("--num_point", type=int, default=256)
     p.add_argument("--batch_size", type=int, default=1)
     p.add_argument("--icp", action="store_true")
+    p.add_argument("--icp_plane", action="store_true",
+                   help="refine by point-to-plane ICP on the class models' normals (implies --icp)")
     p.add_argument("--score", action="store_true", help="ADD / ADD-S, AUC and accuracy summary of the scored poses")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--frames_per_launch", type=int, default=8)
     p.add_argument("--gpu", type=int, default=0)
     args = p.parse_args(argv)
+    args.icp = args.icp or args.icp_plane
     torch.cuda.set_device(args.gpu)
     obj_path = args.object_model or os.path.join(os.path.dirname(os.path.abspath(args.data_dir)),
                                                  "object_model_tfrecord", "obj_models.tfrecords")
@@ -274,6 +300,12 @@ def main(argv=None):
     files = [f for f in files if os.path.exists(f)]
     require(files, "no <seq>_pcnn.tfrecord of class %d under %s" % (args.target_cls, args.data_dir))
     pending, batch_idx, tot_trans, tot_axag, n_launch = None, 0, 0.0, 0.0, 0
+    icp, model_normals = args.icp, None
+    if args.icp_plane:
+        icp = {'estimation': 'point_to_plane'}
+        # the normals of the 21 class models, once; a batch selects its classes' rows
+        model_normals = normals_util.estimate_normals(
+            torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda(), radius=NORMAL_RADIUS)[0]
     log = None
     if args.score:
         diam = score_util.model_diameter(torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda())
@@ -300,8 +332,10 @@ def main(argv=None):
         while len(pending["class_id"]) >= args.batch_size:
             b = _take(pending, 0, args.batch_size)
             pending = _take(pending, args.batch_size, len(pending["class_id"]))
-            out = evaluate_batch(graph, {k: v for k, v in b.items() if isinstance(v, torch.Tensor)}, icp=args.icp,
-                                 score=args.score)
+            el_b = {k: v for k, v in b.items() if isinstance(v, torch.Tensor)}
+            if model_normals is not None:
+                el_b['obj_normals'] = model_normals.index_select(0, el_b['class_id'])
+            out = evaluate_batch(graph, el_b, icp=icp, score=args.score)
             if log is not None:
                 log.append(b["class_id"], torch.stack([out["add_" + n] for n in log.poses], dim=1),
                            torch.stack([out["adds_" + n] for n in log.poses], dim=1), seq=b["seq_id"], frame=b["frame_id"])

@@ -49,7 +49,8 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * under 602 (additions only, no existing argument list or layout changed): cloudaae_frame_segments,
  * cloudaae_radius_outlier, cloudaae_ragged_fps and their workspace queries; cloudaae_dev_gemm_folded (development /
  * test entry); cloudaae_bn_backward_dx_bf16x3 and its two queries; cloudaae_pose_score, cloudaae_cloud_diameter (each with
- * a workspace query), cloudaae_pose_matrix and cloudaae_pose_stack. */
+ * a workspace query), cloudaae_pose_matrix and cloudaae_pose_stack; cloudaae_icp_point_to_plane and
+ * cloudaae_estimate_normals with its workspace query. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -744,8 +745,47 @@ int cloudaae_icp_point_to_point(int b, int m, const float *src, int src_point_st
                                 int max_iteration, double relative_fitness, double relative_rmse,
                                 double *transform, double *rot_out, float *trans_out, double *fitness,
                                 double *rmse, int *iterations, cloudaae_stream_t stream);
+/* The same schedule, matching, tie rule, statistics (fitness, Euclidean inlier rmse), stopping rule and outputs with
+ * the point-to-plane update ("Pose refinement", has the definition): with p the transformed source point, q
+ * its target point and n = tgt_normals[c, j] that point's normal, r = (p - q) . n, J = [p x n; n], A = sum J J^T,
+ * b = sum J r, A x = -b by LDL^T in float64, x = (alpha, beta, gamma, t), U = [Rz(gamma) Ry(beta) Rx(alpha) | t].  Fewer
+ * than six correspondences, a pivot that is not a finite number > 0 or a solution that is not finite leave the pose as
+ * it is.  tgt_normals [b,n,3] float64, packed, one per target point (their sign does not matter).
+ * pose_maps_target_to_source != 0: rot_axag / trans and every returned pose (transform, rot_out, trans_out) are the
+ * target -> source pose: the kernel inverts the initial pose on entry (R^T, -R^T t) and the result on exit, so a caller
+ * holding model -> camera poses can run the iteration scene -> model (src = the scene, dst = the model with its
+ * normals).  fitness and rmse are always those of the src points.  Limits as above. */
+int cloudaae_icp_point_to_plane(int b, int m, const float *src, int src_point_stride, long long src_cloud_stride,
+                                int n, const float *dst, int dst_point_stride, long long dst_cloud_stride,
+                                const double *tgt_normals, int pose_maps_target_to_source, const float *rot_axag,
+                                const float *trans, double radius, double decay, int rounds, int max_iteration,
+                                double relative_fitness, double relative_rmse, double *transform, double *rot_out,
+                                float *trans_out, double *fitness, double *rmse, int *iterations,
+                                cloudaae_stream_t stream);
 /* y[i] = (float)x[i], round to nearest even (an f64 result handed to an fp32 consumer, e.g. a loss kernel). */
 int cloudaae_f64_to_f32(long long n, const double *x, float *y, cloudaae_stream_t stream);
+
+/* ---- surface normals ("Surface normals", has the definition) ---- */
+
+/* Normals of k query points per set from the covariance of their radius neighbourhood in the set's support points.
+ *   support: s packed sets, set i = the points offsets[i] .. offsets[i+1] (offsets [s+1] int, device) of xyz, point j
+ *   at xyz + j*xyz_point_stride (floats, >= 3: obj_batch [b,2048,6] goes in unsliced), max_points points in all;
+ *   queries: k per set, query i of set c at queries + c*query_set_stride + i*query_point_stride (may be the support).
+ * Neighbours of a query: the support points of its set with ((dx^2 + dy^2) + dz^2) < r^2 in double on the widened
+ * coordinates, r = (double)radius.  count [s,k] = their number.  count < min_neighbors: normal (0, 0, 1), eigenvalues
+ * 0.  Otherwise the covariance about the neighbours' mean (two passes, float64, divided by count), its eigenvalues in
+ * ascending order -> eigenvalues [s,k,3] and the unit eigenvector of the smallest -> normals [s,k,3] (cyclic Jacobi).
+ * viewpoint (HOST pointer to three doubles, read during the call; NULL = none): an estimated normal is flipped when
+ * n . (q - v) > 0; without one its sign is the solver's.  Two launches, no floating-point atomics; a set's result does
+ * not depend on s and is bit-reproducible.  workspace: cloudaae_estimate_normals_workspace_bytes(s, max_points) bytes
+ * (-1 for a bad argument).  Limits: 1 <= s <= 65535, k >= 1, s*k <= 2^30, 1 <= max_points <= 2^28, radius > 0,
+ * min_neighbors >= 3. */
+long long cloudaae_estimate_normals_workspace_bytes(int s, long long max_points);
+int cloudaae_estimate_normals(int s, const int *offsets, const float *xyz, int xyz_point_stride, long long max_points,
+                              int k, const float *queries, int query_point_stride, long long query_set_stride,
+                              float radius, int min_neighbors, const double *viewpoint, double *normals,
+                              double *eigenvalues, int *count, void *workspace, long long workspace_bytes,
+                              cloudaae_stream_t stream);
 
 /* ---- pose scores: ADD, ADD-S, model diameter ("Pose scores", has the definition) ---- */
 
