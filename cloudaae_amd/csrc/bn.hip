@@ -365,7 +365,8 @@ __global__ __launch_bounds__(BN_FIN_THREADS) void colsum_finalize_kernel(int C, 
     bn_reduce_partials(partial, parts, C, c, pl, s, s2);
     if (c >= C || pl != 0)
         return;
-    out[c] = (accumulate ? out[c] : 0.0f) + (float)s;
+    // one rounding: added in fp64 (rounding the sum first, then the fp32 addition, could end 1.5 ulp from the exact value)
+    out[c] = (float)((accumulate ? (double)out[c] : 0.0) + s);
 }
 
 // ---- small batches (the FC layers: M = batch per GPU) -----------------------------------------
