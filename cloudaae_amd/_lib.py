@@ -112,6 +112,9 @@ _SIGNATURES = {
     "cloudaae_increment": [_P, _F, _P],
     "cloudaae_transform_object_model": [_I, _I, _I, _P, _P, _P, _P, _P, _P],
     "cloudaae_random_spherical_occluder": [_I, _I, _P, _F, _F, _F, _F, _U, _P, _P],
+    "cloudaae_sample_poses": [_I, _U, _U, _I, _P, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P,
+                              _P, _P],
+    "cloudaae_random_object_occluder": [_I, _U, _U, _I, _I, _P, _I, _P, _P, _P, _I, _F, _F, _F, _P, _P, _P, _P],
     "cloudaae_spherical_flip": [_I, _I, _P, _I, _P, _P, _F, _P, _P, _P],
     "cloudaae_hidden_point_removal": [_I, _I, _P, _P, _U, _P, _P, _P, _P, _P],
     "cloudaae_hidden_point_removal_rows": [_I, _I, _P, _P, _U, _I, _P, _P, _P, _P, _P, _P],

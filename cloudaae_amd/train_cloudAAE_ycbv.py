@@ -75,6 +75,17 @@ def get_training_argparser():
                             "3 x bfloat16 split products on the bf16 matrix cores (fp32 accuracy); f32 = those products on the fp32 "
                             "matrix cores too; bf16 = bf16 operands for the dense layers (BASELINE configs[2])")
     extra.add_argument('--print_every', type=int, default=1, help='print the losses every n batches (each print syncs)')
+    extra.add_argument('--poses', default='records', choices=['records', 'sampled'],
+                       help="records: the pose records of --data_dir (train_syn); sampled: poses drawn on the GPU "
+                            "(utils/sample_pose_in_frustum.py), which needs object models only")
+    extra.add_argument('--occluder', default='spherical', choices=['spherical', 'object'],
+                       help="the two Gaussian blobs, or 512 points of a rotated object model (utils/generate_occluder.py)")
+    extra.add_argument('--dataset', default='ycbv', choices=['ycbv', 'linemod'], help='camera and frustum constants')
+    extra.add_argument('--epoch_size', type=int, default=381553,
+                       help='samples per epoch with --poses sampled [default: the shipped train_syn set]')
+    extra.add_argument('--classes', default='', help='comma-separated class ids to train on [default: all]')
+    extra.add_argument('--pose_seed', type=int, default=123456789, help='seed of the sampled poses')
+    extra.add_argument('--deterministic', action='store_true', help='bit-reproducible steps (TrainGraph(deterministic=True))')
     return parser
 
 
@@ -550,20 +561,33 @@ def transform_object_model(x):
     return x
 
 
-def get_small_data(records, obj_models, seed=0, rows=None, rows_org=None):
+def get_small_data(records, obj_models, seed=0, rows=None, rows_org=None, occluder='spherical', dataset='ycbv',
+                   first_index=0, occluder_seed=None):
     """:96-117 for one batch: records = dict of device tensors translation [B,3], axisangle [B,3],
     class_id [B] (e.g. from tfrecord_io.PoseRecords.epoch); returns the reference's element dict:
     visiblePoints [B,2449,3], visiblePoints_org [B,2049,3], occluder, model_xyz_rot_trans, ...
     rows / rows_org: other row counts of visiblePoints / visiblePoints_org (default: the reference's model points
     [+ occluder points] + 1), filled by the reference's rule -- visible points, then random re-draws of visible
     points (hidden_point_removal.py:38-40).  BASELINE configs[4] (N = 4096) needs a Chamfer target of 4N = 16384 rows,
-    more than any model has points."""
+    more than any model has points.
+    occluder: 'spherical' (two Gaussian blobs, 400 points) or 'object' (512 points of a class model rotated by the sample's
+    rotation, generate_occluder.py:5-35: visiblePoints then has 2048 + 512 + 1 rows); dataset: the camera constants of
+    either.  The object occluder of sample i is a function of (occluder_seed, first_index + i) -- occluder_seed defaults
+    to `seed`.  The defaults give what this function gave before it had these arguments, bit for bit."""
     from .utils import generate_occluder, hidden_point_removal as hpr
+    require(occluder in ('spherical', 'object'), "occluder must be 'spherical' or 'object'")
     x = dict(records)
     x = get_object_model(x, obj_models)
-    x = get_rotation_matrix(x)
+    if x.get('rot_mat64') is None:
+        x = get_rotation_matrix(x)
+    else:                                 # sampled poses bring the exponential map of their axis-angle along
+        x['rot_mat'] = x['rot_gen_mat'] if x.get('rot_gen_mat') is not None else x['rot_mat64'].to(torch.float32)
     x = transform_object_model(x)
-    x = generate_occluder.get_random_spherical_occluder(x, 'ycbv', seed=seed)
+    if occluder == 'object':
+        x = generate_occluder.get_random_object_occluder(x, obj_models.shape[0], dataset=dataset, first_index=first_index,
+                                                         seed=seed if occluder_seed is None else occluder_seed)
+    else:
+        x = generate_occluder.get_random_spherical_occluder(x, dataset, seed=seed)
     x = hpr.sphericalFlip(x, None, 0.8 * math.pi)            # center = zeros_like(translation), :103
     x = hpr.hidden_point_removal(x, seed=seed, rows=rows)
     x = hpr.sphericalFlip_org(x, None, 0.8 * math.pi)
@@ -611,6 +635,40 @@ def synthetic_object_models(num_models=NUM_CLASS, num_point=2048, seed=123456789
     return out if device is None else out.to(device)
 
 
+class SampledPoses(object):
+    """The stand-in for tfrecord_io.PoseRecords when poses are drawn instead of read: `epoch()` yields device dicts from
+    utils.sample_pose_in_frustum.sample_poses.  Sample i of this rank's batch of step s is global sample
+    g = s * global_batch + rank * local_batch + i (s counts from the first epoch on): every rank draws its own index
+    range, nothing is sharded, and a run of other batch or world size meets the same samples at the same g."""
+
+    def __init__(self, epoch_size, global_batch, rank=0, world=1, seed=123456789, classes=None, dataset='ycbv',
+                 camera=None, device=None, num_models=NUM_CLASS):
+        require(global_batch % world == 0, "global batch must divide by the number of ranks")
+        self.epoch_size, self.global_batch, self.rank, self.world = int(epoch_size), int(global_batch), int(rank), int(world)
+        self.local_batch = self.global_batch // self.world
+        self.seed, self.classes, self.dataset, self.camera = int(seed), classes, dataset, camera
+        self.device, self.num_models = device, int(num_models)
+
+    def __len__(self):                     # samples this rank sees per epoch
+        return self.steps_per_epoch() * self.local_batch
+
+    def steps_per_epoch(self):
+        return self.epoch_size // self.global_batch
+
+    def first_index(self, epoch, batch_idx):
+        return (epoch * self.steps_per_epoch() + batch_idx) * self.global_batch + self.rank * self.local_batch
+
+    def epoch(self, batch_size, epoch=0):
+        from .utils import sample_pose_in_frustum as spf
+        require(batch_size == self.local_batch, "SampledPoses was built for another local batch")
+        for batch_idx in range(self.steps_per_epoch()):
+            g0 = self.first_index(epoch, batch_idx)
+            rec = spf.sample_poses(batch_size, self.seed, g0, classes=self.classes, dataset=self.dataset,
+                                   camera=self.camera, device=self.device, num_models=self.num_models)
+            rec['first_index'] = g0
+            yield rec
+
+
 class ClassLossLog(object):
     """The per-class running averages of :318-321 / :397-414 (what the reference sends to
     TensorBoard every 1000 batches), accumulated on the device so the loop never syncs."""
@@ -640,20 +698,28 @@ class ClassLossLog(object):
 
 
 def train_graph(graph, records, obj_models, epoch, class_log=None, log=None, logdir=None, seed=None,
-                max_batches=None, print_every=1, summary_every=1000):
+                max_batches=None, print_every=1, summary_every=1000, occluder='spherical', dataset='ycbv'):
     """One epoch of the reference's train_graph (:332-437): draw shuffled batches of pose records,
     synthesise the element on the GPU (get_small_data), train_step, per-class loss bookkeeping
     every `summary_every` batches, checkpoint at the end of the epoch (:418-424).
-    `records` is this rank's tfrecord_io.PoseRecords shard; obj_models the [21,2048,6] device tensor."""
+    `records` is this rank's tfrecord_io.PoseRecords shard, or a SampledPoses (poses drawn on the GPU: nothing is read
+    on the host or copied); obj_models the [21,2048,6] device tensor."""
     start = time.time()
     dev = graph.device
     batch_idx = 0
     out = None
-    for rec in records.epoch(graph.local_batch, seed=seed):
+    sampled = isinstance(records, SampledPoses)
+    batches = records.epoch(graph.local_batch, epoch) if sampled else records.epoch(graph.local_batch, seed=seed)
+    for rec in batches:
         if max_batches is not None and batch_idx >= max_batches:
             break
-        element = get_small_data({k: torch.as_tensor(v).to(dev, non_blocking=True) for k, v in rec.items()},
-                                 obj_models, seed=(epoch << 32) + batch_idx * graph.world + graph.rank)
+        batch_seed = (epoch << 32) + batch_idx * graph.world + graph.rank
+        if sampled:
+            element = get_small_data(rec, obj_models, seed=batch_seed, occluder=occluder, dataset=dataset,
+                                     first_index=rec['first_index'], occluder_seed=records.seed)
+        else:
+            element = get_small_data({k: torch.as_tensor(v).to(dev, non_blocking=True) for k, v in rec.items()},
+                                     obj_models, seed=batch_seed, occluder=occluder, dataset=dataset)
         out = graph.train_step(element)
         if class_log is not None:
             class_log.add(out)
@@ -676,6 +742,13 @@ def train_graph(graph, records, obj_models, epoch, class_log=None, log=None, log
     if log is not None:
         log('Current epoch Time elapsed %.1f s (%d batches)' % (time.time() - start, batch_idx))
     return batch_idx, out
+
+
+def load_object_models(data_dir, device):
+    """object_model_tfrecord/obj_models.tfrecords under `data_dir` -> device tensor [21,2048,6]."""
+    from . import tfrecord_io
+    models, _ = tfrecord_io.read_and_decode_obj_model(os.path.join(data_dir, "object_model_tfrecord", "obj_models.tfrecords"))
+    return torch.as_tensor(models).to(device)
 
 
 def load_dataset(data_dir, device, rank=0, world=1, classes=None):
@@ -701,10 +774,12 @@ def main(argv=None):
         dist.init_process_group('nccl')
         general['gpu'] = local
     graph = TrainGraph(general, topts, hyper, model_fn=extra['model_fn'], k_neighbor=extra['k'], replay=True,
-                       gemm_dtype=extra['gemm_dtype'])
+                       gemm_dtype=extra['gemm_dtype'], deterministic=bool(extra.get('deterministic')))
     if extra['restore']:
         graph.restore(extra['restore'])
-    if extra['data_dir']:
+    classes = [int(c) for c in extra['classes'].split(',') if c != ''] or None
+    sampled = extra['poses'] == 'sampled'
+    if extra['data_dir'] or sampled:
         # the reference's run: LOG_DIR/<NUM_CLASS>/6d/<timestamp>/log_train.txt (:150-157)
         logdir = os.path.join(general['log_dir'], str(NUM_CLASS), "6d", time.strftime("%Y%m%d-%H%M%S"))
         fout = None
@@ -719,13 +794,23 @@ def main(argv=None):
                 fout.write(msg + '\n')
                 fout.flush()
                 print(msg)
-        obj_models, records = load_dataset(extra['data_dir'], graph.device, graph.rank, graph.world)
+        if sampled:
+            # poses drawn on the GPU: only the object models are read (or made up, without --data_dir); every rank draws
+            # its own range of global sample indices
+            obj_models = load_object_models(extra['data_dir'], graph.device) if extra['data_dir'] \
+                else synthetic_object_models(device=graph.device)
+            records = SampledPoses(extra['epoch_size'], graph.BATCH_SIZE, graph.rank, graph.world, seed=extra['pose_seed'],
+                                   classes=classes, dataset=extra['dataset'], device=graph.device,
+                                   num_models=obj_models.shape[0])
+        else:
+            obj_models, records = load_dataset(extra['data_dir'], graph.device, graph.rank, graph.world, classes=classes)
         log("%d pose records on rank 0, %d batches per epoch" % (len(records), len(records) // graph.local_batch))
         class_log = ClassLossLog(graph.device)
         for epoch in range(int(topts['max_epoch'])):
             log('**** EPOCH %03d ****' % epoch)
             train_graph(graph, records, obj_models, epoch, class_log, log, logdir, seed=123456789 + epoch,
-                        max_batches=extra['steps'] or None, print_every=extra['print_every'])
+                        max_batches=extra['steps'] or None, print_every=extra['print_every'],
+                        occluder=extra['occluder'], dataset=extra['dataset'])
         return
     el = synthetic_element(graph.local_batch, graph.NUM_POINT, graph.device, rank=graph.rank)
     t0 = time.time()

@@ -50,7 +50,7 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * cloudaae_radius_outlier, cloudaae_ragged_fps and their workspace queries; cloudaae_dev_gemm_folded (development /
  * test entry); cloudaae_bn_backward_dx_bf16x3 and its two queries; cloudaae_pose_score, cloudaae_cloud_diameter (each with
  * a workspace query), cloudaae_pose_matrix and cloudaae_pose_stack; cloudaae_icp_point_to_plane and
- * cloudaae_estimate_normals with its workspace query. */
+ * cloudaae_estimate_normals with its workspace query; cloudaae_sample_poses and cloudaae_random_object_occluder. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -693,6 +693,32 @@ int cloudaae_transform_object_model(int b, int npts, int nmodels, const float *m
 int cloudaae_random_spherical_occluder(int b, int per_blob, const float *trans, float wnear, float hnear,
                                        float near_dist, float sigma, unsigned long long seed, float *occluder,
                                        cloudaae_stream_t stream);
+/* Training poses drawn on the device (utils/sample_pose_in_frustum.py:8-153; DESIGN.md, "Pose sampling", has the
+ * definition).  Sample i of the call is global sample g = first_index + i; every draw is a function of (seed, g, Philox
+ * stream id) alone, so a sample does not depend on b, on the number of ranks or on the launch.
+ *   classes [n_classes] int, HOST memory (read before the launch, passed by value): the class ids to draw from, each in
+ *   [0, nmodels); NULL with n_classes = 0: every model.  At most 128 entries.
+ *   wnear, wfar: the frustum widths of get_frustum; near_dist, far_dist; fx, fy, cx, cy, width, height: the camera.
+ * Outputs (device): class_id [b] int64; axisangle [b,3] f64 (the fp32 axis * angle, widened); rot_mat64 [b,3,3] f64 =
+ * cloudaae_exponential_map of it (the same bits); rot_mat32 [b,3,3] f32 = its rounding (optional); translation [b,3] f32: the draw when it projects strictly inside the
+ * image, else the frustum middle (0, 0, (far+near)/2); in_fov [b] uint8: which of the two.  Optional (NULL to skip):
+ * drawn [b,5] f32 = the draw before replacement and its pixel (x, y, z, u, v); raw [b,8] uint32 = the Philox words of
+ * the pose and the translation stream.  One launch, no read-back; every argument is validated before any HIP call. */
+int cloudaae_sample_poses(int b, unsigned long long first_index, unsigned long long seed, int n_classes,
+                          const int *classes, int nmodels, float wnear, float wfar, float near_dist, float far_dist,
+                          float fx, float fy, float cx, float cy, float width, float height, long long *class_id,
+                          double *axisangle, double *rot_mat64, float *rot_mat32, float *translation,
+                          unsigned char *in_fov, float *drawn, unsigned *raw, cloudaae_stream_t stream);
+/* get_random_object_occluder (utils/generate_occluder.py:5-35): occluder [b,per,3] = the first `per` points of a class
+ * model (models [nmodels,npts,6]) rotated by float32(rot_mat64[b]) -- the dot product of cloudaae_transform_object_model
+ * -- plus a centre ~ N(0,wnear/8), N(0,hnear/8), N((near+z)/2,(z-near)/6), z = translation[:,2].  The class is drawn
+ * PER SAMPLE from `classes` (HOST memory, as above; the reference draws one per process).  first_index and seed as
+ * above, with stream ids of its own.  Optional: occ_class [b] int64, raw [b,8] uint32 (centre and class streams).
+ * Every argument is validated before any HIP call; per <= npts. */
+int cloudaae_random_object_occluder(int b, unsigned long long first_index, unsigned long long seed, int nmodels, int npts,
+                                    const float *models, int n_classes, const int *classes, const double *rot_mat64,
+                                    const float *translation, int per, float wnear, float hnear, float near_dist,
+                                    float *occluder, long long *occ_class, unsigned *raw, cloudaae_stream_t stream);
 /* sphericalFlip (utils/hidden_point_removal.py:6-24, 51-68): points = concat(a[b,na,3], bpts[b,nb,3])
  * - center; flipped = 2 (R - |p|) p / |p| + p, R = max|p| * 10^param; both outputs are
  * [b, na+nb+1, 3] with a zero last row (the viewpoint).  bpts may be NULL with nb = 0. */

@@ -9,7 +9,7 @@ mkdir -p "$(dirname "$LOG")"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 fail=0
 for f in tests/test_*_gpu.py; do
-  lim=420; case $f in *test_03*) lim=600;; esac
+  lim=420; case $f in *test_03*) lim=600;; *test_21*) lim=600;; esac   # (test_21: five training runs in child processes of at most 100 s each)
   echo "== $f" >> "$LOG"
   timeout $lim python -m pytest "$f" -q -m gpu --durations=3 >> "$LOG" 2>&1
   rc=$?
