@@ -131,6 +131,9 @@ _SIGNATURES = {
     "cloudaae_frame_segments": [_I, _I, _I, _P, _P, _P, _I, _P, _P, _F, _P, _P, _P, _P, _L, _P],
     "cloudaae_radius_outlier": [_I, _P, _P, _L, _I, _F, _I, _P, _P, _P, _P, _P, _L, _P],
     "cloudaae_ragged_fps": [_I, _P, _P, _L, _I, _P, _P, _P, _P, _L, _P],
+    "cloudaae_mesh_weights": [_I, _P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _L, _P],
+    "cloudaae_mesh_sample": [_I, _P, _P, _L, _L, _P, _P, _P, _P, _P, _I, _U, _U, _P, _P, _P, _P],
+    "cloudaae_mesh_gather_rows": [_I, _I, _P, _L, _P, _L, _I, _I, _P, _L, _P],
 }
 
 
@@ -347,6 +350,7 @@ def lib():
         for q, sig in (("cloudaae_frame_segments_workspace_bytes", [_I, _I, _I, _I]),
                        ("cloudaae_radius_outlier_workspace_bytes", [_I, _L]),
                        ("cloudaae_ragged_fps_workspace_bytes", [_L]),
+                       ("cloudaae_mesh_weights_workspace_bytes", [_L]),
                        ("cloudaae_pose_score_workspace_bytes", [_I, _I, _I]),
                        ("cloudaae_estimate_normals_workspace_bytes", [_I, _L]),
                        ("cloudaae_cloud_diameter_workspace_bytes", [_I, _I])):

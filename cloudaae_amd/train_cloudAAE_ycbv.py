@@ -86,6 +86,10 @@ def get_training_argparser():
     extra.add_argument('--classes', default='', help='comma-separated class ids to train on [default: all]')
     extra.add_argument('--pose_seed', type=int, default=123456789, help='seed of the sampled poses')
     extra.add_argument('--deterministic', action='store_true', help='bit-reproducible steps (TrainGraph(deterministic=True))')
+    extra.add_argument('--meshes', default='', help='directory of *.ply meshes to build the object models from on the GPU '
+                       '(utils/mesh_models.py; class i is the i-th file in sorted order); with --poses sampled only')
+    extra.add_argument('--mesh_scale', type=float, default=1.0,
+                       help='factor on the mesh coordinates (0.001 for meshes in millimetres)')
     return parser
 
 
@@ -767,6 +771,8 @@ def main(argv=None):
     parser = get_training_argparser()
     groups = parse_arg_groups(parser, argv)
     general, topts, hyper, extra = groups['general'], groups['training_options'], groups['hyperparameters'], groups['mi355x']
+    if extra['meshes'] and extra['poses'] != 'sampled':
+        parser.error("--meshes needs --poses sampled (pose records belong to the shipped object models)")
     world = int(os.environ.get('WORLD_SIZE', '1'))
     if world > 1:
         local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -797,8 +803,15 @@ def main(argv=None):
         if sampled:
             # poses drawn on the GPU: only the object models are read (or made up, without --data_dir); every rank draws
             # its own range of global sample indices
-            obj_models = load_object_models(extra['data_dir'], graph.device) if extra['data_dir'] \
-                else synthetic_object_models(device=graph.device)
+            if extra['meshes']:
+                # the models come from the meshes (every rank builds the same ones: a function of the seed and the
+                # file's position), and there are as many classes as files
+                from .utils import mesh_models
+                obj_models = mesh_models.models_from_meshes(mesh_models.mesh_files(extra['meshes']),
+                                                            scale=extra['mesh_scale'], device=graph.device)
+            else:
+                obj_models = load_object_models(extra['data_dir'], graph.device) if extra['data_dir'] \
+                    else synthetic_object_models(device=graph.device)
             records = SampledPoses(extra['epoch_size'], graph.BATCH_SIZE, graph.rank, graph.world, seed=extra['pose_seed'],
                                    classes=classes, dataset=extra['dataset'], device=graph.device,
                                    num_models=obj_models.shape[0])

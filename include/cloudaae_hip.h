@@ -883,6 +883,48 @@ int cloudaae_ragged_fps(int s, const int *offsets, const float *xyz, long long m
                         int *idx, float *out_xyz, void *workspace, long long workspace_bytes,
                         cloudaae_stream_t stream);
 
+/* ---- object models from triangle meshes ("Mesh sampling", has the definition) ---- */
+
+/* s packed meshes: mesh i owns the vertices vert_offsets[i] .. vert_offsets[i+1] of vertices [num_vertices,3] f32 (and
+ * of colors, where given) and the triangles tri_offsets[i] .. tri_offsets[i+1] of triangles [num_triangles,3] int,
+ * whose indices are local to the mesh (offsets [s+1] int, device).  A mesh whose offsets do not lie inside the packed
+ * arrays counts as empty.  At most 2^24 triangles per mesh; s <= 65535; num_vertices, num_triangles <= 2^28.
+ *
+ * Weights: in double on the widened coordinates, no fma: n = (b - a) x (c - a), each component (p q) - (r s);
+ * A2 = sqrt((nx^2 + ny^2) + nz^2); a2max [s] f64 = the largest of the mesh (an integer maximum on the bit pattern: exact
+ * in any order; 0 for a mesh without a valid triangle); weights [num_triangles] uint64 = floor(A2 / A2max * 2^32), in
+ * [0, 2^32].  A triangle with a vertex index outside its mesh, or whose A2 is not finite or is 0, gets weight 0 and is
+ * counted in invalid [s].  A triangle below 2^-32 of the mesh's largest gets weight 0 as well (it is never drawn) and is
+ * not counted.  cum [num_triangles] uint64 = the inclusive prefix sum of the weights inside each mesh (integer, exact).
+ * A memset and four launches, no floating-point atomic, no read-back.  workspace:
+ * cloudaae_mesh_weights_workspace_bytes(num_triangles) bytes (-1 for a bad argument), need not be initialised. */
+long long cloudaae_mesh_weights_workspace_bytes(long long num_triangles);
+int cloudaae_mesh_weights(int s, const int *vert_offsets, const int *tri_offsets, long long num_vertices,
+                          long long num_triangles, const float *vertices, const int *triangles,
+                          unsigned long long *weights, unsigned long long *cum, double *a2max, int *invalid,
+                          void *workspace, long long workspace_bytes, cloudaae_stream_t stream);
+/* n area-uniform surface samples of every mesh, by the cumulative weights `cum` (those of cloudaae_mesh_weights, or the
+ * caller's own: non-decreasing inside a mesh).  Sample j of mesh i has the global index g = first_index + j (< 2^40) and
+ * the four words r of philox4x32(seed, id * 2^40 + g, stream 20), id = mesh_ids[i] (device, [s]; NULL: id = i):
+ * with W = the mesh's last cum, target = the high 64 bits of (r0 2^32 + r1) W; the triangle is the first t with
+ * cum[t] > target; u = u01(r2), v = u01(r3) widened, both replaced by 1 - u, 1 - v when u + v > 1; b0 = (1 - u) - v;
+ * p = (b0 a + u b) + v c per coordinate in double, rounded once to float.  colors [num_vertices,3] f32 (NULL: zeros) are
+ * mixed the same way.  Outputs: xyzrgb [s,n,6] f32; tri [s,n] int (local to the mesh); normal [s,n,3] f64 (optional) =
+ * n / A2 of the triangle, its sign the winding's.  A mesh with W = 0, and a draw whose triangle has an index outside
+ * its mesh (possible with the caller's own cum only), give zeros and triangle -1.  One launch, one lane per sample; a
+ * sample does not depend on s, n or the launch.  Limits as above; s * n <= 2^28. */
+int cloudaae_mesh_sample(int s, const int *vert_offsets, const int *tri_offsets, long long num_vertices,
+                         long long num_triangles, const float *vertices, const float *colors, const int *triangles,
+                         const unsigned long long *cum, const int *mesh_ids, int n, unsigned long long first_index,
+                         unsigned long long seed, float *xyzrgb, int *tri, double *normal, cloudaae_stream_t stream);
+/* dst[i, j, 0..cols) = src[i, idx[i, j], 0..cols) for s sets of rows_per_set rows: idx [s,k] int (device) is local to
+ * the set, as cloudaae_ragged_fps returns it (outside [0, rows_per_set): a row of zeros); NULL: row j itself
+ * (k <= rows_per_set), which repacks a column range.  Row r of the source starts at src + r * src_row_stride elements,
+ * of the destination at dst + r * dst_row_stride (both >= cols); elem_bytes is 4 or 8.  s * k * cols <= 2^32. */
+int cloudaae_mesh_gather_rows(int s, int k, const int *idx, long long rows_per_set, const void *src,
+                              long long src_row_stride, int cols, int elem_bytes, void *dst, long long dst_row_stride,
+                              cloudaae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
