@@ -60,15 +60,57 @@ Knob *knob_slot(const char *name);
         }                                                                        \
     } while (0)
 
+// Per-device host state (what has been set up on which device) lives in arrays of DEVICE_SLOTS entries indexed by
+// the current device; a device the runtime cannot name, or one past the array, shares slot 0.
+constexpr int DEVICE_SLOTS = 64;
+inline int device_slot()
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= DEVICE_SLOTS)
+        dev = 0;
+    return dev;
+}
+
+// Dynamic LDS above 48 KiB has to be allowed per kernel AND device before the launch ("Launch
+// conventions").  Every launcher of such a kernel calls this first, with the bytes of this launch and the most that
+// kernel can ever ask for (a constant of the call site): the attribute is set to that maximum the first time a launch
+// of KERNEL on the current device needs it and never again, so a later, larger launch is already covered.  A launch
+// of 48 KiB or less touches nothing; one above `maximum` is a mistake of the call site and is refused (callers report
+// the result through CLOUDAAE_CHECK_HIP, which puts the entry point's name in front of "invalid argument" and so
+// replaces the text set here: the byte counts are for whoever calls the helper directly or reads it in a debugger).
+// No lock: two threads may both find the slot empty and both set the same value.
+constexpr size_t LDS_ALLOWED_BY_DEFAULT = 48 * 1024;
+template <auto KERNEL>
+hipError_t allow_dynamic_lds(size_t bytes, size_t maximum)
+{
+    static bool raised[DEVICE_SLOTS] = {};
+    if (bytes <= LDS_ALLOWED_BY_DEFAULT)
+        return hipSuccess;
+    if (bytes > maximum) {
+        set_error("allow_dynamic_lds: a launch with %zu bytes of dynamic LDS, its kernel's stated maximum is %zu", bytes,
+                  maximum);
+        return hipErrorInvalidValue;
+    }
+    const int dev = device_slot();
+    if (!raised[dev]) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)maximum);
+        if (e != hipSuccess)
+            return e;
+        raised[dev] = true;
+    }
+    return hipSuccess;
+}
+
 // Scratch of ONE call, stream ordered (hipMallocAsync / hipFreeAsync on the caller's stream: no state outlives the
 // call, nothing synchronises).  The device's default pool is told once to keep what it is given back: with the
 // default release threshold of 0 every stream synchronisation returns the memory to the driver and the next call
 // pays a real allocation.
 inline hipError_t scratch_alloc(void **p, size_t bytes, hipStream_t s)
 {
-    static bool tuned[64] = {};
-    int dev = -1;
-    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && !tuned[dev]) {
+    static bool tuned[DEVICE_SLOTS] = {};
+    const int dev = device_slot();
+    if (!tuned[dev]) {
         hipMemPool_t pool;
         if (hipDeviceGetDefaultMemPool(&pool, dev) == hipSuccess) {
             uint64_t keep = UINT64_MAX;

@@ -924,10 +924,9 @@ static int ec_launch_revlists(const char *name, int count, int b, int n, int k, 
         jobs.rev[i] = rev[i];
     }
     const size_t lds = (size_t)n * sizeof(int);
-    CLOUDAAE_REQUIRE(lds <= 150 * 1024, name, "cloud too large for the LDS counting sort");
-    if (lds > 48 * 1024)
-        CLOUDAAE_CHECK_HIP(hipFuncSetAttribute((const void *)ec_revlist_kernel,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), name);
+    constexpr size_t EC_REV_MAX_LDS = 150 * 1024;
+    CLOUDAAE_REQUIRE(lds <= EC_REV_MAX_LDS, name, "cloud too large for the LDS counting sort");
+    CLOUDAAE_CHECK_HIP(allow_dynamic_lds<ec_revlist_kernel>(lds, EC_REV_MAX_LDS), name);
     hipLaunchKernelGGL(ec_revlist_kernel, dim3(b, count), dim3(EC_REV_THREADS), lds, s, b, n, k, jobs,
                        CLOUDAAE_KNOB("CLOUDAAE_DETERMINISTIC", 0) != 0 ? 1 : 0);
     CLOUDAAE_CHECK_LAUNCH(name);

@@ -363,16 +363,10 @@ template <int BM, int BN, int WM, int WN, bool TA, bool TB, int DEPTH>
 static int launch_x3(const char *name, dim3 grid, hipStream_t s, int M, int N, int K, const float *A, int lda, const float *B,
                      int ldb, float *C, int ldc, const float *bias, int epi, int kchunk, double *cs)
 {
-    constexpr int bytes = x3_lds_bytes<BM, BN>();
-    static bool raised[64] = {};      // (per device: more than 64 KB of dynamic LDS needs the attribute)
-    int dev = 0;
-    CLOUDAAE_CHECK_HIP(hipGetDevice(&dev), name);
-    if (dev >= 0 && dev < 64 && !raised[dev]) {
-        CLOUDAAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_x3_kernel<BM, BN, WM, WN, TA, TB, DEPTH>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, bytes), name);
-        raised[dev] = true;
-    }
-    hipLaunchKernelGGL((gemm_x3_kernel<BM, BN, WM, WN, TA, TB, DEPTH>), grid, dim3(X3_THREADS), bytes, s, M, N, K, A, lda, B, ldb, C,
+    constexpr int bytes = x3_lds_bytes<BM, BN>();     // (every launch of an instantiation asks for the same amount)
+    constexpr auto kernel = &gemm_x3_kernel<BM, BN, WM, WN, TA, TB, DEPTH>;
+    CLOUDAAE_CHECK_HIP(allow_dynamic_lds<kernel>(bytes, bytes), name);
+    hipLaunchKernelGGL(kernel, grid, dim3(X3_THREADS), bytes, s, M, N, K, A, lda, B, ldb, C,
                        ldc, bias, epi, kchunk, cs);
     return 0;
 }
@@ -717,16 +711,10 @@ static int launch_x3s(const char *name, hipStream_t s, int M, int N, int K, cons
     typedef X3S<TM, TN, AS> G;
     constexpr int bytes = BNB ? G::LDS_BNB : G::LDS;
     static_assert(bytes <= 80 * 1024, "two workgroups per CU");
-    static bool raised[64] = {};
-    int dev = 0;
-    CLOUDAAE_CHECK_HIP(hipGetDevice(&dev), name);
-    if (dev >= 0 && dev < 64 && !raised[dev]) {
-        CLOUDAAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm_x3s_kernel<TM, TN, AS, BNB>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, bytes), name);
-        raised[dev] = true;
-    }
+    constexpr auto kernel = &gemm_x3s_kernel<TM, TN, AS, BNB>;
+    CLOUDAAE_CHECK_HIP(allow_dynamic_lds<kernel>(bytes, bytes), name);
     const int tiles = (M / G::BM) * (N / G::BN);
-    hipLaunchKernelGGL((gemm_x3s_kernel<TM, TN, AS, BNB>), dim3(tiles), dim3(256), bytes, s, M, N, K, A, lda,
+    hipLaunchKernelGGL(kernel, dim3(tiles), dim3(256), bytes, s, M, N, K, A, lda,
                        reinterpret_cast<const __bf16 *>(planes), C, ldc, bias, accumulate, cs, f);
     return 0;
 }

@@ -656,19 +656,8 @@ int icp_launch(const char *name, const double *tgt_normals, int inverse, int b, 
     constexpr int NS = PLANE ? ICP_PLANE_SUMS : ICP_SUMS;
     const int hbits = icp_hash_bits(n);
     const size_t lds = icp_lds_bytes(n, hbits, NS);
-    if (lds > 64 * 1024) {
-        static bool raised[64] = {};                       // one per instantiation
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
-            dev = 0;
-        if (!raised[dev]) {
-            CLOUDAAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&icp_kernel<PLANE>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)icp_lds_bytes(ICP_MAX_N, icp_hash_bits(ICP_MAX_N), NS)),
-                               name);
-            raised[dev] = true;
-        }
-    }
+    const size_t max_lds = icp_lds_bytes(ICP_MAX_N, icp_hash_bits(ICP_MAX_N), NS);      // (n <= ICP_MAX_N: checked above)
+    CLOUDAAE_CHECK_HIP(allow_dynamic_lds<icp_kernel<PLANE>>(lds, max_lds), name);
     hipLaunchKernelGGL(icp_kernel<PLANE>, dim3(b), dim3(ICP_THREADS), lds, (hipStream_t)stream, tgt_normals, inverse, m,
                        src, src_point_stride, src_cloud_stride, n, dst, dst_point_stride, dst_cloud_stride, rot_axag,
                        trans, radius, decay, rounds, max_iteration, relative_fitness, relative_rmse, hbits, transform,

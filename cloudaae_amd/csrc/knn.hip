@@ -24,23 +24,9 @@ namespace cloudaae {
 constexpr int KNN_WAVES = 4;
 constexpr int KNN_THREADS = 64 * KNN_WAVES;
 
-// Dynamic LDS above the default limit must be requested once per kernel AND device.
-template <typename F>
-static hipError_t raise_lds_limit(F kernel, bool (&raised)[64])
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
-        dev = 0;
-    if (!raised[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024);
-        if (e != hipSuccess)
-            return e;
-        raised[dev] = true;
-    }
-    return hipSuccess;
-}
-
+// The most dynamic LDS any kernel of this file asks for (the CU has 160 KiB; the kernels hold no static LDS).  Every launch
+// above 48 KiB goes through allow_dynamic_lds (common.h), which allows this much once per kernel and device.
+constexpr size_t KNN_MAX_LDS = 160 * 1024;
 
 template <int K>
 struct TopK {
@@ -480,10 +466,10 @@ template <int K, int QW, int CS>
 static hipError_t launch_knn_scan(int b, int n, int ld, int k, const float *x, int *nn_idx, hipStream_t s)
 {
     const size_t lds = sizeof(float) * (2 * CS * KM_TILE * 68 + 2 * QW * CS * KS_QCAP * 64 + (size_t)n);
-    static bool raised[64] = {};
-    if (hipError_t e = raise_lds_limit(&knn64_scan_kernel<K, QW, CS>, raised); e != hipSuccess)
+    constexpr auto kernel = &knn64_scan_kernel<K, QW, CS>;
+    if (hipError_t e = allow_dynamic_lds<kernel>(lds, KNN_MAX_LDS); e != hipSuccess)
         return e;
-    hipLaunchKernelGGL((knn64_scan_kernel<K, QW, CS>), dim3(ceil_div(n, KM_TILE * QW), b), dim3(64 * QW * CS), lds, s,
+    hipLaunchKernelGGL(kernel, dim3(ceil_div(n, KM_TILE * QW), b), dim3(64 * QW * CS), lds, s,
                        n, ld, k, x, nn_idx);
     return hipSuccess;
 }
@@ -954,7 +940,7 @@ __global__ __launch_bounds__(1024) void knn64_wide_kernel(int n, int ld, int k, 
             float dv[PER];
             unsigned short jv[PER];
             int mine = 0;
-            if (have <= QPQ) {                             // (an overflowed queue stays as it is: the flag will be raised)
+            if (have <= QPQ) {                             // (an overflowed queue stays as it is: the flag will be set)
 #pragma unroll
                 for (int u = 0; u < PER; ++u) {
                     const int i = sub + 8 * u;
@@ -1135,11 +1121,11 @@ template <int K, int QPQ, bool REUSE, bool TWO>
 static hipError_t launch_knn_wide_q(int b, int n, int ld, int k, const float *x, int *nn_idx, hipStream_t s)
 {
     const size_t lds = knn_wide_lds_bytes(n);
-    static bool raised[64] = {};
-    if (hipError_t e = raise_lds_limit(&knn64_wide_kernel<K, QPQ, REUSE, TWO>, raised); e != hipSuccess)
+    constexpr auto kernel = &knn64_wide_kernel<K, QPQ, REUSE, TWO>;
+    if (hipError_t e = allow_dynamic_lds<kernel>(lds, KNN_MAX_LDS); e != hipSuccess)
         return e;
-    hipLaunchKernelGGL((knn64_wide_kernel<K, QPQ, REUSE, TWO>), dim3(ceil_div(n, KM_TILE * 4), b), dim3(1024), lds, s, n, ld,
-                       k, x, nn_idx);
+    hipLaunchKernelGGL(kernel, dim3(ceil_div(n, KM_TILE * 4), b), dim3(1024), lds, s, n, ld, k, x, nn_idx,
+                       (const float *)nullptr);      // (no hint)
     return hipSuccess;
 }
 template <int K>
@@ -1207,17 +1193,17 @@ static hipError_t launch_knn_wide_hinted(int b, int n, int ld, int k, const floa
 {
     hipLaunchKernelGGL(knn64_hint_bound_kernel, dim3(ceil_div(n, 8), b), dim3(256), 0, s, n, ld, k, x, hint, tau);
     const size_t lds = knn_wide_lds_bytes(n);
-    static bool raised[64] = {};
     if (knn_wide_qpq(n) == 144) {
-        if (hipError_t e = raise_lds_limit(&knn64_wide_kernel<K, 144, false, false, true>, raised); e != hipSuccess)
+        constexpr auto kernel = &knn64_wide_kernel<K, 144, false, false, true>;
+        if (hipError_t e = allow_dynamic_lds<kernel>(lds, KNN_MAX_LDS); e != hipSuccess)
             return e;
-        hipLaunchKernelGGL((knn64_wide_kernel<K, 144, false, false, true>), dim3(ceil_div(n, KM_TILE * 4), b), dim3(1024), lds, s,
+        hipLaunchKernelGGL(kernel, dim3(ceil_div(n, KM_TILE * 4), b), dim3(1024), lds, s,
                            n, ld, k, x, nn_idx, tau);
     } else {
-        static bool raised128[64] = {};
-        if (hipError_t e = raise_lds_limit(&knn64_wide_kernel<K, 128, false, false, true>, raised128); e != hipSuccess)
+        constexpr auto kernel = &knn64_wide_kernel<K, 128, false, false, true>;
+        if (hipError_t e = allow_dynamic_lds<kernel>(lds, KNN_MAX_LDS); e != hipSuccess)
             return e;
-        hipLaunchKernelGGL((knn64_wide_kernel<K, 128, false, false, true>), dim3(ceil_div(n, KM_TILE * 4), b), dim3(1024), lds, s,
+        hipLaunchKernelGGL(kernel, dim3(ceil_div(n, KM_TILE * 4), b), dim3(1024), lds, s,
                            n, ld, k, x, nn_idx, tau);
     }
     return hipSuccess;
@@ -1472,10 +1458,10 @@ template <int K, int QPQ>
 static hipError_t launch_knn3_wide_q(int b, int n, int ld, int k, const float *x, int *nn_idx, hipStream_t s)
 {
     const size_t lds = knn3_wide_lds_bytes(n, K);
-    static bool raised[64] = {};
-    if (hipError_t e = raise_lds_limit(&knn3_wide_kernel<K, QPQ>, raised); e != hipSuccess)
+    constexpr auto kernel = &knn3_wide_kernel<K, QPQ>;
+    if (hipError_t e = allow_dynamic_lds<kernel>(lds, KNN_MAX_LDS); e != hipSuccess)
         return e;
-    hipLaunchKernelGGL((knn3_wide_kernel<K, QPQ>), dim3(ceil_div(n, KM_TILE * 4), b), dim3(1024), lds, s, n, ld, k, x, nn_idx);
+    hipLaunchKernelGGL(kernel, dim3(ceil_div(n, KM_TILE * 4), b), dim3(1024), lds, s, n, ld, k, x, nn_idx);
     return hipSuccess;
 }
 template <int K>
@@ -1486,7 +1472,7 @@ static hipError_t launch_knn3_wide(int b, int n, int ld, int k, const float *x, 
            : q == 124 ? launch_knn3_wide_q<K, 124>(b, n, ld, k, x, nn_idx, s)
                       : launch_knn3_wide_q<K, 112>(b, n, ld, k, x, nn_idx, s);
 }
-static bool knn3_wide_fits(int n, int k) { return k <= 20 && n >= 256 && knn3_wide_lds_bytes(n, k <= 10 ? 10 : 20) <= 160 * 1024; }
+static bool knn3_wide_fits(int n, int k) { return k <= 20 && n >= 256 && knn3_wide_lds_bytes(n, k <= 10 ? 10 : 20) <= KNN_MAX_LDS; }
 
 // ---- C = 3, second generation: the selection split into filter + queued drain ------------------
 // knn3_kernel above runs the sorted insert for every candidate of every lane (a wave executes it
@@ -1618,10 +1604,10 @@ template <int K, int CS>
 static hipError_t launch_knn3_scan(int b, int n, int ld, int k, const float *x, int *nn_idx, hipStream_t s)
 {
     const size_t lds = 16 * (size_t)n + 8 * 4 * K3_QCAP * 64;
-    static bool raised[64] = {};
-    if (hipError_t e = raise_lds_limit(&knn3_scan_kernel<K, CS>, raised); e != hipSuccess)
+    constexpr auto kernel = &knn3_scan_kernel<K, CS>;
+    if (hipError_t e = allow_dynamic_lds<kernel>(lds, KNN_MAX_LDS); e != hipSuccess)
         return e;
-    hipLaunchKernelGGL((knn3_scan_kernel<K, CS>), dim3(ceil_div(n, 64 * (4 / CS)), b), dim3(256), lds, s, n, ld, k, x,
+    hipLaunchKernelGGL(kernel, dim3(ceil_div(n, 64 * (4 / CS)), b), dim3(256), lds, s, n, ld, k, x,
                        nn_idx);
     return hipSuccess;
 }
@@ -1710,7 +1696,7 @@ CLOUDAAE_API int cloudaae_knn(int b, int n, int c, int ld, int k, const float *x
         return 0;
     CLOUDAAE_REQUIRE(k <= n, name, "k > number of points (tf.nn.top_k would reject it)");
     hipStream_t s = (hipStream_t)stream;
-    // (a failed launch preparation -- e.g. the LDS limit of a kernel cannot be raised on this device -- is an
+    // (a failed launch preparation -- e.g. a kernel's dynamic LDS cannot be allowed on this device -- is an
     //  error of the call, never a silently skipped kernel)
     const hipError_t e = k <= 10 ? launch_knn<10>(b, n, c, ld, k, x, nn_idx, s)
                        : k <= 20 ? launch_knn<20>(b, n, c, ld, k, x, nn_idx, s)

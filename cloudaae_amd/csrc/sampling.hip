@@ -230,18 +230,12 @@ __global__ __launch_bounds__(256) void scatter_add_point_kernel(int n, int m,
 template <int PPT>
 static int launch_fps_reg(int b, int n, int m, const float *inp, int *out, hipStream_t s)
 {
+    constexpr size_t FPS_MAX_LDS = 144 * 1024;      // the largest cloud kept in LDS (gfx950 has 160 KiB per CU)
     const size_t lds = (size_t)n * 3 * sizeof(float);
-    if (lds <= 144 * 1024) {
-        // opt in to > 64 KiB of dynamic LDS (gfx950 has 160 KiB per CU)
-        if (lds > 48 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)fps_kernel<PPT, true>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) {
-                set_error("cloudaae_farthest_point_sample: %s", hipGetErrorString(e));
-                return (int)e;
-            }
-        }
-        hipLaunchKernelGGL((fps_kernel<PPT, true>), dim3(b), dim3(FPS_THREADS), lds, s, n, m,
+    if (lds <= FPS_MAX_LDS) {
+        constexpr auto kernel = &fps_kernel<PPT, true>;
+        CLOUDAAE_CHECK_HIP(allow_dynamic_lds<kernel>(lds, FPS_MAX_LDS), "cloudaae_farthest_point_sample");
+        hipLaunchKernelGGL(kernel, dim3(b), dim3(FPS_THREADS), lds, s, n, m,
                            inp, out);
     } else {
         hipLaunchKernelGGL((fps_kernel<PPT, false>), dim3(b), dim3(FPS_THREADS), 0, s, n, m,

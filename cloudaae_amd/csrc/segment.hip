@@ -739,19 +739,8 @@ CLOUDAAE_API int cloudaae_radius_outlier(int s, const int *offsets, const float 
     uint8_t *flags = (uint8_t *)(ws + L.flags);
     int *blk_count = (int *)(ws + L.blk_count), *blk_off = (int *)(ws + L.blk_off);
     const int gblk = ceil_div(max_points, SEG_BLOCK);
-    const size_t lds = sizeof(int) * RO_CELLS;
-    {
-        static bool raised[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
-            dev = 0;
-        if (!raised[dev]) {
-            CLOUDAAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ro_grid_kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                               name);
-            raised[dev] = true;
-        }
-    }
+    constexpr size_t lds = sizeof(int) * RO_CELLS;      // (the same for every launch)
+    CLOUDAAE_CHECK_HIP(allow_dynamic_lds<ro_grid_kernel>(lds, lds), name);
     CLOUDAAE_CHECK_HIP(hipMemsetAsync(seg_count, 0, sizeof(int) * (size_t)s, st), name);
     hipLaunchKernelGGL(seg_fill_kernel, dim3(64, s), dim3(256), 0, st, offsets, max_points, seg);
     hipLaunchKernelGGL(ro_grid_kernel, dim3(s), dim3(RO_THREADS), lds, st, offsets, max_points, xyz, radius, grids, cell_start,

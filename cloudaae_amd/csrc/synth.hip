@@ -1061,6 +1061,7 @@ CLOUDAAE_API int cloudaae_hidden_point_removal_rows(int b, int n1, const float *
     CLOUDAAE_REQUIRE(rows >= 1, name, "bad number of output rows");
     // the cloud (12 bytes a point, dynamic LDS) next to the kernel's own static LDS (group slabs, working-set lists, the
     // centroid sums: ~10 KB, read from the code object) must fit the CU's 160 KB
+    constexpr size_t CU_LDS = 160 * 1024;
     static size_t static_lds[2] = {0, 0};
     if (static_lds[0] == 0) {
         hipFuncAttributes a8, a16;
@@ -1070,7 +1071,7 @@ CLOUDAAE_API int cloudaae_hidden_point_removal_rows(int b, int n1, const float *
         static_lds[0] = a8.sharedSizeBytes;
     }
     const size_t lds = (size_t)n1 * 3 * sizeof(float);
-    CLOUDAAE_REQUIRE(lds + static_lds[1] <= 160 * 1024, name, "cloud too large for the LDS-resident hull test");
+    CLOUDAAE_REQUIRE(lds + static_lds[1] <= CU_LDS, name, "cloud too large for the LDS-resident hull test");
     if (b == 0)
         return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -1080,22 +1081,15 @@ CLOUDAAE_API int cloudaae_hidden_point_removal_rows(int b, int n1, const float *
     int *perm = (int *)(sorted + pts * 3);
     int *next_point = perm + pts;
     // spatial order of every cloud: the 3-D grid in Morton order
-    {
-        static bool raised = false;
-        if (!raised) {
-            CLOUDAAE_CHECK_HIP(hipFuncSetAttribute((const void *)hpr_sort_grid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)(HG_CELLS * sizeof(int))), name);
-            raised = true;
-        }
-        hipLaunchKernelGGL(hpr_sort_grid_kernel, dim3(b), dim3(HS_THREADS), HG_CELLS * sizeof(int), s, n1, flipped, sorted, perm,
-                           next_point);
-    }
-    // a cloud that leaves room for ONE workgroup per CU (more than ~5900 points) takes 16 waves instead of 8
-    const bool wide = 2 * (lds + static_lds[0]) > 160 * 1024;
+    constexpr size_t grid_lds = HG_CELLS * sizeof(int);      // (the same for every launch)
+    CLOUDAAE_CHECK_HIP(allow_dynamic_lds<hpr_sort_grid_kernel>(grid_lds, grid_lds), name);
+    hipLaunchKernelGGL(hpr_sort_grid_kernel, dim3(b), dim3(HS_THREADS), grid_lds, s, n1, flipped, sorted, perm, next_point);
+    // a cloud that leaves room for ONE workgroup per CU (more than ~5900 points) takes 16 waves instead of 8: the 8-wave form
+    // never gets more than half a CU less its static LDS, the 16-wave form what the check above lets through
+    const bool wide = 2 * (lds + static_lds[0]) > CU_LDS;
     const int waves = wide ? 16 : 8;
-    if (lds > 48 * 1024)
-        CLOUDAAE_CHECK_HIP(hipFuncSetAttribute(wide ? (const void *)hull_vertex_kernel<16> : (const void *)hull_vertex_kernel<8>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), name);
+    CLOUDAAE_CHECK_HIP(wide ? allow_dynamic_lds<hull_vertex_kernel<16>>(lds, CU_LDS - static_lds[1])
+                            : allow_dynamic_lds<hull_vertex_kernel<8>>(lds, CU_LDS / 2 - static_lds[0]), name);
     // workgroups per cloud: two 8-wave workgroups fit a CU (512 on the chip), one of the 16-wave form (256).  The points of a
     // cloud come from its queue, so a workgroup lives as long as its cloud has points: exactly the resident number is launched.
     // (2 / 3 / 4 x as many -- late workgroups joining the clouds that still have points -- cost more in set-up than they
@@ -1113,8 +1107,11 @@ CLOUDAAE_API int cloudaae_hidden_point_removal_rows(int b, int n1, const float *
     else
         hipLaunchKernelGGL(hull_vertex_kernel<8>, dim3(gx, b), dim3(64 * 8), lds, s, n1, sorted, perm, hpr_stride(n1), culled,
                            next_point, flags);
-    hipLaunchKernelGGL(hpr_gather_kernel, dim3(b), dim3(512), (size_t)n1 * sizeof(int), s, n1, flags, org, seed,
-                       visible, num_vis, visible_id, row_src, rows);
+    // (an int per point where the hull test keeps three floats: a third of what the check above lets through)
+    const size_t gather_lds = (size_t)n1 * sizeof(int);
+    CLOUDAAE_CHECK_HIP(allow_dynamic_lds<hpr_gather_kernel>(gather_lds, (CU_LDS - static_lds[1]) / 3), name);
+    hipLaunchKernelGGL(hpr_gather_kernel, dim3(b), dim3(512), gather_lds, s, n1, flags, org, seed, visible, num_vis,
+                       visible_id, row_src, rows);
     CLOUDAAE_CHECK_LAUNCH(name);
     return 0;
 }
