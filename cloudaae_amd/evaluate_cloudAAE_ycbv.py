@@ -265,7 +265,8 @@ def _take(el, lo, hi):
 
 def main(argv=None):
     """evaluate_cloudAAE_ycbv.py's command line (:688-716, :356-657) without the visualisation and without RGB.
-    Reads <data_dir>/<seq>_pcnn.tfrecord of the class's test sequences (:43-63) file after file, in record order (the
+    Reads <data_dir>/<seq>_pcnn.tfrecord of the class's test sequences (:43-63) -- or, with --files A,B,..., those files,
+    e.g. rendered ones (utils/render.py) -- file after file, in record order (the
     reference interleaves them at random with sample_from_datasets), and prints the per-batch and the final loss
     lines (:568, :652-657).  A last batch smaller than --batch_size is not evaluated (the reference's reshape to
     BATCH_SIZE, :338, cannot take it).  --icp adds the refined pose's losses; --icp_plane refines by point-to-plane ICP
@@ -275,6 +276,9 @@ def main(argv=None):
     from . import train_cloudAAE_ycbv as T
     p = argparse.ArgumentParser()
     p.add_argument("--data_dir", default="ycb_video_data_tfRecords")
+    p.add_argument("--files", default=None,
+                   help="comma-separated frame record files to read instead of the class's test sequences under --data_dir "
+                        "(e.g. what `python -m cloudaae_amd.utils.render` wrote)")
     p.add_argument("--object_model", default=None,
                    help="obj_models.tfrecords [default: <data_dir>/../object_model_tfrecord/obj_models.tfrecords]")
     p.add_argument("--trained_model", required=True, help="checkpoint prefix (TrainGraph.restore)")
@@ -296,9 +300,14 @@ def main(argv=None):
     models, _ = tfrecord_io.read_and_decode_obj_model(obj_path)
     graph = T.TrainGraph({"num_point": args.num_point, "gpu": args.gpu}, {}, {"batch_size": args.batch_size})
     graph.restore(args.trained_model)
-    files = [os.path.join(args.data_dir, str(i).zfill(4) + "_pcnn.tfrecord") for i in VALID_SEQ_ID[args.target_cls]]
-    files = [f for f in files if os.path.exists(f)]
-    require(files, "no <seq>_pcnn.tfrecord of class %d under %s" % (args.target_cls, args.data_dir))
+    if args.files:
+        files = [f for f in args.files.split(",") if f]
+        missing = [f for f in files if not os.path.exists(f)]
+        require(files and not missing, "--files: no such file: %s" % ", ".join(missing))
+    else:
+        files = [os.path.join(args.data_dir, str(i).zfill(4) + "_pcnn.tfrecord") for i in VALID_SEQ_ID[args.target_cls]]
+        files = [f for f in files if os.path.exists(f)]
+        require(files, "no <seq>_pcnn.tfrecord of class %d under %s" % (args.target_cls, args.data_dir))
     pending, batch_idx, tot_trans, tot_axag, n_launch = None, 0, 0.0, 0.0, 0
     icp, model_normals = args.icp, None
     if args.icp_plane:

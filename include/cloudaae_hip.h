@@ -925,6 +925,42 @@ int cloudaae_mesh_gather_rows(int s, int k, const int *idx, long long rows_per_s
                               long long src_row_stride, int cols, int elem_bytes, void *dst, long long dst_row_stride,
                               cloudaae_stream_t stream);
 
+/* ---- depth and label frames of posed meshes ("Rendered frames", has the definition) ---- */
+
+/* f frames of h x w from j posed instances of the s packed meshes above (the layout of cloudaae_mesh_weights):
+ *   intrinsics [f,5] float (fx, fy, cx, cy, factor_depth: the rows cloudaae_frame_segments takes); the instances of
+ *   frame i are inst_offsets[i] .. inst_offsets[i+1] (inst_offsets [f+1] int); instance i draws mesh inst_mesh[i] under
+ *   the pose inst_pose[i] ([j,16] double, row-major 4x4, top three rows read: what cloudaae_pose_matrix writes) and
+ *   writes inst_label[i] (1..255; only the low 8 bits are kept) into `label`.
+ *   inst_vert_base, inst_tri_base [j+1] int: the exclusive prefix sums of the instances' vertex and triangle counts
+ *   in instance order, computed by the host from its copies of the offsets; sum_inst_vertices and sum_inst_triangles
+ *   are their last entries.  The draw rank of triangle t of instance i is inst_tri_base[i] + t.  All arrays are device
+ *   memory.  An instance whose mesh id or offsets do not describe ranges inside the packed arrays, or that lies in no
+ *   frame, draws nothing; bases that do not fit the meshes misplace ranks but never an access.
+ * Vertices: p = pose x in double on the widened floats (((R00 x + R01 y) + R02 z) + t0, no fma); sx = (fx X) / Z + cx,
+ * ix = floor(256 sx + 0.5), likewise iy; unusable when Z is not finite, Z < z_near or |ix|, |iy| > 2^24.  A triangle
+ * with an unusable vertex or an index outside its mesh is counted in dropped [j], one of zero fixed-point area in
+ * degenerate [j]; there is no clipping and no culling.  Pixel (u, v) is sampled at (256 u, 256 v); it is covered when
+ * the three int64 edge values w are >= 0; its depth is z = area2 / ((w_a / Z_a + w_b / Z_b) + w_c / Z_c) and
+ * du = floor(z factor_depth + 0.5), kept when 1 <= du <= 65535; the pixel takes the minimum of (du << 32 | rank).
+ * Outputs: depth [f,h,w] uint16 (0: nothing drawn), label [f,h,w] uint8 (0: background), tri [f,h,w] int (optional:
+ * the winning rank, -1 where empty), dropped, degenerate [j] int.  Every output is an integer and does not depend on
+ * the order of execution, the batch or the run.  Four memsets and four launches (vertices; setup, which rasterises
+ * the triangles of at most 16 samples and queues the others; the queue, one wave per triangle; resolve); only integer
+ * atomics; no read-back.  workspace: cloudaae_render_workspace_bytes(...) bytes, need not be initialised; the query
+ * returns 0 outside the limits, and the launch then returns an error without launching.  Limits: f, h, w, j >= 1;
+ * h * w <= 2^24; f * h * w <= 2^28; sum_inst_vertices, sum_inst_triangles < 2^31; at most 2^24 triangles per mesh
+ * (checked as sum_inst_triangles <= j * 2^24); z_near > 0. */
+long long cloudaae_render_workspace_bytes(int f, int h, int w, int j, long long sum_inst_vertices,
+                                          long long sum_inst_triangles);
+int cloudaae_render_frames(int s, const int *vert_offsets, const int *tri_offsets, long long num_vertices,
+                           long long num_triangles, const float *vertices, const int *triangles, int f, int h, int w,
+                           const float *intrinsics, const int *inst_offsets, int j, const int *inst_mesh,
+                           const int *inst_label, const double *inst_pose, const int *inst_vert_base,
+                           const int *inst_tri_base, long long sum_inst_vertices, long long sum_inst_triangles,
+                           double z_near, uint16_t *depth, uint8_t *label, int *tri, int *dropped, int *degenerate,
+                           void *workspace, long long workspace_bytes, cloudaae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
