@@ -136,6 +136,8 @@ _SIGNATURES = {
     "cloudaae_mesh_gather_rows": [_I, _I, _P, _L, _P, _L, _I, _I, _P, _L, _P],
     "cloudaae_render_frames": [_I, _P, _P, _L, _L, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _D, _P, _P, _P,
                                _P, _P, _P, _L, _P],
+    "cloudaae_vsd_counts": [_I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _D, _I, _P, _P, _P, _P, _P, _P],
+    "cloudaae_pose_max_dist": [_I, _I, _I, _P, _I, _L, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
 }
 
 
@@ -355,6 +357,7 @@ def lib():
                        ("cloudaae_mesh_weights_workspace_bytes", [_L]),
                        ("cloudaae_render_workspace_bytes", [_I, _I, _I, _I, _L, _L]),
                        ("cloudaae_pose_score_workspace_bytes", [_I, _I, _I]),
+                       ("cloudaae_pose_max_dist_workspace_bytes", [_I, _I, _I]),
                        ("cloudaae_estimate_normals_workspace_bytes", [_I, _L]),
                        ("cloudaae_cloud_diameter_workspace_bytes", [_I, _I])):
             getattr(cdll, q).argtypes = sig

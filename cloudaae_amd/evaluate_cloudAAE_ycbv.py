@@ -32,13 +32,14 @@ from .losses import angular_distance_taylor, chamfer_loss, trans_distance
 from .tf_ops.sampling import tf_sampling
 from .train_cloudAAE_ycbv import NUM_CLASS
 from .utils import _functions as F
+from .utils import bop_score as bop_util
 from .utils import icp as icp_util
 from .utils import normals as normals_util
 from .utils import pose_score as score_util
 from .utils import segment as seg_util
 
 
-def evaluate_batch(graph, element, replay=False, icp=None, score=None):
+def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None):
     """One pass of evaluate_cloudAAE_ycbv.py:421-477 on a batch.  Returns the tensors its loop
     fetches (:546-560): xyz_recon [B,4N,3], xyz_recon_FPS [B,N,3], rot_pred, trans_pred, the three
     losses with their per-sample values, mean_dist_loss, element_mean.
@@ -58,12 +59,58 @@ def evaluate_batch(graph, element, replay=False, icp=None, score=None):
     score=True: the predicted pose [rot_pred | trans_pred] and, with icp, the refined one (transformation_icp) are
     scored against [axisangle | translation] on element['obj_batch'] by one cloudaae_pose_score launch: adds add_pred,
     adds_pred and, with icp, add_icp, adds_icp [B] float64 (ADD and ADD-S in metres).  The other outputs are those of
-    score=None."""
+    score=None.
+    bop=dict(meshes=PackedMeshes, mesh_index=[B] host integers or None (then class_id), diameters=[C] (metres, per class),
+    symmetries=None or {class: [n,4,4] transforms that hold the identity}): the same poses are scored with BOP's errors
+    (utils/bop_score.py, DESIGN.md "BOP pose errors") against the sample's own frame, element['frame_depth'] [B,H,W]
+    and element['frame_intrinsics'] [B,5] (element_from_frames(keep_frames=True)): adds vsd_pred [B,K], mssd_pred,
+    mspd_pred [B] float64 and, with icp, vsd_icp, mssd_icp, mspd_icp.  MSSD and MSPD are taken on element['obj_batch'].
+    Not with replay=True.  The other outputs are those of bop=None."""
     icp = _icp_params(icp)
     score = bool(score)
+    if bop is not None:
+        require(isinstance(bop, dict) and bop.get('meshes') is not None and bop.get('diameters') is not None,
+                "bop must be a dict with 'meshes' and 'diameters'")
+        require(not replay, "bop scores are not available with replay=True: every chunk of rendered frames is allocated by "
+                            "its own sizes and read back, which does not fit a recorded plan")
     if replay:
         return _replayed(graph, element, icp, score)
-    return _evaluate(graph, element, icp, score)
+    out = _evaluate(graph, element, icp, score)
+    if bop is not None:
+        out.update(_bop(element, out, bop))
+    return out
+
+
+def _bop(element, out, bop):
+    """VSD, MSSD and MSPD of the predicted pose and, when there is one, of the refined pose."""
+    obj, depth, intr = element.get('obj_batch'), element.get('frame_depth'), element.get('frame_intrinsics')
+    require(obj is not None and depth is not None and intr is not None,
+            "bop needs element['obj_batch'], ['frame_depth'] and ['frame_intrinsics'] (element_from_frames(keep_frames=True))")
+    cls = element['class_id'].to(torch.int64)
+    B = int(cls.shape[0])
+    with torch.no_grad():
+        gt = score_util.pose_matrix(element['axisangle'], element['translation'].to(torch.float32).contiguous())
+        est = score_util.pose_matrix(out['rot_pred'].contiguous(), out['trans_pred'].contiguous())
+        names = ("pred",)
+        if out.get('transformation_icp') is not None:
+            est = score_util.stack_poses(est, out['transformation_icp'])
+            names = ("pred", "icp")
+        else:
+            est = est.unsqueeze(1)
+        diam = bop['diameters']
+        diam = diam if isinstance(diam, torch.Tensor) else torch.from_numpy(np.asarray(diam, np.float64))
+        diam = diam.to(device=cls.device, dtype=torch.float64).index_select(0, cls)
+        mesh_index = bop.get('mesh_index')
+        sym = bop.get('symmetries')
+        cls_host = cls.cpu().numpy() if (mesh_index is None or sym is not None) else None
+        v = bop_util.vsd(bop['meshes'], cls_host if mesh_index is None else mesh_index, est, gt, depth, intr,
+                         np.arange(B), diam, **{k: bop[k] for k in ('delta', 'taus', 'samples_per_launch') if k in bop})
+        d = bop_util.mssd_mspd(obj, est, gt, intr.to(torch.float32),
+                               None if sym is None else [sym.get(int(c)) for c in cls_host])
+    res = {}
+    for k, name in enumerate(names):
+        res['vsd_' + name], res['mssd_' + name], res['mspd_' + name] = v['errors'][:, k], d['mssd'][:, k], d['mspd'][:, k]
+    return res
 
 
 NORMAL_RADIUS = 0.015     # neighbourhood of the class models' normals, metres (profiles/notes_icp_plane.md)
@@ -212,14 +259,16 @@ VALID_SEQ_ID = [[48, 51, 55, 56], [50, 54, 59], [49, 51, 54, 55, 58], [50, 51, 5
                 [48, 55], [50, 54, 56, 59], [55], [51], [57, 59], [48, 54], [48, 57], [57]]
 
 
-def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, device=None):
+def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, device=None, keep_frames=False):
     """create_tfrecord_dataset (:287-335) on decoded frame records (tfrecord_io.decode_frame): the frames that hold
     target_cls, their target_cls segment, the mean-distance filter, radius outlier removal, FPS_random of the inliers
     and of the filtered points from seeded starts, the > 100 and >= num_point rules, quat2axangle, the object model,
     its hidden point removal (centre 0, 0.8 pi).  obj_models: [21, 2048, 6] float32 (numpy or device tensor).
     Returns the element evaluate_batch takes (device tensors: xyz_inlier [B,N,3], xyz, visiblePoints_org
     [B,2049,3], class_id [B], translation [B,3], axisangle [B,3] float64, obj_batch [B,2048,6]) plus seq_id,
-    frame_id and num_valid_points_in_segment [B] (numpy); None when no segment survives."""
+    frame_id and num_valid_points_in_segment [B] (numpy); None when no segment survives.  keep_frames=True adds each
+    sample's own frame, frame_depth [B,H,W] int16 (the uint16 bits) and frame_intrinsics [B,5] float32 (device tensors):
+    what evaluate_batch(bop=...) compares the rendered object with."""
     from .train_cloudAAE_ycbv import get_object_model, get_rotation_matrix, transform_object_model
     from .utils import hidden_point_removal as hpr
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -256,6 +305,10 @@ def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, devic
     el["seq_id"] = np.array([int(frames[int(r.frame[i])]["seq_id"]) for i in keep], np.int64)
     el["frame_id"] = np.array([int(frames[int(r.frame[i])]["frame_id"]) for i in keep], np.int64)
     el["num_valid_points_in_segment"] = r.num_valid_points_in_segment[keep]
+    if keep_frames:
+        of = np.asarray(r.frame, np.int64)[keep]
+        el["frame_depth"] = torch.from_numpy(np.ascontiguousarray(depth[of].astype(np.uint16)).view(np.int16)).to(device)
+        el["frame_intrinsics"] = torch.from_numpy(intr[of]).to(device)
     return el
 
 
@@ -271,7 +324,9 @@ def main(argv=None):
     lines (:568, :652-657).  A last batch smaller than --batch_size is not evaluated (the reference's reshape to
     BATCH_SIZE, :338, cannot take it).  --icp adds the refined pose's losses; --icp_plane refines by point-to-plane ICP
     on the class models' normals instead (computed once, before the loop).  --score prints, after the final line,
-    the ADD / ADD-S summary of the predicted (and refined) poses per class and over all (PoseScoreLog.lines)."""
+    the ADD / ADD-S summary of the predicted (and refined) poses per class and over all (PoseScoreLog.lines).  --bop
+    --meshes DIR [--mesh_scale X] prints, after those, BOP's average recalls (BopScoreLog.lines): class i is the i-th
+    *.ply of DIR in sorted order (the convention of utils/render.py), symmetries the identity alone."""
     from . import tfrecord_io
     from . import train_cloudAAE_ycbv as T
     p = argparse.ArgumentParser()
@@ -289,10 +344,15 @@ def main(argv=None):
     p.add_argument("--icp_plane", action="store_true",
                    help="refine by point-to-plane ICP on the class models' normals (implies --icp)")
     p.add_argument("--score", action="store_true", help="ADD / ADD-S, AUC and accuracy summary of the scored poses")
+    p.add_argument("--bop", action="store_true", help="BOP's VSD / MSSD / MSPD average recalls of the scored poses (needs --meshes)")
+    p.add_argument("--meshes", default=None, help="directory of *.ply files; class i is the i-th in sorted order")
+    p.add_argument("--mesh_scale", type=float, default=1.0, help="factor on the meshes' coordinates (0.001: millimetres to metres)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--frames_per_launch", type=int, default=8)
     p.add_argument("--gpu", type=int, default=0)
     args = p.parse_args(argv)
+    if args.bop and not args.meshes:
+        p.error("--bop needs --meshes DIR")
     args.icp = args.icp or args.icp_plane
     torch.cuda.set_device(args.gpu)
     obj_path = args.object_model or os.path.join(os.path.dirname(os.path.abspath(args.data_dir)),
@@ -319,6 +379,12 @@ def main(argv=None):
     if args.score:
         diam = score_util.model_diameter(torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda())
         log = score_util.PoseScoreLog(("pred", "icp") if args.icp else ("pred",), diameters=diam)
+    bop, bop_log = None, None
+    if args.bop:
+        from .utils import mesh_models
+        diam = score_util.model_diameter(torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda())
+        bop = dict(meshes=mesh_models.pack_meshes(mesh_models.mesh_files(args.meshes), args.mesh_scale), diameters=diam)
+        bop_log = bop_util.BopScoreLog(("pred", "icp") if args.icp else ("pred",), diameters=diam)
 
     def frames():
         for fn in files:
@@ -332,7 +398,8 @@ def main(argv=None):
                 yield buf
 
     for chunk in frames():
-        el = element_from_frames(chunk, args.target_cls, args.num_point, models, seed=args.seed + n_launch)
+        el = element_from_frames(chunk, args.target_cls, args.num_point, models, seed=args.seed + n_launch,
+                                 keep_frames=args.bop)
         n_launch += 1
         if el is None:
             continue
@@ -344,7 +411,11 @@ def main(argv=None):
             el_b = {k: v for k, v in b.items() if isinstance(v, torch.Tensor)}
             if model_normals is not None:
                 el_b['obj_normals'] = model_normals.index_select(0, el_b['class_id'])
-            out = evaluate_batch(graph, el_b, icp=icp, score=args.score)
+            out = evaluate_batch(graph, el_b, icp=icp, score=args.score, bop=bop)
+            if bop_log is not None:
+                bop_log.append(b["class_id"], *[torch.stack([out[m + n] for n in bop_log.poses], dim=1)
+                                                for m in ("vsd_", "mssd_", "mspd_")],
+                               width=int(b["frame_depth"].shape[2]), seq=b["seq_id"], frame=b["frame_id"])
             if log is not None:
                 log.append(b["class_id"], torch.stack([out["add_" + n] for n in log.poses], dim=1),
                            torch.stack([out["adds_" + n] for n in log.poses], dim=1), seq=b["seq_id"], frame=b["frame_id"])
@@ -362,6 +433,9 @@ def main(argv=None):
         print("trans_loss %f axag_loss %f" % (tot_trans / batch_idx, tot_axag / batch_idx))
     if log is not None:
         for line in log.lines():
+            print(line)
+    if bop_log is not None:
+        for line in bop_log.lines():
             print(line)
     sys.stdout.flush()
     return 0

@@ -52,6 +52,37 @@ def _poses(flat, device):
     return out.view(J, 16)
 
 
+def render_instances(p, intr, offs, mesh, lab, poses, H, W, z_near=Z_NEAR, return_tri=False):
+    """The launch behind render_frames, for callers whose poses are already on the device (bop_score.vsd): p a
+    PackedMeshes, intr [F,5] float32 on its device, offs [F+1], mesh, lab [J] host integers (checked by the caller),
+    poses [J,16] float64 on the device.  -> (depth [F,H,W] int16, label uint8, tri int32 or None, counts [2,J] int32:
+    dropped and degenerate, all on the device; tri_base [J+1] numpy).  No read-back."""
+    dev = p.device
+    F, J, S = len(offs) - 1, len(mesh), len(p.num_triangles)
+    vb = np.concatenate([[0], np.cumsum(np.asarray(p.num_vertices, np.int64)[mesh])])
+    tb = np.concatenate([[0], np.cumsum(np.asarray(p.num_triangles, np.int64)[mesh])])
+    L = _lib.lib()
+    nbytes = int(L.cloudaae_render_workspace_bytes(F, H, W, J, int(vb[-1]), int(tb[-1])))
+    require(nbytes > 0, "outside the renderer's limits: H W <= 2^24, F H W <= 2^28, fewer than 2^31 triangles drawn")
+    ints = torch.from_numpy(np.concatenate([offs, mesh, lab, vb, tb]).astype(np.int32)).to(dev)
+    inst_offsets, inst_mesh, inst_label = ints[:F + 1], ints[F + 1:F + 1 + J], ints[F + 1 + J:F + 1 + 2 * J]
+    vert_base, tri_base = ints[F + 1 + 2 * J:F + 2 + 3 * J], ints[F + 2 + 3 * J:]
+    depth = _lib.empty((F, H, W), dtype=torch.int16, device=dev)
+    label = _lib.empty((F, H, W), dtype=torch.uint8, device=dev)
+    tri = _lib.empty((F, H, W), dtype=torch.int32, device=dev) if return_tri else None
+    counts = _lib.empty((2, J), dtype=torch.int32, device=dev)
+    ws = _lib.empty((nbytes,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.cloudaae_render_frames(S, ptr(p.vert_offsets), ptr(p.tri_offsets), int(p.vertices.shape[0]),
+                                            int(p.triangles.shape[0]), ptr(p.vertices), ptr(p.triangles), F, H, W, ptr(intr),
+                                            inst_offsets.data_ptr(), J, inst_mesh.data_ptr(), inst_label.data_ptr(),
+                                            ptr(poses), vert_base.data_ptr(), tri_base.data_ptr(), int(vb[-1]), int(tb[-1]),
+                                            float(z_near), depth.data_ptr(), label.data_ptr(), ptr(tri),
+                                            counts[0].data_ptr(), counts[1].data_ptr(), ptr(ws), nbytes, stream()),
+                   "cloudaae_render_frames")
+    return depth, label, tri, counts, tb
+
+
 def render_frames(meshes, instances, intrinsics, height, width, z_near=Z_NEAR, return_tri=False, scale=1.0, device=None):
     """F frames of height x width.  meshes: a PackedMeshes or what mesh_models.pack_meshes takes (`scale` applies then).
     instances: per frame a list of (mesh index, label in 1..255, pose); a frame may be empty.  pose: model -> camera, a
@@ -79,28 +110,7 @@ def render_frames(meshes, instances, intrinsics, height, width, z_near=Z_NEAR, r
     require(lab.min() >= 1 and lab.max() <= 255, "labels must lie in 1..255 (0 is the background)")
     require(float(z_near) > 0.0, "z_near must be positive")
     offs = np.cumsum([0] + [len(fr) for fr in instances])
-    vb = np.concatenate([[0], np.cumsum(np.asarray(p.num_vertices, np.int64)[mesh])])
-    tb = np.concatenate([[0], np.cumsum(np.asarray(p.num_triangles, np.int64)[mesh])])
-    L = _lib.lib()
-    nbytes = int(L.cloudaae_render_workspace_bytes(F, H, W, J, int(vb[-1]), int(tb[-1])))
-    require(nbytes > 0, "outside the renderer's limits: H W <= 2^24, F H W <= 2^28, fewer than 2^31 triangles drawn")
-    ints = torch.from_numpy(np.concatenate([offs, mesh, lab, vb, tb]).astype(np.int32)).to(dev)
-    inst_offsets, inst_mesh, inst_label = ints[:F + 1], ints[F + 1:F + 1 + J], ints[F + 1 + J:F + 1 + 2 * J]
-    vert_base, tri_base = ints[F + 1 + 2 * J:F + 2 + 3 * J], ints[F + 2 + 3 * J:]
-    poses = _poses(flat, dev)
-    depth = _lib.empty((F, H, W), dtype=torch.int16, device=dev)
-    label = _lib.empty((F, H, W), dtype=torch.uint8, device=dev)
-    tri = _lib.empty((F, H, W), dtype=torch.int32, device=dev) if return_tri else None
-    counts = _lib.empty((2, J), dtype=torch.int32, device=dev)
-    ws = _lib.empty((nbytes,), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.cloudaae_render_frames(S, ptr(p.vert_offsets), ptr(p.tri_offsets), int(p.vertices.shape[0]),
-                                            int(p.triangles.shape[0]), ptr(p.vertices), ptr(p.triangles), F, H, W, ptr(intr),
-                                            inst_offsets.data_ptr(), J, inst_mesh.data_ptr(), inst_label.data_ptr(),
-                                            ptr(poses), vert_base.data_ptr(), tri_base.data_ptr(), int(vb[-1]), int(tb[-1]),
-                                            float(z_near), depth.data_ptr(), label.data_ptr(), ptr(tri),
-                                            counts[0].data_ptr(), counts[1].data_ptr(), ptr(ws), nbytes, stream()),
-                   "cloudaae_render_frames")
+    depth, label, tri, counts, tb = render_instances(p, intr, offs, mesh, lab, _poses(flat, dev), H, W, z_near, return_tri)
     host = counts.cpu().numpy()
     out = dict(depth=depth, label=label, dropped=host[0], degenerate=host[1], tri_base=tb)
     if return_tri:

@@ -50,7 +50,8 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * cloudaae_radius_outlier, cloudaae_ragged_fps and their workspace queries; cloudaae_dev_gemm_folded (development /
  * test entry); cloudaae_bn_backward_dx_bf16x3 and its two queries; cloudaae_pose_score, cloudaae_cloud_diameter (each with
  * a workspace query), cloudaae_pose_matrix and cloudaae_pose_stack; cloudaae_icp_point_to_plane and
- * cloudaae_estimate_normals with its workspace query; cloudaae_sample_poses and cloudaae_random_object_occluder. */
+ * cloudaae_estimate_normals with its workspace query; cloudaae_sample_poses and cloudaae_random_object_occluder;
+ * cloudaae_vsd_counts and cloudaae_pose_max_dist with its workspace query. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -960,6 +961,38 @@ int cloudaae_render_frames(int s, const int *vert_offsets, const int *tri_offset
                            const int *inst_tri_base, long long sum_inst_vertices, long long sum_inst_triangles,
                            double z_near, uint16_t *depth, uint8_t *label, int *tri, int *dropped, int *degenerate,
                            void *workspace, long long workspace_bytes, cloudaae_stream_t stream);
+
+/* ---- BOP pose errors ("BOP pose errors (VSD, MSSD, MSPD)", has the definition) ---- */
+
+/* The pixel counts behind the visible surface discrepancy of b samples with p estimated poses each.
+ *   depth_test [f,h,w] uint16 with intrinsics [f,5] float (fx, fy, cx, cy, factor_depth); frame_of [b] int: the test
+ *   frame of each sample; depth_gt [b,h,w], depth_est [b,p,h,w] uint16: the object's mesh alone, rendered with that
+ *   frame's intrinsics under the ground truth and under the estimates; tau [b,k] double.  All device memory.
+ * Per pixel (u = column, v = row), in double, no fma: m = sqrt((xn xn + yn yn) + 1) with xn = (u - cx) / fx,
+ * yn = (v - cy) / fy; D(d) = (d / factor) m; valid_t = dt != 0; vis_g = dg != 0 and (not valid_t or D(dg) - D(dt) <=
+ * delta); vis_e = de != 0 and (not valid_t or D(de) - D(dt) <= delta or vis_g).
+ * Outputs (int, zeroed by the call): inter [b,p] = #(vis_g and vis_e); uni [b,p] = #(vis_g or vis_e); over [b,p,k] =
+ * #(vis_g and vis_e and |D(dg) - D(de)| >= tau[k]); visib_gt [b] = #vis_g.  Four memsets and one launch; integer atomics
+ * only, so the counts do not depend on the order of execution, the batch or the run.  A frame_of entry outside [0, f)
+ * leaves that sample's counts 0 and causes no access.  Limits: f, h, w, b, p >= 1; 1 <= k <= 16; h * w <= 2^24;
+ * b * p * h * w <= 2^28; outside them the call returns an error and launches nothing. */
+int cloudaae_vsd_counts(int f, int h, int w, const uint16_t *depth_test, const float *intrinsics, int b, int p,
+                        const int *frame_of, const uint16_t *depth_gt, const uint16_t *depth_est, double delta, int k,
+                        const double *tau, int *inter, int *uni, int *over, int *visib_gt, cloudaae_stream_t stream);
+
+/* MSSD and MSPD of b samples with p estimated poses each on the model points of cloudaae_pose_score (model, point_stride,
+ * cloud_stride, est [b,p,16], gt [b,16] as there).  sym [b,smax,16] double: the symmetry transforms of each sample's
+ * object (row-major 4x4, top three rows read), of which the first num_sym[b] (clamped into 1..smax) are used; the
+ * identity must be among them.  mssd [b,p] = min_s sqrt(max_i |E x_i - G (S_s x_i)|^2), squares summed as (dx^2 + dy^2)
+ * + dz^2.  intrinsics [b,5] float (each sample's frame) and mspd [b,p] go together, both or NULL: mspd = min_s
+ * sqrt(max_i ((ue - ug)^2 + (ve - vg)^2)) with u = (fx X) / Z + cx, v = (fy Y) / Z + cy, and +inf when a Z under E or
+ * G S_s is not > 0.  Maxima and minima are exact (integer comparisons on the bit patterns); a memset and two launches.
+ * workspace: cloudaae_pose_max_dist_workspace_bytes(b, p, smax) bytes (-1 for an argument below 1), need not be
+ * initialised.  Limits: b * p * ceil(m / 128) < 2^31, b * p * smax <= 2^28. */
+long long cloudaae_pose_max_dist_workspace_bytes(int b, int p, int smax);
+int cloudaae_pose_max_dist(int b, int p, int m, const float *model, int point_stride, long long cloud_stride,
+                           const double *est, const double *gt, int smax, const int *num_sym, const double *sym,
+                           const float *intrinsics, double *mssd, double *mspd, void *workspace, cloudaae_stream_t stream);
 
 #ifdef __cplusplus
 }
