@@ -189,51 +189,44 @@ __global__ __launch_bounds__(NN_THREADS) void nn_distance_kernel(
 
 // ---- second generation: matrix-core filter + exact verification -----------------------------------
 // The hot loop above spends 8.6 lane-operations per pair on arithmetic whose only purpose is to find
-// WHICH candidate is nearest.  Here the search runs on the matrix cores with a cheaper, differently
-// rounded score, and the reference's arithmetic is applied only where the answer is decided:
-//   * score s_ij = |b'_j|^2 - 2 a'_i . b'_j  (= d^2_ij - |a'_i|^2, the same order over j), primes =
-//     coordinates relative to the candidate cloud's first point (keeps the magnitudes, hence the
-//     rounding errors, small).  One 32 x 32 tile of scores is two v_mfma_f32_32x32x2_f32 (K = 4:
-//     [bx by bz |b|^2] x [-2ax -2ay -2az 1]); rows = candidates, columns = queries, so a lane's 16
-//     accumulator registers are 16 candidates of ITS query and the minimum is taken in the lane.
-//   * per query: the three best UNIT scores (a unit = the 32 rows of two consecutive tiles that one lane
-//     half holds) and the units of the first two.
-//   * afterwards the 64 candidates of the two best units are evaluated with the reference's un-fused
-//     arithmetic (first index of the exact minimum wins).  That is the answer if no third unit can
-//     hold a candidate that is as near in the reference's arithmetic: s3 > s1 + M with
-//     M = 32 * 2^-24 * (|a'| + max_j |b'_j|)^2.  Bound: a score is a 4-term fp32 sum of exact products
-//     plus the rounded |b'|^2 (<= 7 ulp-units of R = (|a'|+|b'|max)^2), the translation by the centre
-//     moves a squared distance by <= 4 * 2^-24 * sqrt(R d^2) <= 4 * 2^-24 * R, and the reference's
-//     value is within 8 * 2^-24 * d^2 of the true one; two candidates whose scores differ by more than
-//     2 * (7 + 4 + 4) * 2^-24 * R = 30 * 2^-24 * R are therefore ordered the same way by the reference.
-//   * otherwise (three units within the margin) a SECOND pass over the scores settles it: every candidate whose
-//     score is at most s1 + M -- nothing else can be as near in the reference's arithmetic -- is evaluated
-//     exactly where it turns up (a tile whose minimum lies above the threshold costs its two MFMAs and the
-//     minimum).  Random clouds need it for about one query in 10^4; clouds with DUPLICATED candidates for every
-//     query: the reference's own training targets are the visible points padded with random re-draws
-//     (utils/hidden_point_removal.py:38-40), so the nearest target point of a query sits in two to four units
-//     with bitwise equal scores.  (Round 2 scanned all candidates of such a query exactly, the 64 lanes sharing
-//     them: 4 x the time of the search at [32,16384]^2 with fourfold duplicates.)  Non-finite scores (overflow,
-//     NaN: every comparison false) still take that full scan.
-// Results are the reference's bit for bit; 2 MFMA + ~13 VALU instructions per 1024 pairs instead of
-// ~140.
-//
-// Round 5: the scores on the BF16 matrix pipe (template SPLIT).  v_mfma_f32_32x32x2_f32 runs at the fp32 vector rate and
-// shares its datapath with the vector ALU: the digest of a tile (the minima, the top three) ADDS to the matrix time
-// (profiles/r05_mfma_valu_overlap.txt).  v_mfma_f32_32x32x16_bf16 is its own pipe -- vector instructions of the same wave
-// overlap it -- and does sixteen products per output element in half the cycles.  Every centred coordinate is split
-// exactly into three bfloat16 pieces v = h + m + l (round to nearest even; 3 x 8 significand bits), the query pieces
-// pre-multiplied by -2 (exact), and a score is the sum over 21 of the 32 K-slots of two such MFMAs:
-//     MFMA 1:  Ch.Qh  Ch.Qm  Cm.Qh  Cm.Qm  (3 coordinates each)   |b'|^2 as its three pieces x 1
-//     MFMA 2:  Ch.Ql  Cl.Qh
-// i.e. every piece product of weight >= 2^-16; each product of two bfloat16 is exact in fp32.  What a score can be off the
-// exact |b'|^2 - 2 a'.b' of the centred fp32 values: the dropped pieces (m.l, l.m, l.l: <= 2^-22 |a'||b'| <= 1 unit of
-// 2^-24 R), the rounding of |b'|^2 itself (3 units), and the accumulation inside the two MFMAs -- 21 non-zero terms and
-// the carried sum; charged here with ONE FULL ULP of R per K-slot (truncating alignment, 2 units each: 64 units), which is
-// far above what the hardware shows (tests/test_00_ops_gpu.py::test_nn_distance_split_score_error measures <= 4 units).
-// With the translation (4) and the reference's own rounding (4) two candidates whose scores differ by more than
-// 2 * (1 + 3 + 64 + 4 + 4) = 152 units are ordered the same way by the reference: M = 160 * 2^-24 * R (five times the
-// fp32 form's margin: still ~1e-6 of R against neighbour gaps of 1e-4 R, the second pass stays a rarity).
+// WHICH candidate is nearest.  nn_distance_filter_kernel runs the search on the bf16 matrix pipe with a cheaper,
+// differently rounded score, and applies the reference's arithmetic only where the answer is decided.
+//   * Score: s_ij = |b'_j|^2 - 2 a'_i . b'_j  (= d^2_ij - |a'_i|^2, the same order over j), primes = coordinates relative
+//     to the candidate cloud's first point (keeps the magnitudes, hence the rounding errors, small).  Every centred
+//     coordinate is split exactly into three bfloat16 pieces v = h + m + l (round to nearest even; 3 x 8 significand bits),
+//     the query pieces pre-multiplied by -2 (exact), and a 32 x 32 tile of scores is two v_mfma_f32_32x32x16_bf16 that use 21
+//     of their 32 K-slots:
+//         MFMA 1:  Ch.Qh  Ch.Qm  Cm.Qh  Cm.Qm  (3 coordinates each)   |b'|^2 as its three pieces x 1
+//         MFMA 2:  Ch.Ql  Cl.Qh
+//     i.e. every piece product of weight >= 2^-16; each product of two bfloat16 is exact in fp32.  Rows = candidates,
+//     columns = queries, so a lane's 16 accumulator registers are 16 candidates of ITS query and the minimum is taken in
+//     the lane.  The instruction runs on its own pipe: vector instructions of the same wave overlap it.
+//   * First pass, per query: the three best UNIT scores (a unit = the 32 rows of two consecutive tiles that one lane half
+//     holds) and the units of the first two.  Afterwards the 64 candidates of the two best units are evaluated with the
+//     reference's un-fused arithmetic (first index of the exact minimum wins).
+//   * Error budget, in units of 2^-24 R with R = (|a'| + max_j |b'_j|)^2.  What a score can be off the exact
+//     |b'|^2 - 2 a'.b' of the centred fp32 values: the dropped pieces (m.l, l.m, l.l: <= 2^-22 |a'||b'|: 1 unit), the
+//     rounding of |b'|^2 itself (3 units), and the accumulation inside the two MFMAs -- 21 non-zero terms and the carried
+//     sum, charged with ONE FULL ULP of R per K-slot (truncating alignment, 2 units each: 64 units), far above what the
+//     hardware shows (tests/test_00_ops_gpu.py::test_nn_distance_split_score_error measures <= 4 units).  The translation
+//     by the centre moves a squared distance by <= 4 * 2^-24 * sqrt(R d^2) (4 units), and the reference's own value is
+//     within 8 * 2^-24 * d^2 of the true one (4 units).  Two candidates whose scores differ by more than
+//     2 * (1 + 3 + 64 + 4 + 4) = 152 units are therefore ordered the same way by the reference; the margin is
+//     M = 160 * 2^-24 * R (~1e-6 of R against neighbour gaps of 1e-4 R) plus an absolute floor of 1e-36.
+//   * Three exits per query:
+//       decided      s3 > s1 + M: no third unit can hold a candidate that is as near in the reference's arithmetic, the
+//                    exact minimum over the two best units is the answer.
+//       second pass  three units within the margin, finite numbers, and many such queries in the workgroup: another pass
+//                    over the scores evaluates exactly every candidate whose score is at most s1 + M -- nothing else can be
+//                    as near -- where it turns up (a tile whose minimum lies above the threshold costs its two MFMAs and the
+//                    minimum).  Clouds with DUPLICATED candidates take it for every query: the reference's own training
+//                    targets are the visible points padded with random re-draws (utils/hidden_point_removal.py:38-40), so
+//                    the nearest target point of a query sits in two to four units with bitwise equal scores.
+//       full scan    non-finite scores (overflow, NaN: every comparison false), or a stray undecided query (random clouds:
+//                    about one in 10^4): the query's wave evaluates all candidates exactly, its 64 lanes sharing them.
+// Results are the reference's bit for bit.  How the kernel got here -- the fp32 score form (v_mfma_f32_32x32x2_f32, margin
+// 32 units) that round 5 replaced, the measurements, the stale-read bug behind the inline-assembly minima -- is in
+// profiles/notes_chamfer_r5.md; the fp32 form itself is kept as profiles/r05_chamfer_fp32_scores_retired.diff.
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 nf_bf16x8 __attribute__((ext_vector_type(8)));
 
@@ -271,9 +264,10 @@ __device__ __forceinline__ void nf_split_candidate(float x, float y, float z, fl
 __device__ __forceinline__ void nf_split_query(float ax, float ay, float az, int half, nf_bf16x8 &b1, nf_bf16x8 &b2)
 {
     __bf16 xh, xm, xl, yh, ym, yl, zh, zm, zl;
-    nf_split3(-2.0f * ax, xh, xm, xl);
-    nf_split3(-2.0f * ay, yh, ym, yl);
-    nf_split3(-2.0f * az, zh, zm, zl);
+    const float sx = -2.0f * ax, sy = -2.0f * ay, sz = -2.0f * az;
+    nf_split3(sx, xh, xm, xl);
+    nf_split3(sy, yh, ym, yl);
+    nf_split3(sz, zh, zm, zl);
     const __bf16 one = (__bf16)1.0f, zero = (__bf16)0.0f;
     b1 = half ? nf_bf16x8{zh, xm, ym, zm, one, one, one, zero} : nf_bf16x8{xh, yh, zh, xm, ym, zm, xh, yh};
     b2 = half ? nf_bf16x8{zero, zero, zero, zero, zero, zero, zero, zero} : nf_bf16x8{xl, yl, zl, xh, yh, zh, zero, zero};
@@ -283,8 +277,11 @@ constexpr int NF_QT = 2;            // query tiles (32 queries each) per wave (4
                                     // [32,4096]^2 and 186 us at [32,16384]x[32,1024]; 2: 109 VGPRs, four waves: 111 / 149 us; 1: 115 us)
 constexpr int NF_WAVES = 4;
 constexpr int NF_QBLOCK = NF_WAVES * NF_QT * 32;   // queries per workgroup
-constexpr int NF_CHUNK = 2048;      // candidates per LDS chunk: 64 tiles x 64 lanes x 8 bytes = 32 KiB
-constexpr int NF_CHUNK_SPLIT = 1024; // the split form stages 48 bytes per candidate: 32 tiles x (64 + 32) lanes x 16 bytes = 48 KiB
+constexpr int NF_CHUNK = 1024;      // candidates per LDS chunk, 48 bytes each: 32 tiles x (64 + 32) lanes x 16 bytes = 48 KiB
+// Granularity of a candidate range: a direction whose candidates are cut over several workgroups is cut at multiples of this.
+// The host (splits_of: how many ranges a direction can have) and the kernel (where range `part` begins) both derive the cut
+// from this one constant, so they agree on it.
+constexpr int NF_RANGE_STEP = 2048;
 
 __device__ __forceinline__ bool key_less(unsigned d, int i, unsigned bd, int bi)
 {
@@ -342,26 +339,44 @@ struct NfTop {
     }
 };
 
-template <bool SPLIT>
+// The two MFMAs of a score tile.  These two functions are the only places the instruction is written: the search kernel and
+// the development entry below (nn_split_scores_kernel) both go through them.
+__device__ __forceinline__ f32x16 nf_mfma_first(nf_bf16x8 A1, nf_bf16x8 B1)
+{
+    f32x16 zero;
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        zero[r] = 0.0f;
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1, B1, zero, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 nf_mfma_second(nf_bf16x8 A2, nf_bf16x8 B2, f32x16 acc)
+{
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(A2, B2, acc, 0, 0, 0);
+}
+// k = 8 .. 15 of MFMA 2: nothing
+__device__ __forceinline__ nf_bf16x8 nf_zero8()
+{
+    return nf_bf16x8{(__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f};
+}
+
 __global__ __launch_bounds__(NF_WAVES * 64, 2) void nn_distance_filter_kernel(
     int n, int m, const float *__restrict__ xyz1, const float *__restrict__ xyz2,
     float *__restrict__ dist1, int *__restrict__ idx1, float *__restrict__ dist2,
     int *__restrict__ idx2, int blocks1, int split1, int split2, unsigned long long *__restrict__ keys1,
     unsigned long long *__restrict__ keys2, const long long *__restrict__ count2)
 {
-    // split > 1: the candidates of that direction are cut into `split` ranges (multiples of NF_CHUNK), one
+    // split > 1: the candidates of that direction are cut into `split` ranges (multiples of NF_RANGE_STEP), one
     // workgroup per (query block, range); every range delivers its exact first-index minimum and the ranges meet
     // in keys[] = min over (distance bits << 32 | index) -- squared distances are >= +0, so their bit patterns
     // order like the values, and equal distances resolve to the lower index, the reference's first-wins rule.
     // A cloud pair of very unequal sizes (the reference's own benchmark: 16384 x 1024 points) otherwise leaves
     // the few workgroups that own the short side's queries scanning the whole long side alone.
-    constexpr int CHUNK = SPLIT ? NF_CHUNK_SPLIT : NF_CHUNK;
-    // fp32 form: float2 per lane and tile; split form: the A operands of MFMA 1 (64 lanes) and of MFMA 2 (its k = 8 .. 15
-    // are zeros: 32 lanes), 16 bytes each.  (+1 tile: the pipeline reads one ahead)
-    __shared__ __attribute__((aligned(16))) char cand_raw[SPLIT ? (CHUNK / 32 + 1) * 96 * 16 : (CHUNK / 32 + 1) * 64 * 8];
-    float2v (*cand)[64] = reinterpret_cast<float2v (*)[64]>(cand_raw);
+
+    // LDS: per tile the A operands of MFMA 1 (64 lanes) and of MFMA 2 (its k = 8 .. 15 are zeros: 32 lanes), 16 bytes each.
+    // (+1 tile: the pipeline reads one ahead)
+    __shared__ __attribute__((aligned(16))) char cand_raw[(NF_CHUNK / 32 + 1) * 96 * 16];
     nf_bf16x8 (*cand2)[32] = reinterpret_cast<nf_bf16x8 (*)[32]>(cand_raw);
-    nf_bf16x8 (*cand1)[64] = reinterpret_cast<nf_bf16x8 (*)[64]>(cand_raw + (CHUNK / 32 + 1) * 32 * 16);
+    nf_bf16x8 (*cand1)[64] = reinterpret_cast<nf_bf16x8 (*)[64]>(cand_raw + (NF_CHUNK / 32 + 1) * 32 * 16);
     __shared__ float bmax_s[NF_WAVES];
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -385,7 +400,7 @@ __global__ __launch_bounds__(NF_WAVES * 64, 2) void nn_distance_filter_kernel(
     if (blk * NF_QBLOCK >= nq)
         return;                                         // (a query block of copies only)
     // this workgroup's candidate range
-    const int range = ((nc + split - 1) / split + NF_CHUNK - 1) / NF_CHUNK * NF_CHUNK;     // (the host's cut: multiples of NF_CHUNK)
+    const int range = ((nc + split - 1) / split + NF_RANGE_STEP - 1) / NF_RANGE_STEP * NF_RANGE_STEP;     // (the host's cut)
     const int cbeg = min(part * range, nc), cend = min(cbeg + range, nc);
     if (cbeg >= cend)
         return;                                         // (an empty trailing range)
@@ -393,8 +408,8 @@ __global__ __launch_bounds__(NF_WAVES * 64, 2) void nn_distance_filter_kernel(
     const float cx = to[0], cy = to[1], cz = to[2];
     // whole quads of candidates can be read as three 16-byte pieces (rows of 12 bytes: every fourth row starts one)
     const bool to_quads = ((uintptr_t)to & 15) == 0 && (sc & 3) == 0;
-    float qx[NF_QT], qy[NF_QT], qz[NF_QT], b0[NF_QT], b1[NF_QT], a2[NF_QT];
-    nf_bf16x8 B1[NF_QT], B2[NF_QT];      // split form: the B operands (this lane's k = 8 half .. 8 half + 7)
+    float qx[NF_QT], qy[NF_QT], qz[NF_QT], a2[NF_QT];
+    nf_bf16x8 B1[NF_QT], B2[NF_QT];      // the B operands (this lane's k = 8 half .. 8 half + 7)
     NfTop top[NF_QT];
 #pragma unroll
     for (int q = 0; q < NF_QT; ++q) {
@@ -404,65 +419,29 @@ __global__ __launch_bounds__(NF_WAVES * 64, 2) void nn_distance_filter_kernel(
         qz[q] = from[3 * (size_t)j + 2];
         const float ax = qx[q] - cx, ay = qy[q] - cy, az = qz[q] - cz;
         a2[q] = ax * ax + ay * ay + az * az;
-        b0[q] = half ? -2.0f * ay : -2.0f * ax;
-        b1[q] = half ? 1.0f : -2.0f * az;
-        if (SPLIT)
-            nf_split_query(ax, ay, az, half, B1[q], B2[q]);
+        nf_split_query(ax, ay, az, half, B1[q], B2[q]);
         top[q].init();
     }
 
-    // split form, in halves (the first pass interleaves the digest of the other accumulator pair with the second half)
+    // the two MFMAs of a tile separately (the first pass interleaves the digest of the other accumulator pair with the second half)
     auto issue_first = [&](f32x16 (&acc)[NF_QT], int t) {
         const nf_bf16x8 A1 = cand1[t][lane];
 #pragma unroll
-        for (int q = 0; q < NF_QT; ++q) {
-            f32x16 zero;
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                zero[r] = 0.0f;
-            acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1, B1[q], zero, 0, 0, 0);
-        }
+        for (int q = 0; q < NF_QT; ++q)
+            acc[q] = nf_mfma_first(A1, B1[q]);
     };
     auto issue_second = [&](f32x16 (&acc)[NF_QT], int t) {
         nf_bf16x8 A2 = cand2[t][c32];
         if (half)
-            A2 = nf_bf16x8{(__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f};
+            A2 = nf_zero8();
 #pragma unroll
         for (int q = 0; q < NF_QT; ++q)
-            acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A2, B2[q], acc[q], 0, 0, 0);
+            acc[q] = nf_mfma_second(A2, B2[q], acc[q]);
     };
     // scores of one candidate tile for the wave's NF_QT query tiles: 2 MFMAs each
     auto issue = [&](f32x16 (&acc)[NF_QT], int t) {
-        if (SPLIT) {
-            const nf_bf16x8 A1 = cand1[t][lane];
-            nf_bf16x8 A2 = cand2[t][c32];
-            if (half)
-                A2 = nf_bf16x8{(__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f};
-#pragma unroll
-            for (int q = 0; q < NF_QT; ++q) {
-                f32x16 zero;
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    zero[r] = 0.0f;
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1, B1[q], zero, 0, 0, 0);
-            }
-#pragma unroll
-            for (int q = 0; q < NF_QT; ++q)
-                acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A2, B2[q], acc[q], 0, 0, 0);
-            return;
-        }
-        const float2v A = cand[t][lane];
-#pragma unroll
-        for (int q = 0; q < NF_QT; ++q) {
-            f32x16 zero;
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                zero[r] = 0.0f;
-            acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(A.x, b0[q], zero, 0, 0, 0);
-        }
-#pragma unroll
-        for (int q = 0; q < NF_QT; ++q)
-            acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(A.y, b1[q], acc[q], 0, 0, 0);
+        issue_first(acc, t);
+        issue_second(acc, t);
     };
     // one chunk of candidates into LDS as MFMA A operands (lane r of a tile: row r; padding rows never win)
     float bmax2 = 0.0f;
@@ -478,17 +457,11 @@ __global__ __launch_bounds__(NF_WAVES * 64, 2) void nn_distance_filter_kernel(
                 if (track)
                     bmax2 = fmaxf(bmax2, bb);
             }
-            if (SPLIT) {
-                nf_bf16x8 lo, hi, lo2;
-                nf_split_candidate(x, y, z, bb, !(k < cnt), lo, hi, lo2);
-                cand1[k >> 5][k & 31] = lo;
-                cand1[k >> 5][32 + (k & 31)] = hi;
-                cand2[k >> 5][k & 31] = lo2;
-            } else {
-                // MFMA A operand: lane r holds k = 0 of row r, lane 32 + r holds k = 1
-                cand[k >> 5][k & 31] = float2v{x, z};
-                cand[k >> 5][32 + (k & 31)] = float2v{y, bb};
-            }
+            nf_bf16x8 lo, hi, lo2;
+            nf_split_candidate(x, y, z, bb, !(k < cnt), lo, hi, lo2);
+            cand1[k >> 5][k & 31] = lo;
+            cand1[k >> 5][32 + (k & 31)] = hi;
+            cand2[k >> 5][k & 31] = lo2;
         }
     };
     // The digest of a tile (8 v_min3 per query tile; the insertion into the top three once per PAIR of
@@ -496,8 +469,8 @@ __global__ __launch_bounds__(NF_WAVES * 64, 2) void nn_distance_filter_kernel(
     // (78 us at B=32, 4096^2, 70 % of the pipe) PLUS the VALU time whether the two are interleaved by
     // hand, left to two waves per SIMD, or both -- so the VALU work is what gets minimised.
     float run[NF_QT];
-    for (int c0 = cbeg; c0 < cend; c0 += CHUNK) {
-        const int cnt = min(CHUNK, cend - c0);
+    for (int c0 = cbeg; c0 < cend; c0 += NF_CHUNK) {
+        const int cnt = min(NF_CHUNK, cend - c0);
         const int padded = (cnt + 31) & ~31;
         __syncthreads();
         stage(c0, cnt, padded, true);
@@ -505,43 +478,30 @@ __global__ __launch_bounds__(NF_WAVES * 64, 2) void nn_distance_filter_kernel(
         const int ntile = padded >> 5, t0 = c0 >> 5;
         f32x16 accA[NF_QT], accB[NF_QT];
         issue(accA, 0);
-        if (SPLIT)
-            __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
         for (int t = 0; t < ntile; t += 2) {
-            if (SPLIT) {
-                // nf_min3 is inline assembly, which the compiler's hazard recogniser does not see: it neither counts the
-                // wait states an XDL result needs before a vector instruction may read it (v_mfma_f32_32x32x16_bf16: 11)
-                // nor keeps its scheduler from putting the v_min3 of an accumulator right behind the MFMA that writes it
-                // -- which it did: stale reads, a few wrong answers per thousand, different in every launch.  (The fp32
-                // matrix instruction of the other form is not an XDL operation and is interlocked.)  The order is pinned
-                // in four groups; inside a group the scheduler is free, and what a group reads was written at least one
-                // whole group of NF_QT independent MFMAs (>= 64 cycles) earlier:
-                //   1  first MFMAs of B          2  second MFMAs of B  |  minima of A (last written in group 4)
-                //   3  first MFMAs of the next A  4  second MFMAs of A  |  minima of B (last written in group 2), push
-                issue_first(accB, t + 1);       // (tile ntile is all padding: inf scores)
-                __builtin_amdgcn_sched_barrier(0);
-                issue_second(accB, t + 1);
-#pragma unroll
-                for (int q = 0; q < NF_QT; ++q)
-                    run[q] = nf_min16(__builtin_inff(), accA[q]);
-                __builtin_amdgcn_sched_barrier(0);
-                issue_first(accA, min(t + 2, ntile));
-                __builtin_amdgcn_sched_barrier(0);
-                issue_second(accA, min(t + 2, ntile));
-#pragma unroll
-                for (int q = 0; q < NF_QT; ++q)
-                    top[q].push(nf_min16(run[q], accB[q]), (t0 + t) >> 1);
-                __builtin_amdgcn_sched_barrier(0);
-                continue;
-            }
-            issue(accB, t + 1);             // (tile ntile is all padding: inf scores)
+            // nf_min3 is inline assembly, which the compiler's hazard recogniser does not see: it neither counts the
+            // wait states an XDL result needs before a vector instruction may read it (v_mfma_f32_32x32x16_bf16: 11)
+            // nor keeps its scheduler from putting the v_min3 of an accumulator right behind the MFMA that writes it
+            // -- which it did: stale reads, a few wrong answers per thousand, different in every launch.  The order is
+            // pinned in four groups; inside a group the scheduler is free, and what a group reads was written at least
+            // one whole group of NF_QT independent MFMAs (>= 64 cycles) earlier:
+            //   1  first MFMAs of B          2  second MFMAs of B  |  minima of A (last written in group 4)
+            //   3  first MFMAs of the next A  4  second MFMAs of A  |  minima of B (last written in group 2), push
+            issue_first(accB, t + 1);       // (tile ntile is all padding: inf scores)
+            __builtin_amdgcn_sched_barrier(0);
+            issue_second(accB, t + 1);
 #pragma unroll
             for (int q = 0; q < NF_QT; ++q)
                 run[q] = nf_min16(__builtin_inff(), accA[q]);
-            issue(accA, min(t + 2, ntile));
+            __builtin_amdgcn_sched_barrier(0);
+            issue_first(accA, min(t + 2, ntile));
+            __builtin_amdgcn_sched_barrier(0);
+            issue_second(accA, min(t + 2, ntile));
 #pragma unroll
             for (int q = 0; q < NF_QT; ++q)
                 top[q].push(nf_min16(run[q], accB[q]), (t0 + t) >> 1);
+            __builtin_amdgcn_sched_barrier(0);
         }
     }
 
@@ -577,7 +537,7 @@ __global__ __launch_bounds__(NF_WAVES * 64, 2) void nn_distance_filter_kernel(
         const float r = sqrtf(a2[q]) + rb;
         // (+ an absolute floor: below ~1e-37 the matrix cores may flush denormal terms, so relative bounds
         // mean nothing there and such clouds always take the full scan)
-        const float margin = (SPLIT ? 160.0f : 32.0f) * 5.9604645e-8f * (r * r) + 1e-36f;
+        const float margin = 160.0f * 5.9604645e-8f * (r * r) + 1e-36f;
         // only the two best units can hold a candidate within the margin of the best score?
         const bool decided = g.s3 > g.s1 + margin;      // false for NaN / overflow as well
 
@@ -666,8 +626,8 @@ __global__ __launch_bounds__(NF_WAVES * 64, 2) void nn_distance_filter_kernel(
                 theta[q] = -__builtin_inff();
             }
         } else {
-            for (int c0 = cbeg; c0 < cend; c0 += CHUNK) {
-                const int cnt = min(CHUNK, cend - c0);
+            for (int c0 = cbeg; c0 < cend; c0 += NF_CHUNK) {
+                const int cnt = min(NF_CHUNK, cend - c0);
                 const int padded = (cnt + 31) & ~31;
                 __syncthreads();
                 stage(c0, cnt, padded, false);
@@ -676,11 +636,9 @@ __global__ __launch_bounds__(NF_WAVES * 64, 2) void nn_distance_filter_kernel(
                 for (int t = 0; t < ntile; ++t) {
                     f32x16 acc[NF_QT];
                     issue(acc, t);              // the same instructions on the same operands: the same scores
-                    if (SPLIT) {                // (the wait states of the XDL results, by hand: see the first pass)
-                        __builtin_amdgcn_sched_barrier(0);
-                        asm volatile("s_nop 15");
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
+                    __builtin_amdgcn_sched_barrier(0);      // (the wait states of the XDL results, by hand: see the first pass)
+                    asm volatile("s_nop 15");
+                    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int q = 0; q < NF_QT; ++q) {
                         const float tm = nf_min16(__builtin_inff(), acc[q]);
@@ -771,7 +729,7 @@ __global__ __launch_bounds__(NF_WAVES * 64, 2) void nn_distance_filter_kernel(
 }
 
 // Development / test entry (cloudaae_dev_nn_split_scores): the split scores of up to 32 queries against up to 32 candidates,
-// built by the SAME operand functions and MFMAs as nn_distance_filter_kernel<true>, next to R = (|a'| + max |b'|)^2 per
+// built by the operand functions and the two MFMA functions of nn_distance_filter_kernel, next to R = (|a'| + max |b'|)^2 per
 // query -- what tests/test_00_ops_gpu.py compares with float64 to show how far inside the margin's accumulation charge
 // the hardware stays.
 __global__ __launch_bounds__(64) void nn_split_scores_kernel(int nq, int nc, const float *__restrict__ from,
@@ -788,13 +746,8 @@ __global__ __launch_bounds__(64) void nn_split_scores_kernel(int nq, int nc, con
     nf_split_candidate(c32 < nc ? x : 0.0f, c32 < nc ? y : 0.0f, c32 < nc ? z : 0.0f, bb, !(c32 < nc), a1lo, a1hi, a2lo);
     const float ax = from[3 * jq] - cx, ay = from[3 * jq + 1] - cy, az = from[3 * jq + 2] - cz;
     nf_split_query(ax, ay, az, half, b1, b2);
-    const nf_bf16x8 zero8 = {(__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f};
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r)
-        acc[r] = 0.0f;
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(half ? a1hi : a1lo, b1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(half ? zero8 : a2lo, b2, acc, 0, 0, 0);
+    f32x16 acc = nf_mfma_first(half ? a1hi : a1lo, b1);
+    acc = nf_mfma_second(half ? nf_zero8() : a2lo, b2, acc);
     float bmax = c32 < nc ? bb : 0.0f;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1)
@@ -1072,18 +1025,19 @@ static int nn_distance_impl(const char *name, int b, int n, const float *xyz1, i
     bool filter = n >= 512 && m >= 512 && (long long)b * ((long long)n + m) >= 64 * NF_QBLOCK;
     if (CLOUDAAE_KNOB_SET("CLOUDAAE_NN_FILTER"))
         filter = CLOUDAAE_KNOB("CLOUDAAE_NN_FILTER", 0) != 0 && n > 0 && m > 0;
+    unsigned long long *keys = nullptr;     // (filter kernel, split candidates) scratch of the call, stream ordered
     if (filter) {
         const int t1 = ceil_div(n, NF_QBLOCK), t2 = ceil_div(m, NF_QBLOCK);
         // A direction with fewer query blocks than the chip has CUs and many candidates (clouds of unequal size) is
-        // cut over its candidates until it has ~4 workgroups per CU, ranges no shorter than one LDS chunk.
+        // cut over its candidates until it has ~4 workgroups per CU, ranges no shorter than NF_RANGE_STEP.
         // (Measured at [32,4096]^2, 256 query blocks per direction: two ranges 152 us, one 117 us -- the fixed
         // cost per workgroup, 64 exact evaluations per query, doubles; [32,16384]x[32,1024]: 365 -> 199 us.)
         auto splits_of = [&](int tq, int nc) {
             int sp = 1;
-            if ((long long)tq * b < 256 && nc >= 2 * NF_CHUNK) {
+            if ((long long)tq * b < 256 && nc >= 2 * NF_RANGE_STEP) {
                 sp = (int)(1024 / ((long long)tq * b));
-                if (sp > nc / NF_CHUNK)
-                    sp = nc / NF_CHUNK;
+                if (sp > nc / NF_RANGE_STEP)
+                    sp = nc / NF_RANGE_STEP;
                 if (sp < 1)
                     sp = 1;
             }
@@ -1092,17 +1046,15 @@ static int nn_distance_impl(const char *name, int b, int n, const float *xyz1, i
             return sp;
         };
         const int s1 = splits_of(t1, m), s2 = splits_of(t2, n);
-        unsigned long long *keys = nullptr, *k1 = nullptr, *k2 = nullptr;
+        unsigned long long *k1 = nullptr, *k2 = nullptr;
         const size_t c1 = s1 > 1 ? (size_t)b * n : 0, c2 = s2 > 1 ? (size_t)b * m : 0;
-        if (c1 + c2 > 0) {      // scratch of the call, stream ordered: no state outlives it
+        if (c1 + c2 > 0) {      // (no state outlives the call)
             CLOUDAAE_CHECK_HIP(scratch_alloc((void **)&keys, (c1 + c2) * sizeof(unsigned long long), s), name);
             CLOUDAAE_CHECK_HIP(hipMemsetAsync(keys, 0xff, (c1 + c2) * sizeof(unsigned long long), s), name);
             k1 = keys;
             k2 = keys + c1;
         }
-        // scores on the bf16 matrix pipe (three-piece split, round 5; <false>, the fp32 matrix instruction of round 4, is
-        // no longer instantiated: profiles/notes_chamfer_r5.md has the A/B)
-        hipLaunchKernelGGL(nn_distance_filter_kernel<true>, dim3(t1 * s1 + t2 * s2, b), dim3(NF_WAVES * 64), 0, s, n, m, xyz1,
+        hipLaunchKernelGGL(nn_distance_filter_kernel, dim3(t1 * s1 + t2 * s2, b), dim3(NF_WAVES * 64), 0, s, n, m, xyz1,
                            xyz2, dist1, idx1, dist2, idx2, t1 * s1, s1, s2, k1, k2, count2);
         if (c1)
             hipLaunchKernelGGL(nn_distance_unpack_kernel, dim3(ceil_div((long long)c1, 256)), dim3(256), 0, s,
@@ -1110,33 +1062,29 @@ static int nn_distance_impl(const char *name, int b, int n, const float *xyz1, i
         if (c2)
             hipLaunchKernelGGL(nn_distance_unpack_kernel, dim3(ceil_div((long long)c2, 256)), dim3(256), 0, s,
                                (long long)c2, k2, dist2, idx2);
-        if (count2 != nullptr && m > 0)
-            hipLaunchKernelGGL(nn_distance_expand_kernel, dim3(ceil_div(m, 256), b), dim3(256), 0, s, m, count2, row_src2, xyz2,
-                               CLOUDAAE_KNOB("CLOUDAAE_NN_PREFIX_VERIFY", 0), dist2, idx2);
-        CLOUDAAE_CHECK_LAUNCH(name);
-        if (keys != nullptr)
-            CLOUDAAE_CHECK_HIP(hipFreeAsync(keys, s), name);
-        return 0;
+    } else {
+        // queries per lane: enough workgroups to fill 256 CUs first, then amortise
+        // LDS reads over more queries
+        const long long total = (long long)b * ((long long)n + m);
+        int Q = total >= 4LL * 256 * 1024 ? 4 : (total >= 256LL * 1024 ? 2 : 1);
+        const int t1 = ceil_div(n, NN_THREADS * Q), t2 = ceil_div(m, NN_THREADS * Q);
+        dim3 grid(t1 + t2, b), block(NN_THREADS);
+        if (Q == 4)
+            hipLaunchKernelGGL(nn_distance_kernel<4>, grid, block, 0, s, n, m, xyz1, xyz2, dist1, idx1,
+                               dist2, idx2, t1, count2);
+        else if (Q == 2)
+            hipLaunchKernelGGL(nn_distance_kernel<2>, grid, block, 0, s, n, m, xyz1, xyz2, dist1, idx1,
+                               dist2, idx2, t1, count2);
+        else
+            hipLaunchKernelGGL(nn_distance_kernel<1>, grid, block, 0, s, n, m, xyz1, xyz2, dist1, idx1,
+                               dist2, idx2, t1, count2);
     }
-    // queries per lane: enough workgroups to fill 256 CUs first, then amortise
-    // LDS reads over more queries
-    const long long total = (long long)b * ((long long)n + m);
-    int Q = total >= 4LL * 256 * 1024 ? 4 : (total >= 256LL * 1024 ? 2 : 1);
-    const int t1 = ceil_div(n, NN_THREADS * Q), t2 = ceil_div(m, NN_THREADS * Q);
-    dim3 grid(t1 + t2, b), block(NN_THREADS);
-    if (Q == 4)
-        hipLaunchKernelGGL(nn_distance_kernel<4>, grid, block, 0, s, n, m, xyz1, xyz2, dist1, idx1,
-                           dist2, idx2, t1, count2);
-    else if (Q == 2)
-        hipLaunchKernelGGL(nn_distance_kernel<2>, grid, block, 0, s, n, m, xyz1, xyz2, dist1, idx1,
-                           dist2, idx2, t1, count2);
-    else
-        hipLaunchKernelGGL(nn_distance_kernel<1>, grid, block, 0, s, n, m, xyz1, xyz2, dist1, idx1,
-                           dist2, idx2, t1, count2);
     if (count2 != nullptr && m > 0)
         hipLaunchKernelGGL(nn_distance_expand_kernel, dim3(ceil_div(m, 256), b), dim3(256), 0, s, m, count2, row_src2, xyz2,
-                               CLOUDAAE_KNOB("CLOUDAAE_NN_PREFIX_VERIFY", 0), dist2, idx2);
+                           CLOUDAAE_KNOB("CLOUDAAE_NN_PREFIX_VERIFY", 0), dist2, idx2);
     CLOUDAAE_CHECK_LAUNCH(name);
+    if (keys != nullptr)
+        CLOUDAAE_CHECK_HIP(hipFreeAsync(keys, s), name);
     return 0;
 }
 
