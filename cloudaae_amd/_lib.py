@@ -138,6 +138,8 @@ _SIGNATURES = {
                                _P, _P, _P, _L, _P],
     "cloudaae_vsd_counts": [_I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _D, _I, _P, _P, _P, _P, _P, _P],
     "cloudaae_pose_max_dist": [_I, _I, _I, _P, _I, _L, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
+    "cloudaae_depth_normals": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "cloudaae_depth_sensor_noise": [_I, _I, _I, _P, _P, _P, _U, _U, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P, _P],
 }
 
 

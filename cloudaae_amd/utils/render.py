@@ -9,6 +9,7 @@ approximates visibility on 2048-point models by hidden point removal); nothing h
     tfrecord_io.write_records(path, frame_records(out['depth'], out['label'], intrinsics, poses, classes, 48, ids))
 
     python -m cloudaae_amd.utils.render --meshes DIR --out DIR --frames N --objects K --seq ID --seed S [--mesh_scale X]
+                                        [--sensor kinect1 --sensor_seed S]
 """
 import argparse
 import os
@@ -83,7 +84,8 @@ def render_instances(p, intr, offs, mesh, lab, poses, H, W, z_near=Z_NEAR, retur
     return depth, label, tri, counts, tb
 
 
-def render_frames(meshes, instances, intrinsics, height, width, z_near=Z_NEAR, return_tri=False, scale=1.0, device=None):
+def render_frames(meshes, instances, intrinsics, height, width, z_near=Z_NEAR, return_tri=False, scale=1.0, device=None,
+                  sensor=None, sensor_seed=0, first_frame=0):
     """F frames of height x width.  meshes: a PackedMeshes or what mesh_models.pack_meshes takes (`scale` applies then).
     instances: per frame a list of (mesh index, label in 1..255, pose); a frame may be empty.  pose: model -> camera, a
     4x4 array or a (rot, trans) pair (axis-angle [3], translation [3]).  intrinsics [F,5] float32: fx, fy, cx, cy,
@@ -92,7 +94,10 @@ def render_frames(meshes, instances, intrinsics, height, width, z_near=Z_NEAR, r
     reads class = label - 1) and, with return_tri, tri [F,H,W] int32 (the winning draw rank, -1 where empty), plus
     dropped, degenerate [J] int32 (numpy, one read-back: triangles left out because a vertex lay behind z_near or
     outside the guard band, or an index outside its mesh; triangles of zero screen area) and tri_base [J+1] (numpy: the
-    draw rank of triangle t of instance j is tri_base[j] + t)."""
+    draw rank of triangle t of instance j is tri_base[j] + t).  With `sensor` (a preset's name or the dict of
+    depth_noise.sensor_params) the depth sensor model of depth_noise.apply follows the resolve: depth and label are the
+    sensor's, clean_depth is the rendering, sensor_counts [F,4] int32 (device) its counts; frame f has the global index
+    first_frame + f under sensor_seed."""
     p = mesh_models.pack_meshes(meshes, scale, device)
     dev = p.device
     F = len(instances)
@@ -115,6 +120,10 @@ def render_frames(meshes, instances, intrinsics, height, width, z_near=Z_NEAR, r
     out = dict(depth=depth, label=label, dropped=host[0], degenerate=host[1], tri_base=tb)
     if return_tri:
         out['tri'] = tri
+    if sensor is not None:
+        from . import depth_noise
+        noisy = depth_noise.apply(depth, label, intr, sensor, seed=sensor_seed, first_frame=first_frame)
+        out.update(depth=noisy['depth'], label=noisy['label'], clean_depth=depth, sensor_counts=noisy['counts'])
     return out
 
 
@@ -203,6 +212,9 @@ def main(argv=None):
     parser.add_argument("--width", type=int, default=None, help="image size [default: the camera's, 640 x 480]")
     parser.add_argument("--height", type=int, default=None)
     parser.add_argument("--frames_per_launch", type=int, default=8)
+    parser.add_argument("--sensor", choices=["none", "kinect1"], default="none",
+                        help="depth sensor model applied to the rendered frames (utils/depth_noise.py) [default: none]")
+    parser.add_argument("--sensor_seed", type=int, default=0)
     parser.add_argument("--gpu", type=int, default=0)
     args = parser.parse_args(argv)
     from .. import tfrecord_io
@@ -223,7 +235,8 @@ def main(argv=None):
         hi = min(lo + max(args.frames_per_launch, 1), args.frames)
         intr = np.array([row] * (hi - lo), np.float32)
         inst = [[(int(c), int(c) + 1, poses[f, k]) for k, c in enumerate(classes[f])] for f in range(lo, hi)]
-        out = render_frames(packed, inst, intr, H, W)
+        sensor = dict(sensor=args.sensor, sensor_seed=args.sensor_seed, first_frame=lo) if args.sensor != "none" else {}
+        out = render_frames(packed, inst, intr, H, W, **sensor)
         dropped += int(out['dropped'].sum())
         payloads += frame_records(out['depth'], out['label'], intr, poses[lo:hi], classes[lo:hi], args.seq,
                                   list(range(lo, hi)))

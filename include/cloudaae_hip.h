@@ -51,7 +51,8 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * test entry); cloudaae_bn_backward_dx_bf16x3 and its two queries; cloudaae_pose_score, cloudaae_cloud_diameter (each with
  * a workspace query), cloudaae_pose_matrix and cloudaae_pose_stack; cloudaae_icp_point_to_plane and
  * cloudaae_estimate_normals with its workspace query; cloudaae_sample_poses and cloudaae_random_object_occluder;
- * cloudaae_vsd_counts and cloudaae_pose_max_dist with its workspace query. */
+ * cloudaae_vsd_counts and cloudaae_pose_max_dist with its workspace query; cloudaae_depth_normals and
+ * cloudaae_depth_sensor_noise. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -993,6 +994,45 @@ long long cloudaae_pose_max_dist_workspace_bytes(int b, int p, int smax);
 int cloudaae_pose_max_dist(int b, int p, int m, const float *model, int point_stride, long long cloud_stride,
                            const double *est, const double *gt, int smax, const int *num_sym, const double *sym,
                            const float *intrinsics, double *mssd, double *mspd, void *workspace, cloudaae_stream_t stream);
+
+/* ---- a depth sensor's noise on depth / label frames ("Sensor noise", has the definition) ---- */
+
+/* The slope at every pixel of f frames of h x w: depth [f,h,w] uint16 and label [f,h,w] uint8 as cloudaae_render_frames
+ * writes them, intrinsics [f,5] float (fx, fy, cx, cy, factor_depth).  All device memory.  In double, no fma:
+ * P(u, v) = (((u - cx) dm) / fx, ((v - cy) dm) / fy, dm), dm = d / factor_depth.  A neighbour is valid inside the image
+ * with depth != 0 and the pixel's label; along each axis the central difference P(+1) - P(-1), else the one-sided
+ * difference with the valid neighbour, else none.  A pixel with depth is flat (normal zeros, theta 0) when an axis has no
+ * difference or n = gx x gy has n . n = 0 or not finite; otherwise theta = acos(min(|n . ray| / (sqrt(n . n) sqrt(ray .
+ * ray)), 1)) with ray = P of the pixel, and the normal is n / sqrt(n . n) turned so that n . ray <= 0.
+ * Outputs: normals [f,h,w,3] float, theta [f,h,w] float (optional, may be NULL), both zeros where depth is 0;
+ * flat_counts [f] int (zeroed by the call): the flat pixels among those with depth.  A memset and one launch, integer
+ * atomics only.  Limits: f, h, w >= 1; h * w <= 2^24; f * h * w <= 2^28; outside them, or with a null pointer, the call
+ * returns an error and launches nothing. */
+int cloudaae_depth_normals(int f, int h, int w, const uint16_t *depth, const uint8_t *label, const float *intrinsics,
+                           float *normals, float *theta, int *flat_counts, cloudaae_stream_t stream);
+
+/* The sensor model on the same inputs; frame i of the launch has the global index first_frame + i (below 2^40).  Per
+ * destination pixel p = v w + u: (n_u, n_v) = normal2(r0, r1), (n_z, unused) = normal2(r2, r3) of philox4x32(seed,
+ * (first_frame + i) 2^24 + p, 21), the dropout word r0 of stream 22; floats widened to double, all later arithmetic in
+ * double without fma.  1. the source s = (clamp(u + rint(n_u sigma_l), 0, w - 1), clamp(v + rint(n_v sigma_l), 0, h - 1));
+ * label_out = label(s); depth(s) = 0 gives depth 0.  2. z = dm(s), theta = min(slope at s, theta_max), sigma_z =
+ * (a0 + a1 ((z - z0)(z - z0))) + ((a2 / sqrt(z)) (theta theta)) / ((pi/2 - theta)(pi/2 - theta)), z' = z + n_z sigma_z.
+ * 3. depth 0 when the unclamped theta > theta_drop, else when r0 < floor(p_drop 2^32).  4. with disparity_step > 0:
+ * k = rint(((fx baseline) / z') / disparity_step), k < 1 (or not a number) gives depth 0, z'' = (fx baseline) /
+ * (k disparity_step); else z'' = z'.  5. du = floor(z'' factor_depth + 0.5), depth 0 unless 1 <= du <= 65535.
+ * Outputs: depth_out [f,h,w] uint16, label_out [f,h,w] uint8 (neither may alias an input), counts [f,4] int (zeroed by
+ * the call): destination pixels whose own input depth is not 0; pixels dropped by the angle; by chance; lost in steps 4
+ * and 5 (each pixel with a source depth ends in exactly one of: kept, angle, chance, lost); z_noisy [f,h,w] double
+ * (optional, may be NULL): z' where the source has depth and z' is finite, else 0.  A memset and one launch, integer
+ * atomics only; the same (seed, global frame, p) gives the same pixel whatever f or the launch split.  Errors (nothing is
+ * launched): the limits of cloudaae_depth_normals; first_frame + f > 2^40; sigma_l < 0; theta_max outside [0, pi/2);
+ * p_drop outside [0, 1]; disparity_step < 0; a non-finite parameter; a null pointer.  factor_depth lives in device
+ * memory and is not read by the host: a frame whose factor_depth is not > 0 comes out with depth 0 everywhere. */
+int cloudaae_depth_sensor_noise(int f, int h, int w, const uint16_t *depth, const uint8_t *label, const float *intrinsics,
+                                unsigned long long seed, unsigned long long first_frame, double sigma_l, double a0, double a1,
+                                double z0, double a2, double theta_max, double theta_drop, double p_drop, double baseline,
+                                double disparity_step, uint16_t *depth_out, uint8_t *label_out, int *counts, double *z_noisy,
+                                cloudaae_stream_t stream);
 
 #ifdef __cplusplus
 }
