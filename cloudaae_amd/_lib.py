@@ -140,6 +140,9 @@ _SIGNATURES = {
     "cloudaae_pose_max_dist": [_I, _I, _I, _P, _I, _L, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
     "cloudaae_depth_normals": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "cloudaae_depth_sensor_noise": [_I, _I, _I, _P, _P, _P, _U, _U, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P, _P],
+    "cloudaae_frame_clouds": [_I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _U, _P, _P, _P, _P, _P, _L, _P],
+    "cloudaae_rendered_scene": [_I, _U, _U, _I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
+                                _P],
 }
 
 
@@ -358,6 +361,7 @@ def lib():
                        ("cloudaae_ragged_fps_workspace_bytes", [_L]),
                        ("cloudaae_mesh_weights_workspace_bytes", [_L]),
                        ("cloudaae_render_workspace_bytes", [_I, _I, _I, _I, _L, _L]),
+                       ("cloudaae_frame_clouds_workspace_bytes", [_I, _I, _I, _I, _I]),
                        ("cloudaae_pose_score_workspace_bytes", [_I, _I, _I]),
                        ("cloudaae_pose_max_dist_workspace_bytes", [_I, _I, _I]),
                        ("cloudaae_estimate_normals_workspace_bytes", [_I, _L]),

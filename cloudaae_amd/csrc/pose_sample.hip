@@ -113,6 +113,24 @@ PS_NOPK __global__ __launch_bounds__(64) void sample_poses_kernel(int b, unsigne
     }
 }
 
+// The object occluder of global sample g whose target lies at depth z: its class (the return value) and its centre c,
+// with the raw words r (centre) and q (class).  The one place of the rule: cloudaae_random_object_occluder and
+// cloudaae_rendered_scene both draw through it.
+PS_NOPK __device__ __forceinline__ int ps_occluder_draw(unsigned long long seed, unsigned long long g, const ClassList &classes,
+                                                        float z, float wnear, float hnear, float near_d, unsigned (&r)[4],
+                                                        unsigned (&q)[4], float (&c)[3])
+{
+    philox4x32(seed, g, PS_STREAM_OCC_CENTRE, r);
+    philox4x32(seed, g, PS_STREAM_OCC_CLASS, q);
+    float n0, n1, n2, n3;
+    normal2(r[0], r[1], n0, n1);
+    normal2(r[2], r[3], n2, n3);
+    c[0] = n0 * (wnear / 8.0f);
+    c[1] = n1 * (hnear / 8.0f);
+    c[2] = (near_d + z) / 2.0f + n2 * ((z - near_d) / 6.0f);
+    return classes.id[ps_pick(q[0], classes.n)];
+}
+
 // get_random_object_occluder (generate_occluder.py:5-35): one lane per (sample, point).  The centre and the class are
 // functions of the sample alone, so every lane of a sample derives the same ones.
 PS_NOPK __global__ __launch_bounds__(256) void object_occluder_kernel(int b, unsigned long long first, unsigned long long seed,
@@ -126,11 +144,10 @@ PS_NOPK __global__ __launch_bounds__(256) void object_occluder_kernel(int b, uns
     if (i >= b * per)
         return;
     const int cloud = i / per, j = i - cloud * per;
-    const unsigned long long g = first + (unsigned long long)cloud;
     unsigned r[4], q[4];
-    philox4x32(seed, g, PS_STREAM_OCC_CENTRE, r);
-    philox4x32(seed, g, PS_STREAM_OCC_CLASS, q);
-    const int cls = classes.id[ps_pick(q[0], classes.n)];
+    float c[3];
+    const int cls = ps_occluder_draw(seed, first + (unsigned long long)cloud, classes, trans[cloud * 3 + 2], wnear, hnear,
+                                     near_d, r, q, c);
     if (j == 0) {
         if (occ_class)
             occ_class[cloud] = (long long)cls;
@@ -142,13 +159,6 @@ PS_NOPK __global__ __launch_bounds__(256) void object_occluder_kernel(int b, uns
             }
         }
     }
-    const float z = trans[cloud * 3 + 2];
-    float n0, n1, n2, n3, c[3];
-    normal2(r[0], r[1], n0, n1);
-    normal2(r[2], r[3], n2, n3);
-    c[0] = n0 * (wnear / 8.0f);
-    c[1] = n1 * (hnear / 8.0f);
-    c[2] = (near_d + z) / 2.0f + n2 * ((z - near_d) / 6.0f);
     const float *p = models + ((size_t)cls * npts + j) * 6;
     const double *R = rot + (size_t)cloud * 9;
     // the dot product of transform_model_kernel (synth.hip): float32(R), left to right, un-fused
@@ -157,6 +167,74 @@ PS_NOPK __global__ __launch_bounds__(256) void object_occluder_kernel(int b, uns
         const float r0 = (float)R[3 * rr], r1 = (float)R[3 * rr + 1], r2 = (float)R[3 * rr + 2];
         const float a = p[0] * r0, bb = p[1] * r1, cc = p[2] * r2;
         occ[(size_t)i * 3 + rr] = ((a + bb) + cc) + c[rr];
+    }
+}
+
+// [R | t; 0 0 0 1], row-major: the model -> camera pose the renderer takes
+PS_NOPK __device__ __forceinline__ void ps_pose(const double *__restrict__ R, double tx, double ty, double tz,
+                                                double *__restrict__ out)
+{
+    const double t[3] = {tx, ty, tz};
+#pragma unroll
+    for (int rr = 0; rr < 3; ++rr) {
+        out[4 * rr + 0] = R[3 * rr + 0];
+        out[4 * rr + 1] = R[3 * rr + 1];
+        out[4 * rr + 2] = R[3 * rr + 2];
+        out[4 * rr + 3] = t[rr];
+    }
+    out[12] = 0.0, out[13] = 0.0, out[14] = 0.0, out[15] = 1.0;
+}
+
+// The scene of a rendered training batch ("Rendered training clouds"): one lane per sample writes the three
+// instances of its two frames.  Frame 2i holds instance 3i (the target alone); frame 2i + 1 holds 3i + 1 (the target
+// again) and 3i + 2 (the occluder: the class and the centre of ps_occluder_draw, under the sample's own rotation).  The
+// classes live on the device, so instance j's vertex and triangle ranks start at j * max_v and j * max_t; the renderer
+// treats the ranks past a mesh's own counts as absent.  A class outside mesh_index gives mesh -1: nothing is drawn.
+PS_NOPK __global__ __launch_bounds__(64) void rendered_scene_kernel(int b, unsigned long long first, unsigned long long seed,
+                                                                   ClassList classes, int nmodels,
+                                                                   const long long *__restrict__ class_id,
+                                                                   const int *__restrict__ mesh_index,
+                                                                   const double *__restrict__ rot, const float *__restrict__ trans,
+                                                                   float wnear, float hnear, float near_d, int max_v, int max_t,
+                                                                   int *__restrict__ inst_offsets, int *__restrict__ inst_mesh,
+                                                                   int *__restrict__ inst_label, double *__restrict__ inst_pose,
+                                                                   int *__restrict__ vert_base, int *__restrict__ tri_base,
+                                                                   long long *__restrict__ occ_class, float *__restrict__ occ_centre)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= b)
+        return;
+    unsigned r[4], q[4];
+    float c[3];
+    const float *t = trans + 3 * (size_t)i;
+    const int ocls = ps_occluder_draw(seed, first + (unsigned long long)i, classes, t[2], wnear, hnear, near_d, r, q, c);
+    const long long cls = class_id[i];
+    const int target = (cls >= 0 && cls < nmodels) ? mesh_index[cls] : -1;
+    const int occluder = mesh_index[ocls];         // (the class list was checked against nmodels by the host)
+    const double *R = rot + 9 * (size_t)i;
+    const int j = 3 * i;
+    inst_offsets[2 * i] = j;
+    inst_offsets[2 * i + 1] = j + 1;
+    inst_mesh[j] = target, inst_mesh[j + 1] = target, inst_mesh[j + 2] = occluder;
+    inst_label[j] = 1, inst_label[j + 1] = 1, inst_label[j + 2] = 2;
+    ps_pose(R, (double)t[0], (double)t[1], (double)t[2], inst_pose + 16 * (size_t)j);
+    ps_pose(R, (double)t[0], (double)t[1], (double)t[2], inst_pose + 16 * (size_t)(j + 1));
+    ps_pose(R, (double)c[0], (double)c[1], (double)c[2], inst_pose + 16 * (size_t)(j + 2));
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        vert_base[j + k] = (j + k) * max_v;
+        tri_base[j + k] = (j + k) * max_t;
+    }
+    occ_class[i] = (long long)ocls;
+    if (occ_centre) {
+        occ_centre[3 * i + 0] = c[0];
+        occ_centre[3 * i + 1] = c[1];
+        occ_centre[3 * i + 2] = c[2];
+    }
+    if (i == b - 1) {
+        inst_offsets[2 * b] = 3 * b;
+        vert_base[3 * b] = 3 * b * max_v;
+        tri_base[3 * b] = 3 * b * max_t;
     }
 }
 
@@ -230,6 +308,33 @@ CLOUDAAE_API int cloudaae_random_object_occluder(int b, unsigned long long first
     hipLaunchKernelGGL(object_occluder_kernel, dim3(ceil_div((long long)b * per, 256)), dim3(256), 0, (hipStream_t)stream, b,
                        first_index, seed, npts, models, list, rot_mat64, translation, per, wnear, hnear, near_dist, occluder,
                        occ_class, raw);
+    CLOUDAAE_CHECK_LAUNCH(name);
+    return 0;
+}
+
+CLOUDAAE_API int cloudaae_rendered_scene(int b, unsigned long long first_index, unsigned long long seed, int nmodels,
+                                         int n_classes, const int *classes, const long long *class_id, const int *mesh_index,
+                                         const double *rot_mat64, const float *translation, float wnear, float hnear,
+                                         float near_dist, int max_vertices, int max_triangles, int *inst_offsets,
+                                         int *inst_mesh, int *inst_label, double *inst_pose, int *inst_vert_base,
+                                         int *inst_tri_base, long long *occ_class, float *occ_centre, cloudaae_stream_t stream)
+{
+    const char *name = "cloudaae_rendered_scene";
+    CLOUDAAE_REQUIRE(b >= 1, name, "b must be >= 1");
+    CLOUDAAE_REQUIRE(max_vertices >= 1 && max_triangles >= 1, name, "max_vertices and max_triangles must be >= 1");
+    CLOUDAAE_REQUIRE(3ll * b * max_vertices <= 2147483647ll && 3ll * b * max_triangles <= 2147483647ll, name,
+                     "3 b max_vertices and 3 b max_triangles (the strided ranks) must lie below 2^31");
+    CLOUDAAE_REQUIRE(class_id && mesh_index && rot_mat64 && translation && inst_offsets && inst_mesh && inst_label &&
+                         inst_pose && inst_vert_base && inst_tri_base && occ_class,
+                     name, "null pointer");
+    ClassList list;
+    const char *bad = ps_class_list(n_classes, classes, nmodels, list);
+    CLOUDAAE_REQUIRE(bad == nullptr, name, bad);
+    CLOUDAAE_REQUIRE(isfinite(wnear) && isfinite(hnear) && isfinite(near_dist), name, "camera constants must be finite");
+    hipLaunchKernelGGL(rendered_scene_kernel, dim3(ceil_div(b, 64)), dim3(64), 0, (hipStream_t)stream, b, first_index, seed, list,
+                       nmodels, class_id, mesh_index, rot_mat64, translation, wnear, hnear, near_dist, max_vertices,
+                       max_triangles, inst_offsets, inst_mesh, inst_label, inst_pose, inst_vert_base, inst_tri_base, occ_class,
+                       occ_centre);
     CLOUDAAE_CHECK_LAUNCH(name);
     return 0;
 }

@@ -90,6 +90,13 @@ def get_training_argparser():
                        '(utils/mesh_models.py; class i is the i-th file in sorted order); with --poses sampled only')
     extra.add_argument('--mesh_scale', type=float, default=1.0,
                        help='factor on the mesh coordinates (0.001 for meshes in millimetres)')
+    extra.add_argument('--visibility', default='hpr', choices=['hpr', 'rendered'],
+                       help="hpr: hidden point removal on the sampled object models; rendered: clouds drawn from depth "
+                            "frames of the --meshes rendered behind a mesh occluder (utils/rendered_data.py); with --poses "
+                            "sampled and --meshes only [default: hpr]")
+    extra.add_argument('--sensor', default='none', choices=['none', 'kinect1'],
+                       help='depth sensor model on the rendered frames (utils/depth_noise.py); with --visibility rendered')
+    extra.add_argument('--sensor_seed', type=int, default=0, help='seed of the sensor noise')
     return parser
 
 
@@ -566,7 +573,7 @@ def transform_object_model(x):
 
 
 def get_small_data(records, obj_models, seed=0, rows=None, rows_org=None, occluder='spherical', dataset='ycbv',
-                   first_index=0, occluder_seed=None):
+                   first_index=0, occluder_seed=None, visibility='hpr', rendered=None):
     """:96-117 for one batch: records = dict of device tensors translation [B,3], axisangle [B,3],
     class_id [B] (e.g. from tfrecord_io.PoseRecords.epoch); returns the reference's element dict:
     visiblePoints [B,2449,3], visiblePoints_org [B,2049,3], occluder, model_xyz_rot_trans, ...
@@ -577,7 +584,22 @@ def get_small_data(records, obj_models, seed=0, rows=None, rows_org=None, occlud
     occluder: 'spherical' (two Gaussian blobs, 400 points) or 'object' (512 points of a class model rotated by the sample's
     rotation, generate_occluder.py:5-35: visiblePoints then has 2048 + 512 + 1 rows); dataset: the camera constants of
     either.  The object occluder of sample i is a function of (occluder_seed, first_index + i) -- occluder_seed defaults
-    to `seed`.  The defaults give what this function gave before it had these arguments, bit for bit."""
+    to `seed`.  The defaults give what this function gave before it had these arguments, bit for bit.
+    visibility: 'hpr' (the above) or 'rendered': the clouds come from rendered depth frames of the sample's mesh behind a
+    mesh occluder (utils/rendered_data.rendered_element, which `rendered` holds the keyword arguments of: packed_meshes,
+    num_point, and optionally mesh_index, sensor, sensor_seed, height, width, min_visible); the records must bring
+    rot_mat64 (sampled poses do), obj_models, rows, rows_org and occluder are not used, and the sample is a function of
+    (occluder_seed, first_index + i)."""
+    require(visibility in ('hpr', 'rendered'), "visibility must be 'hpr' or 'rendered'")
+    if visibility == 'rendered':
+        from .utils import rendered_data
+        require(rendered is not None and rendered.get('packed_meshes') is not None and rendered.get('num_point'),
+                "visibility='rendered' needs rendered=dict(packed_meshes=..., num_point=...)")
+        require(records.get('rot_mat64') is not None, "visibility='rendered' needs sampled poses (rot_mat64)")
+        kw = dict(rendered)
+        return rendered_data.rendered_element(records, kw.pop('packed_meshes'), kw.pop('mesh_index', None),
+                                              kw.pop('num_point'), seed if occluder_seed is None else occluder_seed,
+                                              first_index, dataset=dataset, **kw)
     from .utils import generate_occluder, hidden_point_removal as hpr
     require(occluder in ('spherical', 'object'), "occluder must be 'spherical' or 'object'")
     x = dict(records)
@@ -702,12 +724,15 @@ class ClassLossLog(object):
 
 
 def train_graph(graph, records, obj_models, epoch, class_log=None, log=None, logdir=None, seed=None,
-                max_batches=None, print_every=1, summary_every=1000, occluder='spherical', dataset='ycbv'):
+                max_batches=None, print_every=1, summary_every=1000, occluder='spherical', dataset='ycbv',
+                visibility='hpr', rendered=None):
     """One epoch of the reference's train_graph (:332-437): draw shuffled batches of pose records,
     synthesise the element on the GPU (get_small_data), train_step, per-class loss bookkeeping
     every `summary_every` batches, checkpoint at the end of the epoch (:418-424).
     `records` is this rank's tfrecord_io.PoseRecords shard, or a SampledPoses (poses drawn on the GPU: nothing is read
-    on the host or copied); obj_models the [21,2048,6] device tensor."""
+    on the host or copied); obj_models the [21,2048,6] device tensor.  visibility, rendered: get_small_data's ('rendered'
+    needs a SampledPoses)."""
+    require(visibility == 'hpr' or isinstance(records, SampledPoses), "visibility='rendered' needs sampled poses")
     start = time.time()
     dev = graph.device
     batch_idx = 0
@@ -720,7 +745,8 @@ def train_graph(graph, records, obj_models, epoch, class_log=None, log=None, log
         batch_seed = (epoch << 32) + batch_idx * graph.world + graph.rank
         if sampled:
             element = get_small_data(rec, obj_models, seed=batch_seed, occluder=occluder, dataset=dataset,
-                                     first_index=rec['first_index'], occluder_seed=records.seed)
+                                     first_index=rec['first_index'], occluder_seed=records.seed, visibility=visibility,
+                                     rendered=rendered)
         else:
             element = get_small_data({k: torch.as_tensor(v).to(dev, non_blocking=True) for k, v in rec.items()},
                                      obj_models, seed=batch_seed, occluder=occluder, dataset=dataset)
@@ -773,6 +799,10 @@ def main(argv=None):
     general, topts, hyper, extra = groups['general'], groups['training_options'], groups['hyperparameters'], groups['mi355x']
     if extra['meshes'] and extra['poses'] != 'sampled':
         parser.error("--meshes needs --poses sampled (pose records belong to the shipped object models)")
+    if extra['visibility'] == 'rendered' and not (extra['meshes'] and extra['poses'] == 'sampled'):
+        parser.error("--visibility rendered needs --poses sampled and --meshes (the frames are rendered from the meshes)")
+    if extra['sensor'] != 'none' and extra['visibility'] != 'rendered':
+        parser.error("--sensor needs --visibility rendered (there is no depth frame to apply it to otherwise)")
     world = int(os.environ.get('WORLD_SIZE', '1'))
     if world > 1:
         local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -817,13 +847,21 @@ def main(argv=None):
                                    num_models=obj_models.shape[0])
         else:
             obj_models, records = load_dataset(extra['data_dir'], graph.device, graph.rank, graph.world, classes=classes)
+        rendered = None
+        if extra['visibility'] == 'rendered':
+            from .utils import mesh_models
+            rendered = dict(packed_meshes=mesh_models.pack_meshes(mesh_models.mesh_files(extra['meshes']),
+                                                                  extra['mesh_scale'], graph.device),
+                            num_point=graph.NUM_POINT, sensor=None if extra['sensor'] == 'none' else extra['sensor'],
+                            sensor_seed=extra['sensor_seed'])
         log("%d pose records on rank 0, %d batches per epoch" % (len(records), len(records) // graph.local_batch))
         class_log = ClassLossLog(graph.device)
         for epoch in range(int(topts['max_epoch'])):
             log('**** EPOCH %03d ****' % epoch)
             train_graph(graph, records, obj_models, epoch, class_log, log, logdir, seed=123456789 + epoch,
                         max_batches=extra['steps'] or None, print_every=extra['print_every'],
-                        occluder=extra['occluder'], dataset=extra['dataset'])
+                        occluder=extra['occluder'], dataset=extra['dataset'], visibility=extra['visibility'],
+                        rendered=rendered)
         return
     el = synthetic_element(graph.local_batch, graph.NUM_POINT, graph.device, rank=graph.rank)
     t0 = time.time()

@@ -84,6 +84,41 @@ def render_instances(p, intr, offs, mesh, lab, poses, H, W, z_near=Z_NEAR, retur
     return depth, label, tri, counts, tb
 
 
+def render_instances_strided(p, intr, inst_offsets, inst_mesh, inst_label, poses, vert_base, tri_base, H, W, z_near=Z_NEAR,
+                             return_tri=False):
+    """render_instances for instance arrays that live on the device (cloudaae_rendered_scene writes them): inst_offsets
+    [F+1], inst_mesh, inst_label [J], vert_base, tri_base [J+1] int32 and poses [J,16] float64 device tensors, the bases
+    strided by the largest mesh of p -- vert_base[j] = j maxV, tri_base[j] = j maxT -- because the host does not know
+    which mesh an instance draws.  Ranks past a mesh's own counts are no triangle / an unusable vertex to the renderer.
+    -> (depth [F,H,W] int16, label uint8, tri int32 or None, counts [2,J] int32).  No read-back."""
+    dev = p.device
+    F, J, S = int(inst_offsets.shape[0]) - 1, int(inst_mesh.shape[0]), len(p.num_triangles)
+    require(F >= 1 and J >= 1, "no frame or no instance to draw")
+    require(tuple(intr.shape) == (F, 5) and tuple(poses.shape) == (J, 16), "intrinsics must be [F, 5] and poses [J, 16]")
+    require(int(inst_label.shape[0]) == J and int(vert_base.shape[0]) == J + 1 and int(tri_base.shape[0]) == J + 1,
+            "inst_label must be [J], vert_base and tri_base [J + 1]")
+    require(all(t.dtype == torch.int32 for t in (inst_offsets, inst_mesh, inst_label, vert_base, tri_base)) and
+            poses.dtype == torch.float64, "instance arrays must be int32 and poses float64")
+    sum_v, sum_t = J * int(np.max(p.num_vertices)), J * int(np.max(p.num_triangles))
+    L = _lib.lib()
+    nbytes = int(L.cloudaae_render_workspace_bytes(F, H, W, J, sum_v, sum_t))
+    require(nbytes > 0, "outside the renderer's limits: H W <= 2^24, F H W <= 2^28, fewer than 2^31 strided ranks")
+    depth = _lib.empty((F, H, W), dtype=torch.int16, device=dev)
+    label = _lib.empty((F, H, W), dtype=torch.uint8, device=dev)
+    tri = _lib.empty((F, H, W), dtype=torch.int32, device=dev) if return_tri else None
+    counts = _lib.empty((2, J), dtype=torch.int32, device=dev)
+    ws = _lib.empty((nbytes,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.cloudaae_render_frames(S, ptr(p.vert_offsets), ptr(p.tri_offsets), int(p.vertices.shape[0]),
+                                            int(p.triangles.shape[0]), ptr(p.vertices), ptr(p.triangles), F, H, W, ptr(intr),
+                                            ptr(inst_offsets), J, ptr(inst_mesh), ptr(inst_label), ptr(poses),
+                                            ptr(vert_base), ptr(tri_base), sum_v, sum_t, float(z_near), ptr(depth),
+                                            ptr(label), ptr(tri), counts[0].data_ptr(), counts[1].data_ptr(), ptr(ws),
+                                            nbytes, stream()),
+                   "cloudaae_render_frames")
+    return depth, label, tri, counts
+
+
 def render_frames(meshes, instances, intrinsics, height, width, z_near=Z_NEAR, return_tri=False, scale=1.0, device=None,
                   sensor=None, sensor_seed=0, first_frame=0):
     """F frames of height x width.  meshes: a PackedMeshes or what mesh_models.pack_meshes takes (`scale` applies then).

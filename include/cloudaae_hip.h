@@ -52,7 +52,7 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * a workspace query), cloudaae_pose_matrix and cloudaae_pose_stack; cloudaae_icp_point_to_plane and
  * cloudaae_estimate_normals with its workspace query; cloudaae_sample_poses and cloudaae_random_object_occluder;
  * cloudaae_vsd_counts and cloudaae_pose_max_dist with its workspace query; cloudaae_depth_normals and
- * cloudaae_depth_sensor_noise. */
+ * cloudaae_depth_sensor_noise; cloudaae_frame_clouds with its workspace query and cloudaae_rendered_scene. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -1033,6 +1033,54 @@ int cloudaae_depth_sensor_noise(int f, int h, int w, const uint16_t *depth, cons
                                 double z0, double a2, double theta_max, double theta_drop, double p_drop, double baseline,
                                 double disparity_step, uint16_t *depth_out, uint8_t *label_out, int *counts, double *z_noisy,
                                 cloudaae_stream_t stream);
+
+/* ---- rendered training clouds ("Rendered training clouds", has the definition) ---- */
+
+/* c fixed-size clouds of `rows` points from the labelled pixels of f frames of h x w: depth [f,h,w] uint16, label [f,h,w]
+ * uint8, intrinsics [f,5] float as above.  Cloud i is described by frame_of[i] (int: the frame it reads), want[i] (int:
+ * the label value that selects pixels) and index[i] (long long: its global index g, in [0, 2^39)); fallback [c,3] float
+ * is optional (NULL: zeros).  All device memory, nothing is read back.
+ * Mask: the pixels p = v w + u of the frame with label == want and depth != 0, n of them; the rank of a masked pixel is
+ * its position among them in pixel order.  A masked pixel becomes the point (((u - cx) dm) / fx, ((v - cy) dm) / fy, dm),
+ * dm = (float)depth / factor_depth, in float without fma (the back-projection of cloudaae_frame_segments).
+ * q_j = word 0 of philox4x32(seed, g 2^24 + j, stream), stream 23 for n >= rows and 24 for n < rows.
+ * n >= rows: with s_j = floor(j n / rows), row j is the masked pixel of rank s_j + floor(q_j (s_{j+1} - s_j) / 2^32):
+ * one pixel per stratum, in pixel order, none twice; num_distinct = rows, row_src[j] = j.
+ * 1 <= n < rows: rows 0 .. n-1 are the masked pixels in pixel order, row j >= n is a copy of row floor(q_j n / 2^32);
+ * num_distinct = n, row_src[j] = j below n and the copied row above -- the (cloud, count, source) convention that
+ * cloudaae_nn_distance_prefix takes.  n = 0: every row is fallback[i], num_distinct = 1, row_src = 0.
+ * A cloud whose frame_of lies outside [0, f) or whose index lies outside [0, 2^39) is the n = 0 case and no frame is
+ * read for it.
+ * Outputs: cloud [c,rows,3] float, num_pixels [c] int (n), num_distinct [c] long long, row_src [c,rows] int.
+ * Four launches; no atomic, nothing waits on another workgroup, and the same (frame bytes, want, seed, g) gives the same
+ * cloud whatever c, f or the position in either.  workspace: cloudaae_frame_clouds_workspace_bytes bytes, which is 0
+ * outside the limits: f, h, w, c >= 1; h * w <= 2^24; f * h * w <= 2^28; 1 <= rows <= 2^20; c * rows and
+ * c * ceil(h w / 1024) below 2^31.  Outside them, with a null pointer or a small workspace, the call returns an error
+ * and launches nothing. */
+long long cloudaae_frame_clouds_workspace_bytes(int f, int h, int w, int c, int rows);
+int cloudaae_frame_clouds(int f, int h, int w, const uint16_t *depth, const uint8_t *label, const float *intrinsics, int c,
+                          const int *frame_of, const int *want, const long long *index, const float *fallback, int rows,
+                          unsigned long long seed, float *cloud, int *num_pixels, long long *num_distinct, int *row_src,
+                          void *workspace, long long workspace_bytes, cloudaae_stream_t stream);
+
+/* The scene of a rendered training batch, assembled on the device as cloudaae_render_frames takes it: sample i of b
+ * (global sample first_index + i) gives frame 2i with instance 3i -- mesh mesh_index[class_id[i]], label 1, pose
+ * [rot_mat64[i] | translation[i]] -- and frame 2i + 1 with instance 3i + 1 (the same) and 3i + 2, the occluder: label 2,
+ * mesh mesh_index[class], pose [rot_mat64[i] | centre], class and centre by the rule of cloudaae_random_object_occluder
+ * (streams 19 and 18 under `seed`; classes / n_classes / nmodels, wnear, hnear, near_dist as there).  class_id [b] long
+ * long, mesh_index [nmodels] int, rot_mat64 [b,9] double and translation [b,3] float are device memory; a class_id
+ * outside [0, nmodels) gives mesh -1, which the renderer draws nothing for.  The classes are not known to the host, so
+ * instance j's ranks start at j max_vertices and j max_triangles (the largest mesh's counts; the renderer treats ranks
+ * past a mesh's own counts as absent): pass the sums 3 b max_vertices and 3 b max_triangles on.
+ * Outputs (device): inst_offsets [2b+1], inst_mesh, inst_label [3b] int, inst_pose [3b,16] double, inst_vert_base,
+ * inst_tri_base [3b+1] int, occ_class [b] long long, occ_centre [b,3] float (optional, may be NULL).  One launch.
+ * Errors: b < 1; a maximum < 1; 3 b max_vertices or 3 b max_triangles above 2^31 - 1; a bad class list; a null pointer. */
+int cloudaae_rendered_scene(int b, unsigned long long first_index, unsigned long long seed, int nmodels, int n_classes,
+                            const int *classes, const long long *class_id, const int *mesh_index, const double *rot_mat64,
+                            const float *translation, float wnear, float hnear, float near_dist, int max_vertices,
+                            int max_triangles, int *inst_offsets, int *inst_mesh, int *inst_label, double *inst_pose,
+                            int *inst_vert_base, int *inst_tri_base, long long *occ_class, float *occ_centre,
+                            cloudaae_stream_t stream);
 
 #ifdef __cplusplus
 }
