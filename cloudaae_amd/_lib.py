@@ -143,6 +143,7 @@ _SIGNATURES = {
     "cloudaae_frame_clouds": [_I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _U, _P, _P, _P, _P, _P, _L, _P],
     "cloudaae_rendered_scene": [_I, _U, _U, _I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
                                 _P],
+    "cloudaae_transform_hausdorff": [_I, _I, _P, _I, _I, _P, _I, _P, _D, _P, _P, _P],
 }
 
 
@@ -364,6 +365,7 @@ def lib():
                        ("cloudaae_frame_clouds_workspace_bytes", [_I, _I, _I, _I, _I]),
                        ("cloudaae_pose_score_workspace_bytes", [_I, _I, _I]),
                        ("cloudaae_pose_max_dist_workspace_bytes", [_I, _I, _I]),
+                       ("cloudaae_transform_hausdorff_workspace_bytes", [_I]),
                        ("cloudaae_estimate_normals_workspace_bytes", [_I, _L]),
                        ("cloudaae_cloud_diameter_workspace_bytes", [_I, _I])):
             getattr(cdll, q).argtypes = sig

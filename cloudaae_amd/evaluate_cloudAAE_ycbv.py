@@ -326,7 +326,11 @@ def main(argv=None):
     on the class models' normals instead (computed once, before the loop).  --score prints, after the final line,
     the ADD / ADD-S summary of the predicted (and refined) poses per class and over all (PoseScoreLog.lines).  --bop
     --meshes DIR [--mesh_scale X] prints, after those, BOP's average recalls (BopScoreLog.lines): class i is the i-th
-    *.ply of DIR in sorted order (the convention of utils/render.py), symmetries the identity alone."""
+    *.ply of DIR in sorted order (the convention of utils/render.py).  --symmetries none|auto|FILE: the transform sets
+    MSSD and MSPD take the minimum over -- none (the default): the identity alone; auto: utils.symmetry.find_symmetries
+    for the run's class, on the mesh when --meshes is given, else on the class model; FILE: what `python -m
+    cloudaae_amd.utils.symmetry` wrote.  The found kinds are printed before the score lines, and with --score the
+    classes whose set holds more than the identity take the place of pose_score.SYMMETRIC_CLASSES."""
     from . import tfrecord_io
     from . import train_cloudAAE_ycbv as T
     p = argparse.ArgumentParser()
@@ -347,6 +351,9 @@ def main(argv=None):
     p.add_argument("--bop", action="store_true", help="BOP's VSD / MSSD / MSPD average recalls of the scored poses (needs --meshes)")
     p.add_argument("--meshes", default=None, help="directory of *.ply files; class i is the i-th in sorted order")
     p.add_argument("--mesh_scale", type=float, default=1.0, help="factor on the meshes' coordinates (0.001: millimetres to metres)")
+    p.add_argument("--symmetries", default="none",
+                   help="none, auto (found from --meshes, else from the class models) or a file written by "
+                        "`python -m cloudaae_amd.utils.symmetry`: the objects' symmetry transforms for --bop and --score")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--frames_per_launch", type=int, default=8)
     p.add_argument("--gpu", type=int, default=0)
@@ -375,15 +382,38 @@ def main(argv=None):
         # the normals of the 21 class models, once; a batch selects its classes' rows
         model_normals = normals_util.estimate_normals(
             torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda(), radius=NORMAL_RADIUS)[0]
+    sym_sets, sym_lines = None, []
+    if args.symmetries != "none":
+        from .utils import symmetry as sym_util
+        if args.symmetries == "auto":
+            c = args.target_cls                      # the one class this run evaluates
+            if args.meshes:
+                from .utils import mesh_models
+                found = sym_util.symmetries_of_meshes([mesh_models.mesh_files(args.meshes)[c]], scale=args.mesh_scale,
+                                                      mesh_ids=[c])
+            else:
+                found = sym_util.symmetries_of_models(models[c:c + 1])
+            sym_sets = {c: found[0]["transforms"]}
+            sym_lines = sym_util.kind_lines(found, classes=[c])
+        else:
+            require(os.path.exists(args.symmetries), "--symmetries: no such file: %s" % args.symmetries)
+            sym_sets = sym_util.load_symmetries(args.symmetries)
+            sym_lines = ["symmetry class %d transforms %d" % (c, len(t)) for c, t in sorted(sym_sets.items())]
     log = None
     if args.score:
         diam = score_util.model_diameter(torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda())
-        log = score_util.PoseScoreLog(("pred", "icp") if args.icp else ("pred",), diameters=diam)
+        if sym_sets is None:
+            log = score_util.PoseScoreLog(("pred", "icp") if args.icp else ("pred",), diameters=diam)
+        else:
+            log = score_util.PoseScoreLog(("pred", "icp") if args.icp else ("pred",), diameters=diam,
+                                          symmetric=[c for c, t in sym_sets.items() if len(t) > 1])
     bop, bop_log = None, None
     if args.bop:
         from .utils import mesh_models
         diam = score_util.model_diameter(torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda())
         bop = dict(meshes=mesh_models.pack_meshes(mesh_models.mesh_files(args.meshes), args.mesh_scale), diameters=diam)
+        if sym_sets is not None:
+            bop['symmetries'] = sym_sets
         bop_log = bop_util.BopScoreLog(("pred", "icp") if args.icp else ("pred",), diameters=diam)
 
     def frames():
@@ -431,6 +461,8 @@ def main(argv=None):
     print("batch size %d" % batch_idx)
     if batch_idx:
         print("trans_loss %f axag_loss %f" % (tot_trans / batch_idx, tot_axag / batch_idx))
+    for line in sym_lines:
+        print(line)
     if log is not None:
         for line in log.lines():
             print(line)

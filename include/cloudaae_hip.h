@@ -52,7 +52,8 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * a workspace query), cloudaae_pose_matrix and cloudaae_pose_stack; cloudaae_icp_point_to_plane and
  * cloudaae_estimate_normals with its workspace query; cloudaae_sample_poses and cloudaae_random_object_occluder;
  * cloudaae_vsd_counts and cloudaae_pose_max_dist with its workspace query; cloudaae_depth_normals and
- * cloudaae_depth_sensor_noise; cloudaae_frame_clouds with its workspace query and cloudaae_rendered_scene. */
+ * cloudaae_depth_sensor_noise; cloudaae_frame_clouds with its workspace query and cloudaae_rendered_scene;
+ * cloudaae_transform_hausdorff with its workspace query. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -1081,6 +1082,24 @@ int cloudaae_rendered_scene(int b, unsigned long long first_index, unsigned long
                             int max_triangles, int *inst_offsets, int *inst_mesh, int *inst_label, double *inst_pose,
                             int *inst_vert_base, int *inst_tri_base, long long *occ_class, float *occ_centre,
                             cloudaae_stream_t stream);
+
+/* ---- object symmetries ("Object symmetries", has the definition) ---- */
+
+/* The directed Hausdorff distance of m query points, moved by each of c rigid transforms, from n target points: queries
+ * [m] and targets [n] are float points q_stride / t_stride floats apart (>= 3; the first three are read and widened to
+ * double exactly), transforms [c,4,4] double row-major, top three rows read, applied as T x = ((A00 x + A01 y) + A02 z)
+ * + A03 row by row.  All device memory.  In double, no fma: H2_c = max_i min_j ((dx dx + dy dy) + dz dz) with d = T_c x_i
+ * - y_j; out [c] double = sqrt(H2_c) (correctly rounded) where H2_c <= limit2, else +inf.  limit2 >= 0, +inf allowed.
+ * Minima and maxima are exact (the maxima as integer comparisons on the bit patterns), so the result does not depend on
+ * the order of execution or the run.  A workgroup that finds its candidates' published maxima above limit2 already stops:
+ * their result is +inf either way.  A memset and two launches.  workspace:
+ * cloudaae_transform_hausdorff_workspace_bytes(c) bytes (-1 outside the limit on c), need not be initialised.
+ * Limits: 1 <= c <= 2^20; 1 <= m, n <= 2^24; ceil(c / 4) * ceil(m / 128) < 2^31.  Outside them, with a stride below 3, a
+ * limit2 that is negative or not a number, or a null pointer, the call returns an error and launches nothing. */
+long long cloudaae_transform_hausdorff_workspace_bytes(int c);
+int cloudaae_transform_hausdorff(int c, int m, const float *queries, int q_stride, int n, const float *targets, int t_stride,
+                                 const double *transforms, double limit2, double *out, void *workspace,
+                                 cloudaae_stream_t stream);
 
 #ifdef __cplusplus
 }
