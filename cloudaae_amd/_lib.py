@@ -144,6 +144,7 @@ _SIGNATURES = {
     "cloudaae_rendered_scene": [_I, _U, _U, _I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
                                 _P],
     "cloudaae_transform_hausdorff": [_I, _I, _P, _I, _I, _P, _I, _P, _D, _P, _P, _P],
+    "cloudaae_nearest_equivalent_pose": [_I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
 }
 
 

@@ -26,7 +26,7 @@
 // keeps its arithmetic statement for statement.
 #include "common.h"
 #include "../../include/cloudaae_hip.h"
-#include "pose_math.h"   // icp_rodrigues, icp_apply: shared with pose_score.hip
+#include "pose_math.h"   // icp_rodrigues, icp_apply: shared with pose_score.hip; icp_log_map: with pose_equiv.hip
 
 #include <math.h>
 
@@ -81,55 +81,6 @@ __device__ __forceinline__ int icp_bucket(int cx, int cy, int cz, unsigned mask)
 }  // namespace
 
 // ---- the 3x3 / 4x4 arithmetic of thread 0 (host-callable: it is plain fp64 code) ---------------------------------
-
-// Axis-angle of a rotation matrix, theta in [0, pi].  theta = atan2(|v|, tr - 1) with v the skew part (|v| = 2 sin,
-// tr - 1 = 2 cos): accurate at both ends.  Away from pi the axis is v / |v| (rot = v * theta / |v|, which tends to v / 2
-// as theta -> 0); near pi (cos < -0.5) it is the largest column of the symmetric part (R + R^T) / 2 - cos I =
-// (1 - cos) a a^T, signed to agree with v.
-__host__ __device__ inline void icp_log_map(const double *R, double *r)
-{
-    const double vx = R[7] - R[5], vy = R[2] - R[6], vz = R[3] - R[1];
-    const double tr1 = (R[0] + R[4] + R[8]) - 1.0;
-    const double vn = sqrt((vx * vx + vy * vy) + vz * vz);
-    const double theta = atan2(vn, tr1);
-    if (tr1 > -1.0) {                       // cos theta > -0.5
-        const double f = vn > 0.0 ? theta / vn : 0.5;
-        r[0] = vx * f;
-        r[1] = vy * f;
-        r[2] = vz * f;
-        return;
-    }
-    const double cs = 0.5 * tr1;
-    const double b01 = 0.5 * (R[1] + R[3]), b02 = 0.5 * (R[2] + R[6]), b12 = 0.5 * (R[5] + R[7]);
-    const double b00 = R[0] - cs, b11 = R[4] - cs, b22 = R[8] - cs;
-    double ax = b00, ay = b01, az = b02;
-    if (b11 > b00 && b11 >= b22) {
-        ax = b01;
-        ay = b11;
-        az = b12;
-    } else if (b22 > b00 && b22 > b11) {
-        ax = b02;
-        ay = b12;
-        az = b22;
-    }
-    const double an = sqrt((ax * ax + ay * ay) + az * az);
-    if (!(an > 0.0)) {
-        ax = 1.0;
-        ay = az = 0.0;
-    } else {
-        ax /= an;
-        ay /= an;
-        az /= an;
-    }
-    if ((ax * vx + ay * vy) + az * vz < 0.0) {
-        ax = -ax;
-        ay = -ay;
-        az = -az;
-    }
-    r[0] = ax * theta;
-    r[1] = ay * theta;
-    r[2] = az * theta;
-}
 
 // The rotation R (row-major 3x3) that maximises tr(R^T S) over SO(3), for S = Sigma = (1/n) sum (q - mq)(p - mp)^T:
 // Horn's quaternion -- the eigenvector of the largest eigenvalue of the symmetric 4x4 matrix built from S -- by

@@ -35,11 +35,12 @@ from .utils import _functions as F
 from .utils import bop_score as bop_util
 from .utils import icp as icp_util
 from .utils import normals as normals_util
+from .utils import pose_equiv
 from .utils import pose_score as score_util
 from .utils import segment as seg_util
 
 
-def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None):
+def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None, symmetries=None):
     """One pass of evaluate_cloudAAE_ycbv.py:421-477 on a batch.  Returns the tensors its loop
     fetches (:546-560): xyz_recon [B,4N,3], xyz_recon_FPS [B,N,3], rot_pred, trans_pred, the three
     losses with their per-sample values, mean_dist_loss, element_mean.
@@ -65,7 +66,13 @@ def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None)
     (utils/bop_score.py, DESIGN.md "BOP pose errors") against the sample's own frame, element['frame_depth'] [B,H,W]
     and element['frame_intrinsics'] [B,5] (element_from_frames(keep_frames=True)): adds vsd_pred [B,K], mssd_pred,
     mspd_pred [B] float64 and, with icp, vsd_icp, mssd_icp, mspd_icp.  MSSD and MSPD are taken on element['obj_batch'].
-    Not with replay=True.  The other outputs are those of bop=None."""
+    Not with replay=True.  The other outputs are those of bop=None.
+    symmetries=a utils.pose_equiv.SymmetryTable (or bop['symmetries_table']): the rotation and translation errors are also
+    taken against the label that is equivalent under the class's symmetries and nearest the pose's rotation (DESIGN.md,
+    "Equivalent poses"; one cloudaae_nearest_equivalent_pose launch per pose set): adds axag_loss_sym, trans_loss_sym,
+    axag_loss_perSample_sym, trans_loss_perSample_sym and, with icp, axag_loss_icp_sym, trans_loss_icp_sym,
+    axag_loss_perSample_icp_sym, trans_loss_perSample_icp_sym.  Works with replay=True.  The other outputs are those of
+    symmetries=None."""
     icp = _icp_params(icp)
     score = bool(score)
     if bop is not None:
@@ -73,9 +80,13 @@ def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None)
                 "bop must be a dict with 'meshes' and 'diameters'")
         require(not replay, "bop scores are not available with replay=True: every chunk of rendered frames is allocated by "
                             "its own sizes and read back, which does not fit a recorded plan")
+    if symmetries is None and bop is not None:
+        symmetries = bop.get('symmetries_table')
+    if symmetries is not None:
+        require(isinstance(symmetries, pose_equiv.SymmetryTable), "symmetries must be a pose_equiv.SymmetryTable")
     if replay:
-        return _replayed(graph, element, icp, score)
-    out = _evaluate(graph, element, icp, score)
+        return _replayed(graph, element, icp, score, symmetries)
+    out = _evaluate(graph, element, icp, score, symmetries)
     if bop is not None:
         out.update(_bop(element, out, bop))
     return out
@@ -125,7 +136,7 @@ def _icp_params(icp):
     return dict(icp)
 
 
-def _replayed(graph, element, icp=None, score=False):
+def _replayed(graph, element, icp=None, score=False, symmetries=None):
     N = graph.NUM_POINT
     src = {'xyz_inlier': (element['xyz_inlier'], torch.float32),
            'visiblePoints_org': (element['visiblePoints_org'][:, 0:N, :], torch.float32),
@@ -141,6 +152,8 @@ def _replayed(graph, element, icp=None, score=False):
         key += (('icp', tuple(sorted(icp.items()))),)
     if score:
         key += (('score',),)
+    if symmetries is not None:
+        key += (('symmetries', id(symmetries)),)
     plans = graph.__dict__.setdefault('_eval_plans', {})
     if key not in plans:
         static = {k: torch.empty(tuple(v.shape), dtype=dt, device=graph.device) for k, (v, dt) in src.items()}
@@ -153,7 +166,7 @@ def _replayed(graph, element, icp=None, score=False):
     if plan is None:
         plan = _lib.StepPlan(graph.device)
         with _lib.record(plan):
-            out = _evaluate(graph, static, icp, score)
+            out = _evaluate(graph, static, icp, score, symmetries)
         if plan.foreign_ops:
             import warnings
             warnings.warn("evaluation pass not replayable (torch kernels inside: %s)" % sorted(set(plan.foreign_ops)))
@@ -165,7 +178,7 @@ def _replayed(graph, element, icp=None, score=False):
     return out
 
 
-def _evaluate(graph, element, icp=None, score=False):
+def _evaluate(graph, element, icp=None, score=False, symmetries=None):
     N = graph.NUM_POINT
     xyz = element['xyz_inlier']
     require(xyz.dim() == 3 and xyz.shape[1] >= N and xyz.shape[2] == 3, "xyz_inlier must be [B, >=num_point, 3]")
@@ -198,7 +211,22 @@ def _evaluate(graph, element, icp=None, score=False):
         out.update(_refine(element, xyz[:, 0:N, :], rot_pred, trans_pred, translation, icp))
     if score:
         out.update(_score(element, rot_pred, trans_pred, translation, out.get('transformation_icp')))
+    if symmetries is not None:
+        out.update(_equivalent_errors(element, cls, rot_pred, trans_pred, translation, symmetries, ''))
+        if icp is not None:
+            out.update(_equivalent_errors(element, cls, icp_util.to_float32(out['rot_icp']), out['trans_icp'], translation,
+                                          symmetries, '_icp'))
     return out
+
+
+def _equivalent_errors(element, cls, rot, trans, translation, table, tag):
+    """The errors of the pose (rot, trans) against the equivalent label nearest its rotation."""
+    with torch.no_grad():
+        near = pose_equiv.nearest_equivalent_pose(rot, element['axisangle'], translation, cls, table)
+        trans_loss, trans_per = trans_distance.get_translation_error(trans, near['trans_equiv'])
+        axag_loss, axag_per = angular_distance_taylor.get_rotation_error(rot, near['rot_equiv'])
+    return {'trans_loss%s_sym' % tag: trans_loss, 'trans_loss_perSample%s_sym' % tag: trans_per,
+            'axag_loss%s_sym' % tag: axag_loss, 'axag_loss_perSample%s_sym' % tag: axag_per}
 
 
 def _score(element, rot_pred, trans_pred, translation, transformation_icp):
@@ -330,7 +358,9 @@ def main(argv=None):
     MSSD and MSPD take the minimum over -- none (the default): the identity alone; auto: utils.symmetry.find_symmetries
     for the run's class, on the mesh when --meshes is given, else on the class model; FILE: what `python -m
     cloudaae_amd.utils.symmetry` wrote.  The found kinds are printed before the score lines, and with --score the
-    classes whose set holds more than the identity take the place of pose_score.SYMMETRIC_CLASSES."""
+    classes whose set holds more than the identity take the place of pose_score.SYMMETRIC_CLASSES.  With a symmetry set
+    the translation and rotation errors are also taken against the nearest equivalent label (evaluate_batch(symmetries=)):
+    every batch line and the final line get their *_sym twins."""
     from . import tfrecord_io
     from . import train_cloudAAE_ycbv as T
     p = argparse.ArgumentParser()
@@ -376,13 +406,14 @@ def main(argv=None):
         files = [f for f in files if os.path.exists(f)]
         require(files, "no <seq>_pcnn.tfrecord of class %d under %s" % (args.target_cls, args.data_dir))
     pending, batch_idx, tot_trans, tot_axag, n_launch = None, 0, 0.0, 0.0, 0
+    tot_sym = {}                                 # sums of the *_sym means (--symmetries)
     icp, model_normals = args.icp, None
     if args.icp_plane:
         icp = {'estimation': 'point_to_plane'}
         # the normals of the 21 class models, once; a batch selects its classes' rows
         model_normals = normals_util.estimate_normals(
             torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda(), radius=NORMAL_RADIUS)[0]
-    sym_sets, sym_lines = None, []
+    sym_sets, sym_lines, sym_table = None, [], None
     if args.symmetries != "none":
         from .utils import symmetry as sym_util
         if args.symmetries == "auto":
@@ -395,9 +426,11 @@ def main(argv=None):
                 found = sym_util.symmetries_of_models(models[c:c + 1])
             sym_sets = {c: found[0]["transforms"]}
             sym_lines = sym_util.kind_lines(found, classes=[c])
+            sym_table = pose_equiv.SymmetryTable.from_results(found, len(models), [c], graph.device)
         else:
             require(os.path.exists(args.symmetries), "--symmetries: no such file: %s" % args.symmetries)
             sym_sets = sym_util.load_symmetries(args.symmetries)
+            sym_table = pose_equiv.load_symmetry_table(args.symmetries, len(models), graph.device)
             sym_lines = ["symmetry class %d transforms %d" % (c, len(t)) for c, t in sorted(sym_sets.items())]
     log = None
     if args.score:
@@ -441,7 +474,7 @@ def main(argv=None):
             el_b = {k: v for k, v in b.items() if isinstance(v, torch.Tensor)}
             if model_normals is not None:
                 el_b['obj_normals'] = model_normals.index_select(0, el_b['class_id'])
-            out = evaluate_batch(graph, el_b, icp=icp, score=args.score, bop=bop)
+            out = evaluate_batch(graph, el_b, icp=icp, score=args.score, bop=bop, symmetries=sym_table)
             if bop_log is not None:
                 bop_log.append(b["class_id"], *[torch.stack([out[m + n] for n in bop_log.poses], dim=1)
                                                 for m in ("vsd_", "mssd_", "mspd_")],
@@ -456,11 +489,17 @@ def main(argv=None):
                 batch_idx, int(b["seq_id"][0]), int(b["frame_id"][0]), tl, al)
             if args.icp:
                 line += " trans_loss_icp %f rot_loss_icp %f" % (float(out["trans_loss_icp"]), float(out["axag_loss_icp"]))
+            if sym_table is not None:
+                for k in ("trans_loss_sym", "axag_loss_sym") + (("trans_loss_icp_sym", "axag_loss_icp_sym") if args.icp else ()):
+                    tot_sym[k] = tot_sym.get(k, 0.0) + float(out[k])
+                    line += " %s %f" % (k.replace("axag", "rot"), float(out[k]))
             print(line)
             batch_idx += 1
     print("batch size %d" % batch_idx)
     if batch_idx:
         print("trans_loss %f axag_loss %f" % (tot_trans / batch_idx, tot_axag / batch_idx))
+        if tot_sym:
+            print(" ".join("%s %f" % (k, v / batch_idx) for k, v in tot_sym.items()))
     for line in sym_lines:
         print(line)
     if log is not None:

@@ -97,6 +97,10 @@ def get_training_argparser():
     extra.add_argument('--sensor', default='none', choices=['none', 'kinect1'],
                        help='depth sensor model on the rendered frames (utils/depth_noise.py); with --visibility rendered')
     extra.add_argument('--sensor_seed', type=int, default=0, help='seed of the sensor noise')
+    extra.add_argument('--symmetries', default='none',
+                       help="none: the pose labels as they are [default]; auto: find the rotational symmetries of the classes "
+                            "trained on (of the --meshes, else of the class models) and train against the nearest equivalent "
+                            "label (utils/pose_equiv.py); or the JSON file python -m cloudaae_amd.utils.symmetry wrote")
     return parser
 
 
@@ -115,7 +119,8 @@ class TrainGraph(object):
 
     def __init__(self, general_opts=None, train_opts=None, hyperparameters=None, device=None,
                  model_fn='get_model_dgcnn_mean_6d', k_neighbor=K_NEIGHBOR, process_group=None, seed=123456789,
-                 replay=False, gemm_dtype='bf16x3', side_stream=None, sync_bn=False, deterministic=False):
+                 replay=False, gemm_dtype='bf16x3', side_stream=None, sync_bn=False, deterministic=False,
+                 symmetries=None):
         general_opts = dict(general_opts or {})
         train_opts = dict(train_opts or {})
         hyperparameters = dict(hyperparameters or {})
@@ -190,11 +195,29 @@ class TrainGraph(object):
         # reverse neighbour lists -- at a price (measured: DESIGN.md).  One process, one mode: the library's knob is
         # process-wide and set at every step.
         self.deterministic = bool(deterministic)
+        # symmetries: a pose_equiv.SymmetryTable.  The pose terms are then taken against the label that is equivalent
+        # under the object's symmetries and nearest the predicted rotation -- the minimum of the loss over the symmetry
+        # set, the choice held constant in the gradient -- found by one launch in front of the loss (DESIGN.md,
+        # "Equivalent poses").  None: the element's labels as they are, and not one call more.
         self.replay = bool(replay)
         self.reuse_staged_inputs = False
         self._plan = self._plan_key = self._plan_out = self._static = self._staged = None
         self._plans = {}                     # parked recordings of other input shapes
+        self.symmetries = None
+        if symmetries is not None:
+            self.set_symmetries(symmetries)
         self._build()
+
+    def set_symmetries(self, table):
+        """Give the graph a symmetry table (or None) after construction, e.g. once the object models are known.  Steps
+        recorded so far are dropped: the launch is part of a recorded step."""
+        if table is not None:
+            from .utils.pose_equiv import SymmetryTable
+            require(isinstance(table, SymmetryTable), "symmetries must be a pose_equiv.SymmetryTable or None")
+            table.on(self.device)
+        self.symmetries = table
+        self._plan = self._plan_key = self._plan_out = self._static = self._staged = None
+        self._plans = {}
 
     # -- graph construction: create every variable once, then pack them ---------------------
     def _build(self):
@@ -297,11 +320,18 @@ class TrainGraph(object):
         # :236-268 -- Chamfer loss, translation error, SO(3) error (float64) and the weighted total: the search and
         # ONE tail launch (same arithmetic as chamfer_loss.get_loss / trans_distance.get_translation_error /
         # angular_distance_taylor.get_rotation_error / the sum of :268, which stay available on their own)
+        trans_label, rot_label, equiv = element['translation'], element['axisangle'], {}
+        if self.symmetries is not None:
+            from .utils.pose_equiv import nearest_equivalent_pose
+            near = nearest_equivalent_pose(rot_pred, rot_label, trans_label, cls, self.symmetries)
+            trans_label, rot_label = near['trans_equiv'], near['rot_equiv']
+            equiv = dict(axisangle_equiv=rot_label, translation_equiv=trans_label, symmetry_member=near['member'],
+                         symmetry_phi=near['phi'])
         (total_loss, xyz_loss, xyz_loss_per_sample, trans_loss, trans_loss_perSample, axag_loss,
-         axag_loss_perSample) = F.StepLossFn.apply(xyz_recon, visiblePoints_org_final, trans_pred, element['translation'],
-                                                   rot_pred, element['axisangle'], *LOSS_WEIGHTS,
+         axag_loss_perSample) = F.StepLossFn.apply(xyz_recon, visiblePoints_org_final, trans_pred, trans_label,
+                                                   rot_pred, rot_label, *LOSS_WEIGHTS,
                                                    self._one if is_training else None, count2, row_src2)
-        return dict(total_loss=total_loss, xyz_loss=xyz_loss, trans_loss=trans_loss, axag_loss=axag_loss,
+        return dict(equiv, total_loss=total_loss, xyz_loss=xyz_loss, trans_loss=trans_loss, axag_loss=axag_loss,
                     xyz_recon=xyz_recon, xyz_loss_per_sample=xyz_loss_per_sample,
                     trans_loss_perSample=trans_loss_perSample, axag_loss_perSample=axag_loss_perSample,
                     rot_pred=rot_pred, trans_pred=trans_pred, visiblePoints_final=noisy,
@@ -793,6 +823,29 @@ def load_dataset(data_dir, device, rank=0, world=1, classes=None):
     return obj_models, (records.shard(rank, world) if world > 1 else records)
 
 
+def symmetry_table_for(spec, obj_models, classes=None, meshes='', mesh_scale=1.0, device=None):
+    """--symmetries auto|FILE -> (pose_equiv.SymmetryTable over the obj_models.shape[0] classes, the lines that say what
+    was found).  auto: symmetries_of_meshes of the --meshes when there are any, else symmetries_of_models of the class
+    models, for `classes` (default: all)."""
+    import json
+    from .utils import pose_equiv, symmetry
+    num_class = int(obj_models.shape[0])
+    if spec != 'auto':
+        with open(spec) as f:
+            entries = json.load(f)["classes"]
+        ids = [int(e["class"]) for e in entries]
+        return pose_equiv.load_symmetry_table(spec, num_class, device), symmetry.kind_lines(entries, ids)
+    ids = list(range(num_class)) if classes is None else [int(c) for c in classes]
+    if meshes:
+        from .utils import mesh_models
+        files = mesh_models.mesh_files(meshes)
+        results = symmetry.symmetries_of_meshes([files[c] for c in ids], scale=mesh_scale, device=device, mesh_ids=ids)
+    else:
+        results = symmetry.symmetries_of_models(obj_models[ids][:, :, :3].contiguous())
+    table = pose_equiv.SymmetryTable.from_results(results, num_class, ids, device)
+    return table, symmetry.kind_lines(results, ids)
+
+
 def main(argv=None):
     parser = get_training_argparser()
     groups = parse_arg_groups(parser, argv)
@@ -803,6 +856,8 @@ def main(argv=None):
         parser.error("--visibility rendered needs --poses sampled and --meshes (the frames are rendered from the meshes)")
     if extra['sensor'] != 'none' and extra['visibility'] != 'rendered':
         parser.error("--sensor needs --visibility rendered (there is no depth frame to apply it to otherwise)")
+    if extra['symmetries'] != 'none' and not (extra['data_dir'] or extra['poses'] == 'sampled'):
+        parser.error("--symmetries needs object models: give --data_dir or --poses sampled")
     world = int(os.environ.get('WORLD_SIZE', '1'))
     if world > 1:
         local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -855,6 +910,12 @@ def main(argv=None):
                             num_point=graph.NUM_POINT, sensor=None if extra['sensor'] == 'none' else extra['sensor'],
                             sensor_seed=extra['sensor_seed'])
         log("%d pose records on rank 0, %d batches per epoch" % (len(records), len(records) // graph.local_batch))
+        if extra['symmetries'] != 'none':
+            table, lines = symmetry_table_for(extra['symmetries'], obj_models, classes, extra['meshes'], extra['mesh_scale'],
+                                              graph.device)
+            graph.set_symmetries(table)
+            for line in lines:
+                log(line)
         class_log = ClassLossLog(graph.device)
         for epoch in range(int(topts['max_epoch'])):
             log('**** EPOCH %03d ****' % epoch)

@@ -53,7 +53,7 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * cloudaae_estimate_normals with its workspace query; cloudaae_sample_poses and cloudaae_random_object_occluder;
  * cloudaae_vsd_counts and cloudaae_pose_max_dist with its workspace query; cloudaae_depth_normals and
  * cloudaae_depth_sensor_noise; cloudaae_frame_clouds with its workspace query and cloudaae_rendered_scene;
- * cloudaae_transform_hausdorff with its workspace query. */
+ * cloudaae_transform_hausdorff with its workspace query; cloudaae_nearest_equivalent_pose. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -1100,6 +1100,58 @@ long long cloudaae_transform_hausdorff_workspace_bytes(int c);
 int cloudaae_transform_hausdorff(int c, int m, const float *queries, int q_stride, int n, const float *targets, int t_stride,
                                  const double *transforms, double limit2, double *out, void *workspace,
                                  cloudaae_stream_t stream);
+
+/* ---- equivalent poses ("Equivalent poses", has the definition) ---- */
+
+/* The symmetry table of num_class classes, all device memory:
+ *   sym_index  [num_class,3] int     kind, first, count of class i
+ *   sym_centre [num_class,3] double  the symmetry centre c in the object frame (read for kinds with members)
+ *   sym_axis   [num_class,3] double  the unit axis a (read for CLOUDAAE_SYMMETRY_AXIAL)
+ *   sym_rot    [num_rot,9]   double  rotations, row-major 3x3; may be NULL when num_rot = 0
+ * CLOUDAAE_SYMMETRY_NONE: no members (an object without symmetry; also what a spherical one is given: every rotation
+ * is equivalent there and no label is nearer than another in a useful sense).  CLOUDAAE_SYMMETRY_FINITE: the count
+ * rotations G_j = sym_rot[first + j], 1 <= count <= CLOUDAAE_SYMMETRY_MAX_MEMBERS, the identity first.
+ * CLOUDAAE_SYMMETRY_AXIAL: every rotation about a, and with count = 1 also F = sym_rot[first], a half-turn about a
+ * line perpendicular to a, times those; count is 0 or 1.  The index lives on the device, so the host cannot read it:
+ * an entry with another kind, or whose first / count leave [0, num_rot] or the limits above, is treated as
+ * CLOUDAAE_SYMMETRY_NONE by the kernel and never followed; so is a class_id outside [0, num_class). */
+#define CLOUDAAE_SYMMETRY_NONE 0
+#define CLOUDAAE_SYMMETRY_FINITE 1
+#define CLOUDAAE_SYMMETRY_AXIAL 2
+#define CLOUDAAE_SYMMETRY_MAX_MEMBERS 64
+
+/* Of the poses T_label o [S | c - S c], S in the class's symmetry set, the one whose rotation is nearest the predicted
+ * one.  rot_pred [b,3] axis-angle, float (rot_pred_is_f64 = 0) or double (1), widened exactly; rot_label [b,3] double,
+ * trans_label [b,3] float, class_id [b] long long; the table as above.  In double, no fma, products and sums in the
+ * written order; exp is the exponential map of cloudaae_exponential_map (the loss's op sequence).
+ *   Rp = exp(rot_pred), Rl = exp(rot_label), M = Rp^T Rl: M[i][k] = (Rp[0][i] Rl[0][k] + Rp[1][i] Rl[1][k]) + Rp[2][i] Rl[2][k],
+ *   so that tr(M S) is the trace the loss sees for the label Rl S.  tr X = (X00 + X11) + X22; a matrix product X Y has
+ *   (X Y)[i][k] = (X[i][0] Y[0][k] + X[i][1] Y[1][k]) + X[i][2] Y[2][k].
+ *   none:   S* = I, member = 0, phi = 0, s* = tr M; rot_equiv and trans_equiv are the labels, copied bit for bit.
+ *   finite: s_j = (t_0 + t_1) + t_2 with t_i = (M[i][0] G_j[0][i] + M[i][1] G_j[1][i]) + M[i][2] G_j[2][i]; member = the
+ *           smallest j with the largest s_j, S* = G_member, phi = 0.
+ *   axial:  for the cosets E_0 = I and, with count = 1, E_1 = F:  N = M E_e (N = M itself for e = 0),
+ *           u_i = (N[i][0] a0 + N[i][1] a1) + N[i][2] a2, alpha = (a0 u0 + a1 u1) + a2 u2, tau = tr N,
+ *           beta = (a0 (N12 - N21) + a1 (N20 - N02)) + a2 (N01 - N10), d = tau - alpha,
+ *           s_e = alpha + sqrt(d d + beta beta)  (the maximum of tr(N R_a(phi)) over phi),
+ *           phi_e = atan2(beta, d), or 0 when d = beta = 0;
+ *           member = the smallest e with the largest s_e, phi = phi_member, S* = E_member R_a(phi) (R_a itself for member 0)
+ *           with R_a(phi)[i][k] = (delta_ik + sin(phi) K[i][k]) + (1 - cos(phi)) (K K)[i][k], K = [a]x.
+ *   Where S* is the identity matrix exactly (member 0 of a finite set, or no turn about the axis) rot_equiv and trans_equiv
+ *   are again the labels, copied bit for bit.  Otherwise
+ *   rot_equiv [b,3] double = the log map of Rl S* as "Pose refinement" defines it for rot_out (theta = atan2(|v|, tr - 1),
+ *           the axis from the symmetric part when cos < -0.5);
+ *   trans_equiv [b,3] float = float(double(trans_label) + Rl w), w_i = c_i - (S* c)_i, (X v)_i = (X[i][0] v0 + X[i][1] v1)
+ *           + X[i][2] v2: the translation of T_label o [S* | c - S* c], the convention of cloudaae_pose_max_dist's G (S x);
+ *   member [b] int, phi [b] double, angle [b] double = acos(clamp((s* - 1) / 2, -0.9999999, 0.9999999)), the loss's clamp.
+ * One wave per sample, one launch, no workspace, no atomics: bit-reproducible and independent of b.
+ * Errors (nothing is launched): b outside [1, 2^24]; rot_pred_is_f64 not 0 or 1; num_class < 1; num_rot outside
+ * [0, 2^24]; a null pointer (sym_rot may be NULL only with num_rot = 0). */
+int cloudaae_nearest_equivalent_pose(int b, const void *rot_pred, int rot_pred_is_f64, const double *rot_label,
+                                     const float *trans_label, const long long *class_id, int num_class,
+                                     const int *sym_index, const double *sym_centre, const double *sym_axis, int num_rot,
+                                     const double *sym_rot, double *rot_equiv, float *trans_equiv, int *member, double *phi,
+                                     double *angle, cloudaae_stream_t stream);
 
 #ifdef __cplusplus
 }
