@@ -145,6 +145,9 @@ _SIGNATURES = {
                                 _P],
     "cloudaae_transform_hausdorff": [_I, _I, _P, _I, _I, _P, _I, _P, _D, _P, _P, _P],
     "cloudaae_nearest_equivalent_pose": [_I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
+    "cloudaae_pose_compose": [_I, _P, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P],
+    "cloudaae_depth_fit_counts": [_I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "cloudaae_select_pose": [_I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
 }
 
 

@@ -37,10 +37,11 @@ from .utils import icp as icp_util
 from .utils import normals as normals_util
 from .utils import pose_equiv
 from .utils import pose_score as score_util
+from .utils import pose_verify as verify_util
 from .utils import segment as seg_util
 
 
-def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None, symmetries=None):
+def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None, symmetries=None, verify=None):
     """One pass of evaluate_cloudAAE_ycbv.py:421-477 on a batch.  Returns the tensors its loop
     fetches (:546-560): xyz_recon [B,4N,3], xyz_recon_FPS [B,N,3], rot_pred, trans_pred, the three
     losses with their per-sample values, mean_dist_loss, element_mean.
@@ -72,7 +73,17 @@ def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None,
     "Equivalent poses"; one cloudaae_nearest_equivalent_pose launch per pose set): adds axag_loss_sym, trans_loss_sym,
     axag_loss_perSample_sym, trans_loss_perSample_sym and, with icp, axag_loss_icp_sym, trans_loss_icp_sym,
     axag_loss_perSample_icp_sym, trans_loss_perSample_icp_sym.  Works with replay=True.  The other outputs are those of
-    symmetries=None."""
+    symmetries=None.
+    verify=dict(meshes=PackedMeshes, mesh_index=[B] host integers or None (then class_id), hypotheses=a
+    utils.pose_verify.HypothesisTable, tau=0.01 (metres), mode=0, base=None or [B,4,4] float64 poses to take the
+    predicted pose's place): the predicted pose is the base of the class's hypotheses (cloudaae_pose_compose); with icp all B P of them are refined in one refine_pose_icp call with the same parameters
+    (candidate 0 is then transformation_icp bit for bit); every candidate is rendered and compared with the sample's own
+    frame (utils/pose_verify.py, DESIGN.md "Pose verification"), element['frame_depth'], ['frame_intrinsics'] and, for mode
+    0, ['frame_label'] and ['frame_want'] (element_from_frames(keep_frames=True, keep_labels=True)), and the winner is
+    kept: adds verify_best [B] int32, verify_score [B,P], verify_margin [B], verify_counts [B,P,6], verify_candidates
+    [B,P,4,4], transformation_ver [B,4,4], rot_ver [B,3] float64, trans_ver [B,3] float32, trans_loss_ver / axag_loss_ver
+    with their per-sample values and, with score, bop and symmetries, the _ver twins of their _pred outputs.  Not with
+    replay=True.  The other outputs are those of verify=None."""
     icp = _icp_params(icp)
     score = bool(score)
     if bop is not None:
@@ -80,6 +91,12 @@ def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None,
                 "bop must be a dict with 'meshes' and 'diameters'")
         require(not replay, "bop scores are not available with replay=True: every chunk of rendered frames is allocated by "
                             "its own sizes and read back, which does not fit a recorded plan")
+    if verify is not None:
+        require(isinstance(verify, dict) and verify.get('meshes') is not None and
+                isinstance(verify.get('hypotheses'), verify_util.HypothesisTable),
+                "verify must be a dict with 'meshes' and 'hypotheses' (a pose_verify.HypothesisTable)")
+        require(not replay, "pose verification is not available with replay=True: every chunk of rendered frames is allocated "
+                            "by its own sizes and read back, which does not fit a recorded plan")
     if symmetries is None and bop is not None:
         symmetries = bop.get('symmetries_table')
     if symmetries is not None:
@@ -87,13 +104,87 @@ def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None,
     if replay:
         return _replayed(graph, element, icp, score, symmetries)
     out = _evaluate(graph, element, icp, score, symmetries)
+    if verify is not None:
+        out.update(_verify(graph, element, out, verify, icp, score, symmetries))
     if bop is not None:
         out.update(_bop(element, out, bop))
+        if verify is not None:
+            out.update(_bop(element, out, bop, only_ver=True))
     return out
 
 
-def _bop(element, out, bop):
-    """VSD, MSSD and MSPD of the predicted pose and, when there is one, of the refined pose."""
+def _verify(graph, element, out, verify, icp, score, symmetries):
+    """The hypotheses of the predicted pose, refined like it when there is an ICP, judged against the sample's frame; the
+    winner's pose and its errors."""
+    depth, intr = element.get('frame_depth'), element.get('frame_intrinsics')
+    mode = int(verify.get('mode', verify_util.MODE_SEGMENT))
+    label, want = (element.get('frame_label'), element.get('frame_want')) if mode == verify_util.MODE_SEGMENT else (None, None)
+    require(depth is not None and intr is not None and (mode != verify_util.MODE_SEGMENT or (label is not None and want is not None)),
+            "verify needs element['frame_depth'], ['frame_intrinsics'] and, for mode 0, ['frame_label'] and ['frame_want'] "
+            "(element_from_frames(keep_frames=True, keep_labels=True))")
+    cls = element['class_id'].to(torch.int64)
+    B, N = int(cls.shape[0]), graph.NUM_POINT
+    translation = element['translation'].to(torch.float32)
+    with torch.no_grad():
+        base = verify.get('base')
+        predicted = base is None
+        if predicted:
+            base = score_util.pose_matrix(out['rot_pred'].contiguous(), out['trans_pred'].contiguous())
+        c = verify_util.compose(base, cls, verify['hypotheses'])
+        P = int(c['pose'].shape[1])
+        cand, rot, trans = c['pose'], c['rot_axag'], c['trans']
+        if icp is not None:
+            # candidate 0 starts from the prediction itself, as _refine does; the kernel's samples are independent
+            rot0, trans0 = icp_util.to_float32(rot), trans.clone()
+            if predicted:
+                rot0[:, 0] = out['rot_pred']
+                trans0[:, 0] = out['trans_pred']
+            scene = element['xyz_inlier'].to(torch.float32).contiguous()[:, 0:N, :]
+            r = _icp_call(element, element['obj_batch'].repeat_interleave(P, dim=0),
+                          scene.repeat_interleave(P, dim=0).contiguous(), rot0.view(B * P, 3), trans0.view(B * P, 3), icp, P)
+            cand, rot, trans = r['transformation'].view(B, P, 4, 4), r['rot_axag'].view(B, P, 3), r['trans'].view(B, P, 3)
+        mesh_index = verify.get('mesh_index')
+        v = verify_util.verify_poses(verify['meshes'], cls.cpu().numpy() if mesh_index is None else mesh_index, cand, depth,
+                                     label, want, intr, np.arange(B), tau=verify.get('tau', 0.01), mode=mode,
+                                     valid=c['valid'], **{k: verify[k] for k in ('samples_per_launch',) if k in verify})
+        pick = v['best'].to(torch.int64).view(B, 1, 1).expand(B, 1, 3)
+        rot_ver = rot.gather(1, pick).squeeze(1).contiguous()
+        trans_ver = trans.gather(1, pick).squeeze(1).contiguous()
+        rot_ver32 = icp_util.to_float32(rot_ver)
+        trans_loss, trans_per = trans_distance.get_translation_error(trans_ver, translation)
+        axag_loss, axag_per = angular_distance_taylor.get_rotation_error(rot_ver32, element['axisangle'])
+    res = dict(verify_best=v['best'], verify_score=v['score'], verify_margin=v['margin'], verify_counts=v['counts'],
+               verify_candidates=cand, transformation_ver=v['pose_best'], rot_ver=rot_ver, trans_ver=trans_ver,
+               trans_loss_ver=trans_loss, trans_loss_perSample_ver=trans_per, axag_loss_ver=axag_loss,
+               axag_loss_perSample_ver=axag_per)
+    if score:
+        with torch.no_grad():
+            gt = score_util.pose_matrix(element['axisangle'], translation.contiguous())
+            s = score_util.score_poses(element['obj_batch'], v['pose_best'], gt)
+        res.update(add_ver=s['add'][:, 0], adds_ver=s['adds'][:, 0])
+    if symmetries is not None:
+        res.update(_equivalent_errors(element, cls, rot_ver32, trans_ver, translation, symmetries, '_ver'))
+    return res
+
+
+def _icp_call(element, obj, scene, rot, trans, params, repeat=1):
+    """refine_pose_icp as _refine calls it, on models and scenes that hold every sample `repeat` times in a row."""
+    if params.get('estimation', 'point_to_point') == 'point_to_plane':
+        params = dict(params)
+        normal_radius = params.pop('normal_radius', NORMAL_RADIUS)
+        params.pop('pose_maps_target_to_source', None)
+        normals = element.get('obj_normals')
+        if normals is None:
+            normals = normals_util.estimate_normals(element['obj_batch'], radius=normal_radius)[0]
+        return icp_util.refine_pose_icp(scene, obj, rot.contiguous(), trans.contiguous(),
+                                        normals=normals.repeat_interleave(repeat, dim=0).contiguous(),
+                                        pose_maps_target_to_source=True, **params)
+    return icp_util.refine_pose_icp(obj, scene, rot.contiguous(), trans.contiguous(), **params)
+
+
+def _bop(element, out, bop, only_ver=False):
+    """VSD, MSSD and MSPD of the predicted pose and, when there is one, of the refined pose; only_ver: of the verified
+    pose alone (a call of its own, so that the others' numbers are formed as without verification)."""
     obj, depth, intr = element.get('obj_batch'), element.get('frame_depth'), element.get('frame_intrinsics')
     require(obj is not None and depth is not None and intr is not None,
             "bop needs element['obj_batch'], ['frame_depth'] and ['frame_intrinsics'] (element_from_frames(keep_frames=True))")
@@ -103,7 +194,9 @@ def _bop(element, out, bop):
         gt = score_util.pose_matrix(element['axisangle'], element['translation'].to(torch.float32).contiguous())
         est = score_util.pose_matrix(out['rot_pred'].contiguous(), out['trans_pred'].contiguous())
         names = ("pred",)
-        if out.get('transformation_icp') is not None:
+        if only_ver:
+            est, names = out['transformation_ver'].unsqueeze(1), ("ver",)
+        elif out.get('transformation_icp') is not None:
             est = score_util.stack_poses(est, out['transformation_icp'])
             names = ("pred", "icp")
         else:
@@ -287,7 +380,8 @@ VALID_SEQ_ID = [[48, 51, 55, 56], [50, 54, 59], [49, 51, 54, 55, 58], [50, 51, 5
                 [48, 55], [50, 54, 56, 59], [55], [51], [57, 59], [48, 54], [48, 57], [57]]
 
 
-def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, device=None, keep_frames=False):
+def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, device=None, keep_frames=False,
+                        keep_labels=False):
     """create_tfrecord_dataset (:287-335) on decoded frame records (tfrecord_io.decode_frame): the frames that hold
     target_cls, their target_cls segment, the mean-distance filter, radius outlier removal, FPS_random of the inliers
     and of the filtered points from seeded starts, the > 100 and >= num_point rules, quat2axangle, the object model,
@@ -296,7 +390,9 @@ def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, devic
     [B,2049,3], class_id [B], translation [B,3], axisangle [B,3] float64, obj_batch [B,2048,6]) plus seq_id,
     frame_id and num_valid_points_in_segment [B] (numpy); None when no segment survives.  keep_frames=True adds each
     sample's own frame, frame_depth [B,H,W] int16 (the uint16 bits) and frame_intrinsics [B,5] float32 (device tensors):
-    what evaluate_batch(bop=...) compares the rendered object with."""
+    what evaluate_batch(bop=...) compares the rendered object with.  keep_labels=True adds frame_label [B,H,W] uint8, the
+    same frame's label image, and frame_want [B] int32, the label value by which extract_segments selects target_cls
+    (target_cls + 1): what evaluate_batch(verify=...) takes the object's segment from."""
     from .train_cloudAAE_ycbv import get_object_model, get_rotation_matrix, transform_object_model
     from .utils import hidden_point_removal as hpr
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -337,7 +433,28 @@ def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, devic
         of = np.asarray(r.frame, np.int64)[keep]
         el["frame_depth"] = torch.from_numpy(np.ascontiguousarray(depth[of].astype(np.uint16)).view(np.int16)).to(device)
         el["frame_intrinsics"] = torch.from_numpy(intr[of]).to(device)
+    if keep_labels:
+        of = np.asarray(r.frame, np.int64)[keep]
+        el["frame_label"] = torch.from_numpy(np.ascontiguousarray(label[of].astype(np.uint8))).to(device)
+        el["frame_want"] = torch.full((B,), int(target_cls) + 1, dtype=torch.int32, device=device)
     return el
+
+
+def verify_lines(rows):
+    """One line per class from (class_id, verify_best, verify_margin) device tensors of the batches (one read-back): how
+    many samples kept hypothesis 0 (the prediction) and how many chose each of the next three, and the mean margin."""
+    if not rows:
+        return []
+    cls = torch.cat([r[0] for r in rows]).cpu().numpy()
+    best = torch.cat([r[1] for r in rows]).cpu().numpy()
+    margin = torch.cat([r[2] for r in rows]).cpu().numpy()
+    out = []
+    for c in np.unique(cls):
+        sel = cls == c
+        k = [int((best[sel] == j).sum()) for j in range(4)]
+        out.append("verify class %d n %d kept0 %d chose1 %d chose2 %d chose3 %d mean_margin %f"
+                   % (int(c), int(sel.sum()), k[0], k[1], k[2], k[3], float(margin[sel].mean())))
+    return out
 
 
 def _take(el, lo, hi):
@@ -360,7 +477,10 @@ def main(argv=None):
     cloudaae_amd.utils.symmetry` wrote.  The found kinds are printed before the score lines, and with --score the
     classes whose set holds more than the identity take the place of pose_score.SYMMETRIC_CLASSES.  With a symmetry set
     the translation and rotation errors are also taken against the nearest equivalent label (evaluate_batch(symmetries=)):
-    every batch line and the final line get their *_sym twins."""
+    every batch line and the final line get their *_sym twins.  --verify --meshes DIR: the identity and the three principal
+    half turns of the class model (utils.pose_verify.flip_hypotheses) are composed with the predicted pose, refined like
+    it under --icp, and judged against the frame (evaluate_batch(verify=)); the winner is scored as a further pose `ver`
+    in every summary, and after the summaries one line per class says how often which hypothesis was kept."""
     from . import tfrecord_io
     from . import train_cloudAAE_ycbv as T
     p = argparse.ArgumentParser()
@@ -384,12 +504,18 @@ def main(argv=None):
     p.add_argument("--symmetries", default="none",
                    help="none, auto (found from --meshes, else from the class models) or a file written by "
                         "`python -m cloudaae_amd.utils.symmetry`: the objects' symmetry transforms for --bop and --score")
+    p.add_argument("--verify", action="store_true",
+                   help="verify the flip hypotheses of the predicted pose against the observed depth and score the winner "
+                        "as the pose `ver` (needs --meshes)")
+    p.add_argument("--verify_tau", type=float, default=0.01, help="depth tolerance of --verify, metres")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--frames_per_launch", type=int, default=8)
     p.add_argument("--gpu", type=int, default=0)
     args = p.parse_args(argv)
     if args.bop and not args.meshes:
         p.error("--bop needs --meshes DIR")
+    if args.verify and not args.meshes:
+        p.error("--verify needs --meshes DIR")
     args.icp = args.icp or args.icp_plane
     torch.cuda.set_device(args.gpu)
     obj_path = args.object_model or os.path.join(os.path.dirname(os.path.abspath(args.data_dir)),
@@ -432,13 +558,14 @@ def main(argv=None):
             sym_sets = sym_util.load_symmetries(args.symmetries)
             sym_table = pose_equiv.load_symmetry_table(args.symmetries, len(models), graph.device)
             sym_lines = ["symmetry class %d transforms %d" % (c, len(t)) for c, t in sorted(sym_sets.items())]
+    names = ("pred",) + (("icp",) if args.icp else ()) + (("ver",) if args.verify else ())      # the scored poses
     log = None
     if args.score:
         diam = score_util.model_diameter(torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda())
         if sym_sets is None:
-            log = score_util.PoseScoreLog(("pred", "icp") if args.icp else ("pred",), diameters=diam)
+            log = score_util.PoseScoreLog(names, diameters=diam)
         else:
-            log = score_util.PoseScoreLog(("pred", "icp") if args.icp else ("pred",), diameters=diam,
+            log = score_util.PoseScoreLog(names, diameters=diam,
                                           symmetric=[c for c, t in sym_sets.items() if len(t) > 1])
     bop, bop_log = None, None
     if args.bop:
@@ -447,7 +574,15 @@ def main(argv=None):
         bop = dict(meshes=mesh_models.pack_meshes(mesh_models.mesh_files(args.meshes), args.mesh_scale), diameters=diam)
         if sym_sets is not None:
             bop['symmetries'] = sym_sets
-        bop_log = bop_util.BopScoreLog(("pred", "icp") if args.icp else ("pred",), diameters=diam)
+        bop_log = bop_util.BopScoreLog(names, diameters=diam)
+    verify, verify_rows = None, []
+    if args.verify:
+        from .utils import mesh_models
+        c = args.target_cls
+        verify = dict(meshes=bop['meshes'] if bop is not None else
+                      mesh_models.pack_meshes(mesh_models.mesh_files(args.meshes), args.mesh_scale),
+                      hypotheses=verify_util.HypothesisTable.from_models(models[c:c + 1], [c], len(models)),
+                      tau=args.verify_tau)
 
     def frames():
         for fn in files:
@@ -462,7 +597,7 @@ def main(argv=None):
 
     for chunk in frames():
         el = element_from_frames(chunk, args.target_cls, args.num_point, models, seed=args.seed + n_launch,
-                                 keep_frames=args.bop)
+                                 keep_frames=args.bop or args.verify, keep_labels=args.verify)
         n_launch += 1
         if el is None:
             continue
@@ -474,7 +609,9 @@ def main(argv=None):
             el_b = {k: v for k, v in b.items() if isinstance(v, torch.Tensor)}
             if model_normals is not None:
                 el_b['obj_normals'] = model_normals.index_select(0, el_b['class_id'])
-            out = evaluate_batch(graph, el_b, icp=icp, score=args.score, bop=bop, symmetries=sym_table)
+            out = evaluate_batch(graph, el_b, icp=icp, score=args.score, bop=bop, symmetries=sym_table, verify=verify)
+            if verify is not None:
+                verify_rows.append((b["class_id"].to(torch.int64), out["verify_best"].to(torch.int64), out["verify_margin"]))
             if bop_log is not None:
                 bop_log.append(b["class_id"], *[torch.stack([out[m + n] for n in bop_log.poses], dim=1)
                                                 for m in ("vsd_", "mssd_", "mspd_")],
@@ -489,8 +626,11 @@ def main(argv=None):
                 batch_idx, int(b["seq_id"][0]), int(b["frame_id"][0]), tl, al)
             if args.icp:
                 line += " trans_loss_icp %f rot_loss_icp %f" % (float(out["trans_loss_icp"]), float(out["axag_loss_icp"]))
+            if args.verify:
+                line += " trans_loss_ver %f rot_loss_ver %f" % (float(out["trans_loss_ver"]), float(out["axag_loss_ver"]))
             if sym_table is not None:
-                for k in ("trans_loss_sym", "axag_loss_sym") + (("trans_loss_icp_sym", "axag_loss_icp_sym") if args.icp else ()):
+                for k in (("trans_loss_sym", "axag_loss_sym") + (("trans_loss_icp_sym", "axag_loss_icp_sym") if args.icp else ()) +
+                          (("trans_loss_ver_sym", "axag_loss_ver_sym") if args.verify else ())):
                     tot_sym[k] = tot_sym.get(k, 0.0) + float(out[k])
                     line += " %s %f" % (k.replace("axag", "rot"), float(out[k]))
             print(line)
@@ -508,6 +648,8 @@ def main(argv=None):
     if bop_log is not None:
         for line in bop_log.lines():
             print(line)
+    for line in verify_lines(verify_rows):
+        print(line)
     sys.stdout.flush()
     return 0
 

@@ -53,7 +53,8 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * cloudaae_estimate_normals with its workspace query; cloudaae_sample_poses and cloudaae_random_object_occluder;
  * cloudaae_vsd_counts and cloudaae_pose_max_dist with its workspace query; cloudaae_depth_normals and
  * cloudaae_depth_sensor_noise; cloudaae_frame_clouds with its workspace query and cloudaae_rendered_scene;
- * cloudaae_transform_hausdorff with its workspace query; cloudaae_nearest_equivalent_pose. */
+ * cloudaae_transform_hausdorff with its workspace query; cloudaae_nearest_equivalent_pose; cloudaae_pose_compose,
+ * cloudaae_depth_fit_counts and cloudaae_select_pose. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -1152,6 +1153,58 @@ int cloudaae_nearest_equivalent_pose(int b, const void *rot_pred, int rot_pred_i
                                      const int *sym_index, const double *sym_centre, const double *sym_axis, int num_rot,
                                      const double *sym_rot, double *rot_equiv, float *trans_equiv, int *member, double *phi,
                                      double *angle, cloudaae_stream_t stream);
+
+/* ---- pose verification ("Pose verification", has the definition) ---- */
+
+/* p hypotheses per sample from a base pose and the class's transform set.  base [b,16] double (row-major 4x4, top three
+ * rows read), class_id [b] long long; the table: hyp_index [nclass+1] int, offsets into hyp [n_total,16] double (row-major
+ * 4x4, top three rows read) -- class c owns members hyp_index[c] .. hyp_index[c+1] - 1, the first of which is the identity
+ * by the caller's contract.  All device memory.  Hypothesis j of sample i is base_i H_{c,j}, in double, no fma:
+ *   C[r][k] = (A[r][0] H[0][k] + A[r][1] H[1][k]) + A[r][2] H[2][k]                 k = 0, 1, 2
+ *   C[r][3] = ((A[r][0] H[0][3] + A[r][1] H[1][3]) + A[r][2] H[2][3]) + A[r][3]
+ * with A = base_i.  j >= the class's count repeats member 0 and sets valid to 0; a class_id outside [0, nclass), or an
+ * entry whose offsets leave [0, n_total] or run backwards, is an empty set: H = I for every j, valid 0, and hyp is not read.
+ * Outputs: pose [b,p,16] double (bottom row 0 0 0 1), rot_axag [b,p,3] double = the log map of C's rotation as "Pose
+ * refinement" defines it for rot_out (angle in [0, pi]), trans [b,p,3] float = float(C[r][3]), valid [b,p] int.
+ * One launch, one lane per hypothesis, no atomics: bit-reproducible and independent of b.
+ * Limits: b, p >= 1; b * p <= 2^28; nclass >= 1; 0 <= n_total <= 2^24; outside them, or with a null pointer (hyp may be
+ * NULL only with n_total = 0), the call returns an error and launches nothing. */
+int cloudaae_pose_compose(int b, const double *base, const long long *class_id, int nclass, const int *hyp_index, int n_total,
+                          const double *hyp, int p, double *pose, double *rot_axag, float *trans, int *valid,
+                          cloudaae_stream_t stream);
+
+/* How each of p rendered hypotheses of b samples agrees with the depth the camera saw.  depth_test [f,h,w] uint16;
+ * label [f,h,w] uint8 or NULL; frame_of [b] int: the test frame of each sample; want [b] int: the label value of the
+ * sample's object (may be NULL with label NULL); depth_hyp [b,p,h,w] uint16: the object's mesh alone, rendered with that
+ * frame's intrinsics (so the same factor_depth); tau [b] int, in depth units.  All device memory.
+ * Integer arithmetic on the uint16 values widened to int, no floating point.  Per pixel, t = test depth, d = hypothesis
+ * depth, seg = (label != NULL and label == want and t != 0):
+ *   rendered   d != 0
+ *   consistent d != 0 and t != 0 and |d - t| <= tau
+ *   in_front   d != 0 and t != 0 and t - d > tau     (the camera saw through the hypothesis)
+ *   behind     d != 0 and t != 0 and d - t > tau     (hidden by something nearer)
+ *   unknown    d != 0 and t == 0
+ *   explained  seg and consistent
+ * Outputs (zeroed by the call): counts [b,p,6] int in that order; seg_total [b] int = #seg; abs_sum [b,p] long long = the
+ * sum of |d - t| over the consistent pixels.  Three memsets and one launch; integer atomics only, so the results do not
+ * depend on the order of execution, the batch or the run.  A frame_of entry outside [0, f) leaves that sample's counts 0
+ * and causes no access.  Limits: f, h, w, b, p >= 1; h * w <= 2^24; b * p * h * w <= 2^28; outside them, or with a null
+ * pointer other than label (and want with it), the call returns an error and launches nothing. */
+int cloudaae_depth_fit_counts(int f, int h, int w, const uint16_t *depth_test, const uint8_t *label, int b, int p,
+                              const int *frame_of, const int *want, const uint16_t *depth_hyp, const int *tau, int *counts,
+                              int *seg_total, long long *abs_sum, cloudaae_stream_t stream);
+
+/* The winner among the p hypotheses of each sample.  counts [b,p,6], seg_total [b] as cloudaae_depth_fit_counts writes
+ * them, valid [b,p] int, pose [b,p,16] double.  mode 0 (the segment rule): num = explained, den = seg_total + in_front;
+ * mode 1 (the silhouette rule, for callers without a label): num = consistent, den = (consistent + in_front) + behind.
+ * A hypothesis with den <= 0, num < 0 or valid = 0 has num = 0, den = 1.  Hypothesis j beats k when num_j den_k >
+ * num_k den_j in 64-bit integers (exact: num <= 2^24, den < 2^26); best [b] int is the lowest index that no other beats.
+ * score [b,p] double = (double)num / (double)den; pose_best [b,16] double = pose[best], copied bit for bit; margin [b]
+ * double = score[best] - the largest score among the others, 0 for p = 1.  One launch, one lane per sample, no atomics.
+ * Limits: b, p >= 1; b * p <= 2^28; mode 0 or 1; outside them, or with a null pointer, the call returns an error and
+ * launches nothing. */
+int cloudaae_select_pose(int b, int p, const int *counts, const int *seg_total, const int *valid, const double *pose,
+                         int mode, int *best, double *score, double *pose_best, double *margin, cloudaae_stream_t stream);
 
 #ifdef __cplusplus
 }
