@@ -148,6 +148,10 @@ _SIGNATURES = {
     "cloudaae_pose_compose": [_I, _P, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P],
     "cloudaae_depth_fit_counts": [_I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "cloudaae_select_pose": [_I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
+    "cloudaae_ppf_model_pairs": [_I, _P, _P, _I, _L, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
+    "cloudaae_ppf_vote": [_I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P,
+                          _P, _P, _P, _P, _P, _P],
+    "cloudaae_ppf_cluster": [_I, _I, _P, _P, _P, _I, _P, _D, _I, _P, _P, _P, _P, _P, _P],
 }
 
 

@@ -38,10 +38,11 @@ from .utils import normals as normals_util
 from .utils import pose_equiv
 from .utils import pose_score as score_util
 from .utils import pose_verify as verify_util
+from .utils import ppf as ppf_util
 from .utils import segment as seg_util
 
 
-def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None, symmetries=None, verify=None):
+def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None, symmetries=None, verify=None, propose=None):
     """One pass of evaluate_cloudAAE_ycbv.py:421-477 on a batch.  Returns the tensors its loop
     fetches (:546-560): xyz_recon [B,4N,3], xyz_recon_FPS [B,N,3], rot_pred, trans_pred, the three
     losses with their per-sample values, mean_dist_loss, element_mean.
@@ -83,7 +84,14 @@ def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None,
     kept: adds verify_best [B] int32, verify_score [B,P], verify_margin [B], verify_counts [B,P,6], verify_candidates
     [B,P,4,4], transformation_ver [B,4,4], rot_ver [B,3] float64, trans_ver [B,3] float32, trans_loss_ver / axag_loss_ver
     with their per-sample values and, with score, bop and symmetries, the _ver twins of their _pred outputs.  Not with
-    replay=True.  The other outputs are those of verify=None."""
+    replay=True.  The other outputs are those of verify=None.
+    propose=dict(models=a utils.ppf.PPFModels, top=4, ref_step=5, peaks=2, normal_radius=0.02 (metres)): pose hypotheses by
+    point-pair-feature voting (utils/ppf.py, DESIGN.md "Pose proposals") from the first N points of element['xyz_inlier']
+    with normals estimated towards the camera: adds proposed_poses [B,top,4,4] float64, proposed_score and proposed_valid
+    [B,top] int32.  With verify they are appended after the class's hypotheses as candidates P_h .. P_h + top - 1 (an
+    invalid proposal repeats candidate 0, as compose does past a set's end), refined with icp by the same single call, judged
+    with the others and their valid passed to cloudaae_select_pose; the first P_h candidates' poses, counts and scores are
+    those of the call without propose bit for bit.  Not with replay=True.  The other outputs are those of propose=None."""
     icp = _icp_params(icp)
     score = bool(score)
     if bop is not None:
@@ -97,6 +105,11 @@ def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None,
                 "verify must be a dict with 'meshes' and 'hypotheses' (a pose_verify.HypothesisTable)")
         require(not replay, "pose verification is not available with replay=True: every chunk of rendered frames is allocated "
                             "by its own sizes and read back, which does not fit a recorded plan")
+    if propose is not None:
+        require(isinstance(propose, dict) and isinstance(propose.get('models'), ppf_util.PPFModels),
+                "propose must be a dict with 'models' (a ppf.PPFModels)")
+        require(not replay, "pose proposals are not available with replay=True: the mask, the candidates and the table pass "
+                            "through allocations and kernels of their own sizes, which does not fit a recorded plan")
     if symmetries is None and bop is not None:
         symmetries = bop.get('symmetries_table')
     if symmetries is not None:
@@ -104,8 +117,12 @@ def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None,
     if replay:
         return _replayed(graph, element, icp, score, symmetries)
     out = _evaluate(graph, element, icp, score, symmetries)
+    prop = None
+    if propose is not None:
+        prop = _propose(graph, element, propose)
+        out.update(proposed_poses=prop['pose'], proposed_score=prop['score'], proposed_valid=prop['valid'])
     if verify is not None:
-        out.update(_verify(graph, element, out, verify, icp, score, symmetries))
+        out.update(_verify(graph, element, out, verify, icp, score, symmetries, prop))
     if bop is not None:
         out.update(_bop(element, out, bop))
         if verify is not None:
@@ -113,9 +130,23 @@ def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None,
     return out
 
 
-def _verify(graph, element, out, verify, icp, score, symmetries):
-    """The hypotheses of the predicted pose, refined like it when there is an ICP, judged against the sample's frame; the
-    winner's pose and its errors."""
+PROPOSE_NORMAL_RADIUS = 0.02     # neighbourhood of the scene normals of the proposals, metres
+
+
+def _propose(graph, element, propose):
+    """The pose proposals of the network's N input points."""
+    N = graph.NUM_POINT
+    with torch.no_grad():
+        scene = element['xyz_inlier'].to(torch.float32).contiguous()[:, 0:N, :].contiguous()
+        normals, mask = ppf_util.scene_normals(scene, float(propose.get('normal_radius', PROPOSE_NORMAL_RADIUS)))
+        return ppf_util.propose_poses(propose['models'], scene, normals, mask, element['class_id'].to(torch.int64),
+                                      top=int(propose.get('top', 4)), ref_step=int(propose.get('ref_step', 5)),
+                                      peaks=int(propose.get('peaks', 2)))
+
+
+def _verify(graph, element, out, verify, icp, score, symmetries, prop=None):
+    """The hypotheses of the predicted pose and, when given, the proposals, refined like the prediction when there is an
+    ICP, judged against the sample's frame; the winner's pose and its errors."""
     depth, intr = element.get('frame_depth'), element.get('frame_intrinsics')
     mode = int(verify.get('mode', verify_util.MODE_SEGMENT))
     label, want = (element.get('frame_label'), element.get('frame_want')) if mode == verify_util.MODE_SEGMENT else (None, None)
@@ -132,7 +163,15 @@ def _verify(graph, element, out, verify, icp, score, symmetries):
             base = score_util.pose_matrix(out['rot_pred'].contiguous(), out['trans_pred'].contiguous())
         c = verify_util.compose(base, cls, verify['hypotheses'])
         P = int(c['pose'].shape[1])
-        cand, rot, trans = c['pose'], c['rot_axag'], c['trans']
+        cand, rot, trans, valid = c['pose'], c['rot_axag'], c['trans'], c['valid']
+        if prop is not None:
+            # candidates P .. P + top - 1; a proposal that is none repeats candidate 0
+            ok = prop['valid'] != 0
+            cand = torch.cat([cand, torch.where(ok[:, :, None, None], prop['pose'], cand[:, 0:1])], dim=1).contiguous()
+            rot = torch.cat([rot, torch.where(ok[:, :, None], prop['rot_axag'], rot[:, 0:1])], dim=1).contiguous()
+            trans = torch.cat([trans, torch.where(ok[:, :, None], prop['trans'], trans[:, 0:1])], dim=1).contiguous()
+            valid = torch.cat([valid, prop['valid']], dim=1).contiguous()
+            P = int(cand.shape[1])
         if icp is not None:
             # candidate 0 starts from the prediction itself, as _refine does; the kernel's samples are independent
             rot0, trans0 = icp_util.to_float32(rot), trans.clone()
@@ -146,7 +185,7 @@ def _verify(graph, element, out, verify, icp, score, symmetries):
         mesh_index = verify.get('mesh_index')
         v = verify_util.verify_poses(verify['meshes'], cls.cpu().numpy() if mesh_index is None else mesh_index, cand, depth,
                                      label, want, intr, np.arange(B), tau=verify.get('tau', 0.01), mode=mode,
-                                     valid=c['valid'], **{k: verify[k] for k in ('samples_per_launch',) if k in verify})
+                                     valid=valid, **{k: verify[k] for k in ('samples_per_launch',) if k in verify})
         pick = v['best'].to(torch.int64).view(B, 1, 1).expand(B, 1, 3)
         rot_ver = rot.gather(1, pick).squeeze(1).contiguous()
         trans_ver = trans.gather(1, pick).squeeze(1).contiguous()
@@ -457,6 +496,22 @@ def verify_lines(rows):
     return out
 
 
+def propose_lines(rows, flips):
+    """One line per class from (class_id, verify_best) device tensors of the batches (one read-back) when the candidates
+    were candidate 0 (the prediction), `flips` - 1 further hypotheses of the class and then the proposals: how many winners
+    came from each."""
+    if not rows:
+        return []
+    cls = torch.cat([r[0] for r in rows]).cpu().numpy()
+    best = torch.cat([r[1] for r in rows]).cpu().numpy()
+    out = []
+    for c in np.unique(cls):
+        b = best[cls == c]
+        out.append("propose class %d n %d from_prediction %d from_flip %d from_proposal %d"
+                   % (int(c), len(b), int((b == 0).sum()), int(((b > 0) & (b < flips)).sum()), int((b >= flips).sum())))
+    return out
+
+
 def _take(el, lo, hi):
     return {k: v[lo:hi] for k, v in el.items()}
 
@@ -480,7 +535,10 @@ def main(argv=None):
     every batch line and the final line get their *_sym twins.  --verify --meshes DIR: the identity and the three principal
     half turns of the class model (utils.pose_verify.flip_hypotheses) are composed with the predicted pose, refined like
     it under --icp, and judged against the frame (evaluate_batch(verify=)); the winner is scored as a further pose `ver`
-    in every summary, and after the summaries one line per class says how often which hypothesis was kept."""
+    in every summary, and after the summaries one line per class says how often which hypothesis was kept.  --propose ppf
+    (with --verify --meshes): --propose_top pose proposals by point-pair-feature voting on --propose_points oriented
+    points of the class's mesh (utils/ppf.py) join the candidates, and a last line per class says how many winners came
+    from the prediction, from a flip and from a proposal."""
     from . import tfrecord_io
     from . import train_cloudAAE_ycbv as T
     p = argparse.ArgumentParser()
@@ -508,6 +566,10 @@ def main(argv=None):
                    help="verify the flip hypotheses of the predicted pose against the observed depth and score the winner "
                         "as the pose `ver` (needs --meshes)")
     p.add_argument("--verify_tau", type=float, default=0.01, help="depth tolerance of --verify, metres")
+    p.add_argument("--propose", default=None, choices=("ppf",),
+                   help="add pose proposals by point-pair-feature voting to the candidates of --verify (needs --verify --meshes)")
+    p.add_argument("--propose_top", type=int, default=4, help="proposals per sample")
+    p.add_argument("--propose_points", type=int, default=256, help="oriented points of the class's mesh in the pair table")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--frames_per_launch", type=int, default=8)
     p.add_argument("--gpu", type=int, default=0)
@@ -516,6 +578,8 @@ def main(argv=None):
         p.error("--bop needs --meshes DIR")
     if args.verify and not args.meshes:
         p.error("--verify needs --meshes DIR")
+    if args.propose and not (args.verify and args.meshes):
+        p.error("--propose needs --verify and --meshes DIR")
     args.icp = args.icp or args.icp_plane
     torch.cuda.set_device(args.gpu)
     obj_path = args.object_model or os.path.join(os.path.dirname(os.path.abspath(args.data_dir)),
@@ -583,6 +647,12 @@ def main(argv=None):
                       mesh_models.pack_meshes(mesh_models.mesh_files(args.meshes), args.mesh_scale),
                       hypotheses=verify_util.HypothesisTable.from_models(models[c:c + 1], [c], len(models)),
                       tau=args.verify_tau)
+    propose = None
+    if args.propose:
+        c = args.target_cls
+        propose = dict(models=ppf_util.PPFModels.from_meshes([mesh_models.mesh_files(args.meshes)[c]], num_point=args.propose_points,
+                                                              scale=args.mesh_scale, classes=[c], num_class=len(models)),
+                       top=args.propose_top)
 
     def frames():
         for fn in files:
@@ -609,7 +679,8 @@ def main(argv=None):
             el_b = {k: v for k, v in b.items() if isinstance(v, torch.Tensor)}
             if model_normals is not None:
                 el_b['obj_normals'] = model_normals.index_select(0, el_b['class_id'])
-            out = evaluate_batch(graph, el_b, icp=icp, score=args.score, bop=bop, symmetries=sym_table, verify=verify)
+            out = evaluate_batch(graph, el_b, icp=icp, score=args.score, bop=bop, symmetries=sym_table, verify=verify,
+                                 propose=propose)
             if verify is not None:
                 verify_rows.append((b["class_id"].to(torch.int64), out["verify_best"].to(torch.int64), out["verify_margin"]))
             if bop_log is not None:
@@ -650,6 +721,9 @@ def main(argv=None):
             print(line)
     for line in verify_lines(verify_rows):
         print(line)
+    if propose is not None:
+        for line in propose_lines([r[:2] for r in verify_rows], verify['hypotheses'].max_members):
+            print(line)
     sys.stdout.flush()
     return 0
 

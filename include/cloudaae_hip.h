@@ -1206,6 +1206,79 @@ int cloudaae_depth_fit_counts(int f, int h, int w, const uint16_t *depth_test, c
 int cloudaae_select_pose(int b, int p, const int *counts, const int *seg_total, const int *valid, const double *pose,
                          int mode, int *best, double *score, double *pose_best, double *margin, cloudaae_stream_t stream);
 
+/* ---- pose proposals by point-pair-feature voting ("Pose proposals", has the definition) ---- */
+
+/* Shared by the three calls below.  Arithmetic: double on the float points widened exactly, + - * / sqrt only, no fma,
+ * products and sums in the written order.  No angle is formed on the device: cos_edges [n_angle-1] double holds
+ * cos(k pi / n_angle), k = 1 .. n_angle-1, and bin(c) = #{k : c <= cos_edges[k-1]}; alpha_edges [n_alpha/2 - 1] double holds
+ * cos(k pi / (n_alpha/2)) likewise, and alpha_cs [n_alpha,2] double the cosine and sine of the bin centres
+ * -pi + (j + 1/2) 2 pi / n_alpha.  The host makes the tables; whoever reads the same tables gets the same integers.
+ *   key(p1, n1, p2, n2): d = p2 - p1, len = sqrt((dx dx + dy dy) + dz dz); none when !(len > 0); t = len / dist_step, none
+ *     unless 0 <= t < n_dist; q_d = (int)t; c1 = ((n1.x dx + n1.y dy) + n1.z dz) / len, c2 the same with n2,
+ *     c3 = (n1.x n2.x + n1.y n2.y) + n1.z n2.z; key = ((q_d n_angle + bin(c1)) n_angle + bin(c2)) n_angle + bin(c3).
+ *     Normals are taken as unit vectors and are not normalised again.
+ *   Q(n), the rotation taking n onto +x: row 0 = n; with h = 1 + |n.x| and a = (n.y n.z) / h,
+ *     n.x >= 0: row 1 = (-n.y, 1 - (n.y n.y) / h, -a),    row 2 = (-n.z, -a, 1 - (n.z n.z) / h);
+ *     n.x <  0: row 1 = (-n.y, -(1 - (n.y n.y) / h), a),  row 2 = ( n.z, -a, 1 - (n.z n.z) / h)   (Q(-n), then a half turn about z).
+ *   direction(n1, d): y = (Q10 dx + Q11 dy) + Q12 dz, z = (Q20 dx + Q21 dy) + Q22 dz with Q = Q(n1), r = sqrt(y y + z z); none
+ *     when !(r > 0); else (y / r, z / r). */
+
+/* The pair table of s packed point sets: offsets [s+1] int into xyz [m_total,3] float and normals [m_total,3] double;
+ * pair_offsets [s+1] long long, pair_offsets[i+1] - pair_offsets[i] = M_i^2; dist_step [s] double.  All device memory.  For
+ * the ordered pair (r, i) of set j, entry e = pair_offsets[j] + r M_j + i gets key [e] int = key(p_r, n_r, p_i, n_i), or -1
+ * for i = r, a pair without a key or without a direction; ref [e] int = r; dir [e,2] float = (float) direction(n_r, p_i - p_r),
+ * zeros with key -1.  A set whose offsets leave [0, m_total] or whose pairs leave [0, n_pairs) is not written.  One
+ * launch, one wave per point.  Limits: 1 <= s <= 2^20; 1 <= m_total <= 2^24; 1 <= n_pairs <= 2^28; n_dist >= 1;
+ * 1 <= n_angle <= 64; n_dist n_angle^3 <= 2^24; outside them, or with a null pointer, an error and no launch. */
+int cloudaae_ppf_model_pairs(int s, const int *offsets, const long long *pair_offsets, int m_total, long long n_pairs,
+                             const float *xyz, const double *normals, const double *dist_step, int n_dist, int n_angle,
+                             const double *cos_edges, int *key, int *ref, float *dir, cloudaae_stream_t stream);
+
+/* Voting.  scene [b,n,3] float, scene_normals [b,n,3] double, mask [b,n] uint8 (non-zero: usable), class_id [b] long long.
+ * The models: offsets [nclass+1] int into model_xyz [m_total,3] float / model_normals [m_total,3] double, dist_step [nclass]
+ * double, bucket_start [nclass, n_key+1] int (n_key = n_dist n_angle^3): the entries of key k of class c are
+ * bucket_start[c][k] .. bucket_start[c][k+1] - 1 of entry_ref [n_entries] int (the model point r, local to its set) and
+ * entry_dir [n_entries,2] float.  All device memory.
+ * R = ceil(n / ref_step) reference slots per sample; slot j's reference point is usable point number j ref_step of the
+ * sample in index order (an empty slot when there are fewer).  One workgroup per (sample, slot) keeps m_max n_alpha
+ * int counters in LDS (zeroed).  For every other usable point i with k = key(p_ref, n_ref, p_i, n_i) and u = direction(n_ref,
+ * p_i - p_ref), and every entry e of the bucket clamped to [0, n_entries) with 0 <= entry_ref[e] < M_c:  w = entry_dir[e],
+ * ca = u.y w.y + u.z w.z, sa = u.z w.y - u.y w.z (alpha = alpha_scene - alpha_model), q = #{k : ca <= alpha_edges[k-1]},
+ * bin = sa >= 0 ? n_alpha/2 + q : n_alpha/2 - 1 - q; counter [entry_ref[e] n_alpha + bin] += 1.
+ * A class_id outside [0, nclass), a model with offsets that leave [0, m_total] or M_c outside [1, m_max], or an empty slot
+ * reads no table and leaves all counters 0.
+ * Peak k = 0 .. peaks-1 is the k-th cell by (votes descending, cell index ascending): votes [b,R,peaks] int, model_index
+ * = cell / n_alpha, bin = cell % n_alpha (both -1 where votes = 0) and pose [b,R,peaks,16] double = T_s^-1 Rx T_m (the identity
+ * where votes = 0) with (ca, sa) = alpha_cs[bin], Qm = Q(n_model), Qs = Q(n_ref):
+ *   A[0][k] = Qm[0][k], A[1][k] = ca Qm[1][k] - sa Qm[2][k], A[2][k] = sa Qm[1][k] + ca Qm[2][k];
+ *   R[i][k] = (Qs[0][i] A[0][k] + Qs[1][i] A[1][k]) + Qs[2][i] A[2][k];  t[i] = p_ref[i] - ((R[i][0] pm.x + R[i][1] pm.y) + R[i][2] pm.z).
+ * acc: NULL, or [b,R,m_max,n_alpha] int that receives every counter.  Integer LDS atomics only: the result depends on no
+ * order, batch or run.  Limits: b >= 1; 2 <= n <= 2^20; 1 <= ref_step <= n; b R <= 2^24; 1 <= peaks <= 4 <= m_max n_alpha;
+ * n_alpha even in [2, 128]; 4 m_max n_alpha <= 158 KiB; 0 <= n_entries <= 2^28; the limits of cloudaae_ppf_model_pairs on
+ * n_dist, n_angle and m_total; 1 <= m_max <= m_total.  Outside them, or with a null pointer (acc aside; the entries may be
+ * NULL with n_entries = 0), an error and no launch. */
+int cloudaae_ppf_vote(int b, int n, const float *scene, const double *scene_normals, const uint8_t *mask,
+                      const long long *class_id, int ref_step, int peaks, int nclass, const int *offsets, int m_total, int m_max,
+                      const float *model_xyz, const double *model_normals, const double *dist_step, int n_dist, int n_angle,
+                      int n_alpha, const double *cos_edges, const double *alpha_edges, const double *alpha_cs,
+                      const int *bucket_start, long long n_entries, const int *entry_ref, const float *entry_dir, int *votes,
+                      int *model_index, int *bin, double *pose, int *acc, cloudaae_stream_t stream);
+
+/* Greedy clustering of c candidates per sample: votes [b,c] int, pose [b,c,16] double, class_id [b] long long,
+ * trans_thresh2 [nclass] double (the squared translation threshold of each class), rot_bound = 1 + 2 cos(rot_thresh).
+ * Candidates with votes > 0 are visited by (votes descending, index ascending).  A candidate b joins the first cluster,
+ * in founding order, whose representative a has (dx dx + dy dy) + dz dz <= trans_thresh2 (d = t_a - t_b) and
+ * (r_0 + r_1) + r_2 >= rot_bound, r_i = (Ra[i][0] Rb[i][0] + Ra[i][1] Rb[i][1]) + Ra[i][2] Rb[i][2]; otherwise it founds one
+ * and is its representative.  A cluster's score is the sum of its members' votes.  A class_id outside [0, nclass) gives no
+ * cluster.  Slot t = 0 .. top-1 is the t-th cluster by (score descending, founding order ascending): pose_out [b,top,16] =
+ * its representative's pose bit for bit, rot_axag [b,top,3] double = the log map of "Pose refinement", trans [b,top,3]
+ * float, score [b,top] int, valid [b,top] int = 1; past the clusters the identity, zeros and valid 0.  One launch, one wave
+ * per sample, no atomics.  Limits: 1 <= b <= 2^24; 1 <= c <= 4096; 1 <= top <= 64; nclass >= 1; rot_bound a number.
+ * Outside them, or with a null pointer, an error and no launch. */
+int cloudaae_ppf_cluster(int b, int c, const int *votes, const double *pose, const long long *class_id, int nclass,
+                         const double *trans_thresh2, double rot_bound, int top, double *pose_out, double *rot_axag, float *trans,
+                         int *score, int *valid, cloudaae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
