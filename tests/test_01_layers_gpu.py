@@ -346,8 +346,18 @@ def test_losses_vs_oracle(hip):
     got, gper = angular_distance_taylor.get_rotation_error(pd, lab.cuda())
     got.backward()
     assert got.dtype == torch.float32 and gper.dtype == torch.float64
-    assert _rel(gper, wper) < 1e-12 and abs(float(got) - float(want)) < 1e-6
-    assert _rel(pd.grad, p32.grad) < 1e-5
+    assert abs(float(got) - float(want)) < 1e-6
+    # every row by itself against the 50-digit reference, with the bounds of tests/test_34_step_paths_gpu.py: the rows that
+    # nearly coincide with their label (clipped) and the opposite ones are tiny next to a maximum set by angles near 1
+    import step_reference as SR
+    ref = SR.rotation(p32.detach().numpy(), lab.numpy(), SR.MP)
+    assert ref.clipped[2] == 1 and (np.abs(np.abs(ref.t) - SR.LIM) > 1e-9).all()
+    errs = SR.rotation_errors({"theta": gper.cpu().numpy(), "rot_loss": np.float32(float(got)), "drot": pd.grad.cpu().numpy(),
+                               "drot_scale": 1.0 / B}, ref)
+    assert all(v <= SR.allowed_of(k) for k, v in errs.items()), errs
+    # (the oracle itself, float64 torch, holds these bounds only on the well-conditioned rows)
+    easy = (ref.clipped == 0) & (np.abs(ref.t) < 0.99)
+    assert _rel(gper.cpu()[easy], wper.detach()[easy]) < 1e-12 and _rel(pd.grad.cpu()[easy], p32.grad[easy]) < 1e-5
     R = angular_distance_taylor.exponential_map(lab.cuda())
     assert _rel(R, MO.exponential_map(lab)) < 1e-14
 
