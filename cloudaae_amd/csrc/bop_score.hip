@@ -24,14 +24,6 @@
 
 namespace cloudaae {
 
-// no packed-fp32 instruction in these kernels (tests/test_isa_rules.py; csrc/Makefile says why).  By attribute, as
-// render.hip does; the atomics and the ballot are the compiler's builtins for the reason given there.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define BS_NOPK __attribute__((target("no-packed-fp32-ops")))
-#else
-#define BS_NOPK
-#endif
-
 typedef unsigned long long u64;
 
 constexpr int VS_BLOCK = 256;
@@ -53,12 +45,7 @@ struct VsdArgs {
     int *inter, *uni, *over, *visib_gt;
 };
 
-BS_NOPK __device__ __forceinline__ int vs_count(bool pred)
-{
-    return __builtin_popcountll(__builtin_amdgcn_ballot_w64(pred));
-}
-
-BS_NOPK __global__ __launch_bounds__(VS_BLOCK) void vsd_counts_kernel(VsdArgs a)
+__global__ __launch_bounds__(VS_BLOCK) void vsd_counts_kernel(VsdArgs a)
 {
     __shared__ int red[VS_WAVES][VS_SLOTS];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -95,7 +82,7 @@ BS_NOPK __global__ __launch_bounds__(VS_BLOCK) void vsd_counts_kernel(VsdArgs a)
             valid_t |= (unsigned)vt << i;
             vis_g |= (unsigned)vg << i;
         }
-        n_vis += vs_count(vg);
+        n_vis += wave_count(vg);
     }
 
     double tau[VS_MAX_K];
@@ -123,12 +110,12 @@ BS_NOPK __global__ __launch_bounds__(VS_BLOCK) void vsd_counts_kernel(VsdArgs a)
             const bool both = vg && ve;
             const u64 both_mask = __builtin_amdgcn_ballot_w64(both);
             n_inter += __builtin_popcountll(both_mask);
-            n_union += vs_count(vg || ve);
+            n_union += wave_count(vg || ve);
             if (both_mask) {                       // (wave-uniform)
 #pragma unroll
                 for (int k = 0; k < VS_MAX_K; ++k)
                     if (k < a.k)
-                        n_over[k] += vs_count(both && diff >= tau[k]);
+                        n_over[k] += wave_count(both && diff >= tau[k]);
             }
         }
         if (lane == 0) {
@@ -162,18 +149,18 @@ constexpr int MD_WAVES = MD_BLOCK / 64;
 
 static int md_tiles(int m) { return ceil_div(m, MD_BLOCK); }
 
-BS_NOPK __device__ __forceinline__ int md_num_sym(const int *num_sym, int s, int smax)
+__device__ __forceinline__ int md_num_sym(const int *num_sym, int s, int smax)
 {
     return min(max(num_sym[s], 1), smax);
 }
 
 // acc [b*p][smax][2]: the bit patterns of max_i |E x_i - G S x_i|^2 and of the largest squared pixel distance
-BS_NOPK __global__ __launch_bounds__(MD_BLOCK) void pose_max_dist_kernel(int p, int m, int tiles, const float *__restrict__ model,
-                                                                        int ps, long long cs, const double *__restrict__ est,
-                                                                        const double *__restrict__ gt, int smax,
-                                                                        const int *__restrict__ num_sym,
-                                                                        const double *__restrict__ sym,
-                                                                        const float *__restrict__ intrinsics, u64 *acc)
+__global__ __launch_bounds__(MD_BLOCK) void pose_max_dist_kernel(int p, int m, int tiles, const float *__restrict__ model,
+                                                                int ps, long long cs, const double *__restrict__ est,
+                                                                const double *__restrict__ gt, int smax,
+                                                                const int *__restrict__ num_sym,
+                                                                const double *__restrict__ sym,
+                                                                const float *__restrict__ intrinsics, u64 *acc)
 {
     __shared__ u64 red[MD_WAVES][2];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -229,9 +216,9 @@ BS_NOPK __global__ __launch_bounds__(MD_BLOCK) void pose_max_dist_kernel(int p, 
 }
 
 // one lane per (sample, pose): the minimum over the symmetries (exact on the bits), then the square root
-BS_NOPK __global__ void pose_max_dist_finish_kernel(int n, int p, int smax, const int *__restrict__ num_sym,
-                                                    const u64 *__restrict__ acc, double *__restrict__ mssd,
-                                                    double *__restrict__ mspd)
+__global__ void pose_max_dist_finish_kernel(int n, int p, int smax, const int *__restrict__ num_sym,
+                                            const u64 *__restrict__ acc, double *__restrict__ mssd,
+                                            double *__restrict__ mspd)
 {
     const int sp = blockIdx.x * blockDim.x + threadIdx.x;
     if (sp >= n)

@@ -170,6 +170,12 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
+// the number of lanes of the wave whose predicate holds, the same value in every lane
+__device__ __forceinline__ int wave_count(bool pred)
+{
+    return __builtin_popcountll(__builtin_amdgcn_ballot_w64(pred));
+}
+
 // max of a 64-bit key over the wave, the same value in every lane.  Inside a row of 16 lanes the partner comes through
 // DPP (quad swaps, then the half-row and row mirrors: after the quad steps a quad is uniform, so the mirrors act as
 // "xor 4" and "xor 8"); the four row maxima are read as scalars (v_readlane) and meet on the scalar unit -- no trip

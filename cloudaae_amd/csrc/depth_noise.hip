@@ -19,14 +19,6 @@
 
 namespace cloudaae {
 
-// no packed-fp32 instruction in these kernels (tests/test_isa_rules.py; csrc/Makefile says why).  By attribute, as
-// render.hip does; the atomics and the ballot are the compiler's builtins for the reason given there.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define DN_NOPK __attribute__((target("no-packed-fp32-ops")))
-#else
-#define DN_NOPK
-#endif
-
 typedef unsigned long long u64;
 
 constexpr int DN_BLOCK = 256;
@@ -45,20 +37,15 @@ struct DnFrame {
     double fx, fy, cx, cy, factor;
 };
 
-DN_NOPK __device__ __forceinline__ int dn_count(bool pred)
-{
-    return __builtin_popcountll(__builtin_amdgcn_ballot_w64(pred));
-}
-
 // adds the workgroup's totals of N per-lane predicates into dst[0 .. N): every lane of the workgroup must call it
 template <int N>
-DN_NOPK __device__ __forceinline__ void dn_add_counts(const bool (&pred)[N], int *dst)
+__device__ __forceinline__ void dn_add_counts(const bool (&pred)[N], int *dst)
 {
     __shared__ int red[DN_WAVES][N];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-        const int n = dn_count(pred[i]);
+        const int n = wave_count(pred[i]);
         if (lane == 0)
             red[wv][i] = n;
     }
@@ -74,7 +61,7 @@ DN_NOPK __device__ __forceinline__ void dn_add_counts(const bool (&pred)[N], int
 }
 
 // P = (((u - cx) dm) / fx, ((v - cy) dm) / fy, dm) with dm = d / factor
-DN_NOPK __device__ __forceinline__ void dn_backproject(const DnFrame &fr, int u, int v, unsigned short d, double (&p)[3])
+__device__ __forceinline__ void dn_backproject(const DnFrame &fr, int u, int v, unsigned short d, double (&p)[3])
 {
     const double dm = (double)d / fr.factor;
     p[0] = (((double)u - fr.cx) * dm) / fr.fx;
@@ -83,7 +70,7 @@ DN_NOPK __device__ __forceinline__ void dn_backproject(const DnFrame &fr, int u,
 }
 
 // the neighbour (u, v) of a pixel with label l: valid when inside the image, with depth and with that label
-DN_NOPK __device__ __forceinline__ bool dn_tap(const DnFrame &fr, int u, int v, unsigned char l, double (&p)[3])
+__device__ __forceinline__ bool dn_tap(const DnFrame &fr, int u, int v, unsigned char l, double (&p)[3])
 {
     if (u < 0 || u >= fr.w || v < 0 || v >= fr.h)
         return false;
@@ -96,8 +83,8 @@ DN_NOPK __device__ __forceinline__ bool dn_tap(const DnFrame &fr, int u, int v, 
 }
 
 // the difference along one axis: central when both neighbours are valid, one-sided with the valid one, else none
-DN_NOPK __device__ __forceinline__ bool dn_axis(const DnFrame &fr, int u, int v, int du, int dv, unsigned char l,
-                                               const double (&centre)[3], double (&g)[3])
+__device__ __forceinline__ bool dn_axis(const DnFrame &fr, int u, int v, int du, int dv, unsigned char l,
+                                       const double (&centre)[3], double (&g)[3])
 {
     double lo[3], hi[3];
     const bool vlo = dn_tap(fr, u - du, v - dv, l, lo), vhi = dn_tap(fr, u + du, v + dv, l, hi);
@@ -109,14 +96,14 @@ DN_NOPK __device__ __forceinline__ bool dn_axis(const DnFrame &fr, int u, int v,
     return true;
 }
 
-DN_NOPK __device__ __forceinline__ double dn_dot(const double (&a)[3], const double (&b)[3])
+__device__ __forceinline__ double dn_dot(const double (&a)[3], const double (&b)[3])
 {
     return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
 }
 
 // The slope at pixel (u, v), whose depth d is not 0.  false: the pixel is flat (normal zeros, theta 0).  Otherwise n is
 // the unit normal turned towards the camera and theta its angle to the viewing ray, in [0, pi / 2].
-DN_NOPK __device__ __forceinline__ bool dn_slope(const DnFrame &fr, int u, int v, unsigned short d, double (&n)[3], double &theta)
+__device__ __forceinline__ bool dn_slope(const DnFrame &fr, int u, int v, unsigned short d, double (&n)[3], double &theta)
 {
     n[0] = n[1] = n[2] = 0.0;
     theta = 0.0;
@@ -145,8 +132,8 @@ DN_NOPK __device__ __forceinline__ bool dn_slope(const DnFrame &fr, int u, int v
     return true;
 }
 
-DN_NOPK __device__ __forceinline__ DnFrame dn_frame(int f, int h, int w, const unsigned short *depth, const unsigned char *label,
-                                                   const float *intrinsics)
+__device__ __forceinline__ DnFrame dn_frame(int f, int h, int w, const unsigned short *depth, const unsigned char *label,
+                                           const float *intrinsics)
 {
     DnFrame fr;
     const size_t hw = (size_t)h * w;
@@ -159,12 +146,12 @@ DN_NOPK __device__ __forceinline__ DnFrame dn_frame(int f, int h, int w, const u
 }
 
 // grid = f * tiles: workgroup b takes pixels (b % tiles) * 256 .. of frame b / tiles
-DN_NOPK __global__ __launch_bounds__(DN_BLOCK) void depth_normals_kernel(int h, int w, int tiles,
-                                                                        const unsigned short *__restrict__ depth,
-                                                                        const unsigned char *__restrict__ label,
-                                                                        const float *__restrict__ intrinsics,
-                                                                        float *__restrict__ normals, float *__restrict__ theta_out,
-                                                                        int *__restrict__ flat_counts)
+__global__ __launch_bounds__(DN_BLOCK) void depth_normals_kernel(int h, int w, int tiles,
+                                                                const unsigned short *__restrict__ depth,
+                                                                const unsigned char *__restrict__ label,
+                                                                const float *__restrict__ intrinsics,
+                                                                float *__restrict__ normals, float *__restrict__ theta_out,
+                                                                int *__restrict__ flat_counts)
 {
     const int f = blockIdx.x / tiles, tile = blockIdx.x % tiles;
     const int hw = h * w;
@@ -192,14 +179,14 @@ struct DnSensor {
     u64 seed, first_frame;
 };
 
-DN_NOPK __global__ __launch_bounds__(DN_BLOCK) void depth_sensor_noise_kernel(int h, int w, int tiles,
-                                                                             const unsigned short *__restrict__ depth,
-                                                                             const unsigned char *__restrict__ label,
-                                                                             const float *__restrict__ intrinsics, DnSensor s,
-                                                                             unsigned short *__restrict__ depth_out,
-                                                                             unsigned char *__restrict__ label_out,
-                                                                             int *__restrict__ counts,
-                                                                             double *__restrict__ z_noisy)
+__global__ __launch_bounds__(DN_BLOCK) void depth_sensor_noise_kernel(int h, int w, int tiles,
+                                                                     const unsigned short *__restrict__ depth,
+                                                                     const unsigned char *__restrict__ label,
+                                                                     const float *__restrict__ intrinsics, DnSensor s,
+                                                                     unsigned short *__restrict__ depth_out,
+                                                                     unsigned char *__restrict__ label_out,
+                                                                     int *__restrict__ counts,
+                                                                     double *__restrict__ z_noisy)
 {
     const int f = blockIdx.x / tiles, tile = blockIdx.x % tiles;
     const int hw = h * w;

@@ -16,14 +16,6 @@
 
 namespace cloudaae {
 
-// no packed-fp32 instruction in these kernels (tests/test_isa_rules.py; csrc/Makefile says why).  By attribute, as
-// render.hip and depth_noise.hip do; the ballot is the compiler's builtin for the reason given in render.hip.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define FC_NOPK __attribute__((target("no-packed-fp32-ops")))
-#else
-#define FC_NOPK
-#endif
-
 typedef unsigned long long u64;
 
 constexpr int FC_BLOCK = 256;
@@ -56,7 +48,7 @@ struct FcArgs {
 
 // the frame cloud c reads, or -1: a frame outside [0, f) or a global index outside [0, 2^39) makes the cloud the n = 0
 // case, and nothing of the frames is read for it
-FC_NOPK __device__ __forceinline__ int fc_frame(const FcArgs &a, int c)
+__device__ __forceinline__ int fc_frame(const FcArgs &a, int c)
 {
     const int fr = a.frame_of[c];
     const long long g = a.index[c];
@@ -64,7 +56,7 @@ FC_NOPK __device__ __forceinline__ int fc_frame(const FcArgs &a, int c)
 }
 
 // whether pixel p of the tile's pass belongs to the mask (p < h w is part of it)
-FC_NOPK __device__ __forceinline__ bool fc_masked(const FcArgs &a, int fr, int want, int p, unsigned short &d)
+__device__ __forceinline__ bool fc_masked(const FcArgs &a, int fr, int want, int p, unsigned short &d)
 {
     d = 0;
     if (fr < 0 || p >= a.h * a.w)
@@ -77,7 +69,7 @@ FC_NOPK __device__ __forceinline__ bool fc_masked(const FcArgs &a, int fr, int w
 }
 
 // grid = c * tiles: workgroup b counts the masked pixels of tile b % tiles of cloud b / tiles
-FC_NOPK __global__ __launch_bounds__(FC_BLOCK) void frame_clouds_count_kernel(FcArgs a)
+__global__ __launch_bounds__(FC_BLOCK) void frame_clouds_count_kernel(FcArgs a)
 {
     __shared__ int red[FC_WAVES];
     const int c = blockIdx.x / a.tiles, tile = blockIdx.x % a.tiles;
@@ -104,7 +96,7 @@ FC_NOPK __global__ __launch_bounds__(FC_BLOCK) void frame_clouds_count_kernel(Fc
 
 // grid = c: one workgroup turns the cloud's tile counts into their exclusive prefix, 256 at a time (a Hillis-Steele
 // scan in LDS), and writes n and num_distinct
-FC_NOPK __global__ __launch_bounds__(FC_BLOCK) void frame_clouds_scan_kernel(FcArgs a)
+__global__ __launch_bounds__(FC_BLOCK) void frame_clouds_scan_kernel(FcArgs a)
 {
     __shared__ int buf[2][FC_BLOCK];
     const int c = blockIdx.x, tid = threadIdx.x;
@@ -135,7 +127,7 @@ FC_NOPK __global__ __launch_bounds__(FC_BLOCK) void frame_clouds_scan_kernel(FcA
 }
 
 // row j of cloud c: the back-projection of pixel p with depth d
-FC_NOPK __device__ __forceinline__ void fc_write_row(const FcArgs &a, int c, int fr, int j, int p, unsigned short d)
+__device__ __forceinline__ void fc_write_row(const FcArgs &a, int c, int fr, int j, int p, unsigned short d)
 {
     const float *k = a.intrinsics + 5 * (size_t)fr;
     const float fx = k[0], fy = k[1], cx = k[2], cy = k[3], factor = k[4];
@@ -151,7 +143,7 @@ FC_NOPK __device__ __forceinline__ void fc_write_row(const FcArgs &a, int c, int
 }
 
 // grid = c * tiles, as the count: every masked lane forms its rank and decides whether its pixel is a row
-FC_NOPK __global__ __launch_bounds__(FC_BLOCK) void frame_clouds_scatter_kernel(FcArgs a)
+__global__ __launch_bounds__(FC_BLOCK) void frame_clouds_scatter_kernel(FcArgs a)
 {
     __shared__ int part[FC_PASSES * FC_WAVES];
     const int c = blockIdx.x / a.tiles, tile = blockIdx.x % a.tiles;
@@ -204,7 +196,7 @@ FC_NOPK __global__ __launch_bounds__(FC_BLOCK) void frame_clouds_scatter_kernel(
 }
 
 // one lane per (cloud, row): the fallback rows of an empty mask and the re-drawn rows j >= n of a small one
-FC_NOPK __global__ __launch_bounds__(FC_BLOCK) void frame_clouds_fill_kernel(FcArgs a)
+__global__ __launch_bounds__(FC_BLOCK) void frame_clouds_fill_kernel(FcArgs a)
 {
     const long long gl = (long long)blockIdx.x * FC_BLOCK + threadIdx.x;
     if (gl >= (long long)a.c * a.rows)

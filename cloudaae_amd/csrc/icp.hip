@@ -34,14 +34,6 @@ using namespace cloudaae;
 
 namespace {
 
-// no packed-fp32 instruction in these kernels (tests/test_isa_rules.py; csrc/Makefile says why).  The host pass
-// does not know the feature: the attribute goes to the device pass only.
-#ifdef __HIP_DEVICE_COMPILE__
-#define ICP_NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define ICP_NO_PACKED_FP32
-#endif
-
 constexpr int ICP_THREADS = 512;
 constexpr int ICP_WAVES = ICP_THREADS / 64;
 constexpr int ICP_PER_LANE = 8;
@@ -406,7 +398,7 @@ __device__ __forceinline__ bool icp_estimate(const double *sums, const double *c
 // PLANE: nrm [b,n,3] = the target points' normals; inverse != 0: rot / trans and the results are the target -> source
 // pose (inverted on entry and on exit).  Point to point takes nrm = nullptr, inverse = 0.
 template <bool PLANE>
-__global__ void __launch_bounds__(ICP_THREADS) ICP_NO_PACKED_FP32
+__global__ void __launch_bounds__(ICP_THREADS)
 icp_kernel(const double *__restrict__ nrm_all, int inverse, int m, const float *__restrict__ src, int sps, long long scs, int n, const float *__restrict__ dst,
                int dps, long long dcs, const float *__restrict__ rot, const float *__restrict__ trans, double radius,
                double decay, int rounds, int max_it, double rel_fit, double rel_rmse, int hbits,
@@ -504,37 +496,19 @@ icp_kernel(const double *__restrict__ nrm_all, int inverse, int m, const float *
                 icp_apply(L.bc, (double)x[0], (double)x[1], (double)x[2], P[k][0], P[k][1], P[k][2]);
             }
         }
-        icp_match<PLANE>(L, P, m, rho2, inv_h, reach, mask, ctr, nrm);
+        // one pass = one matching, then thread 0's statistics and update; the first pass of a round is not an iteration
         int its = 0;
-        if (tid == 0) {
-            fit = sums[0] / (double)m;
-            rmse = sums[0] > 0.0 ? sqrt(sums[D2] / sums[0]) : 0.0;
-            const bool cont = rounds > 0 && max_it > 0;
-            L.bc[24] = cont ? 1.0 : 0.0;
-            L.bc[25] = 0.0;
-            if (cont && sums[0] > 0.0 && icp_estimate<PLANE>(sums, ctr, L.bc + 12)) {
-                icp_compose(L.bc + 12, L.bc);
-                L.bc[25] = 1.0;
-            }
-        }
-        __syncthreads();
-        for (int it = 0; it < max_it; ++it) {
-            if (L.bc[24] == 0.0)
-                break;
-            if (L.bc[25] != 0.0) {
-#pragma unroll
-                for (int k = 0; k < ICP_PER_LANE; ++k)
-                    icp_apply(L.bc + 12, P[k][0], P[k][1], P[k][2], P[k][0], P[k][1], P[k][2]);
-            }
+        auto pass = [&](bool first) __attribute__((always_inline)) {
             icp_match<PLANE>(L, P, m, rho2, inv_h, reach, mask, ctr, nrm);
-            ++its;
+            if (!first)
+                ++its;
             if (tid == 0) {
                 const double f = sums[0] / (double)m;
                 const double e = sums[0] > 0.0 ? sqrt(sums[D2] / sums[0]) : 0.0;
-                const bool converged = fabs(fit - f) < rel_fit && fabs(rmse - e) < rel_rmse;
+                const bool converged = !first && fabs(fit - f) < rel_fit && fabs(rmse - e) < rel_rmse;
                 fit = f;
                 rmse = e;
-                const bool cont = !converged && its < max_it;
+                const bool cont = first ? rounds > 0 && max_it > 0 : !converged && its < max_it;
                 L.bc[24] = cont ? 1.0 : 0.0;
                 L.bc[25] = 0.0;
                 if (cont && sums[0] > 0.0 && icp_estimate<PLANE>(sums, ctr, L.bc + 12)) {
@@ -543,6 +517,29 @@ icp_kernel(const double *__restrict__ nrm_all, int inverse, int m, const float *
                 }
             }
             __syncthreads();
+        };
+        auto move = [&]() __attribute__((always_inline)) {
+            if (L.bc[25] != 0.0) {
+#pragma unroll
+                for (int k = 0; k < ICP_PER_LANE; ++k)
+                    icp_apply(L.bc + 12, P[k][0], P[k][1], P[k][2], P[k][0], P[k][1], P[k][2]);
+            }
+        };
+        // The pass is expanded once for point to plane and twice for point to point, by measurement: the kernels are bound by
+        // instruction fetch on one lane's path, and each is fastest in that form (profiles/notes_no_packed_fp32_build.md).
+        if constexpr (PLANE) {
+            for (bool first = true;; first = false) {
+                pass(first);
+                if (its >= max_it || L.bc[24] == 0.0)
+                    break;
+                move();
+            }
+        } else {
+            pass(true);
+            while (its < max_it && L.bc[24] != 0.0) {
+                move();
+                pass(false);
+            }
         }
         if (tid == 0 && rounds > 0)
             it_out[(long long)c * rounds + r] = its;
@@ -569,7 +566,7 @@ icp_kernel(const double *__restrict__ nrm_all, int inverse, int m, const float *
     }
 }
 
-__global__ void ICP_NO_PACKED_FP32 f64_to_f32_kernel(long long n, const double *__restrict__ x, float *__restrict__ y)
+__global__ void f64_to_f32_kernel(long long n, const double *__restrict__ x, float *__restrict__ y)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n)

@@ -26,17 +26,9 @@ constexpr long long MS_MAX_TOTAL = 1ll << 28;      // vertices, triangles and sa
 constexpr int MS_MAX_MESHES = 65535;
 typedef unsigned long long u64;
 
-// no packed-fp32 instruction in these kernels (tests/test_isa_rules.py; csrc/Makefile says why).  By attribute, as
-// pose_sample.hip does: the Makefile's blob hash is pinned by profiles/roofline_traffic.json.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MS_NOPK __attribute__((target("no-packed-fp32-ops")))
-#else
-#define MS_NOPK
-#endif
-
 // the mesh that holds packed triangle t: the last s with offsets[s] <= t (empty meshes are stepped over); s_count when
 // t lies past the last mesh
-MS_NOPK __device__ __forceinline__ int ms_mesh_of(const int *__restrict__ offsets, int s_count, int t)
+__device__ __forceinline__ int ms_mesh_of(const int *__restrict__ offsets, int s_count, int t)
 {
     int lo = 0, hi = s_count + 1;
     while (lo < hi) {
@@ -51,7 +43,7 @@ MS_NOPK __device__ __forceinline__ int ms_mesh_of(const int *__restrict__ offset
 
 // the three corners of packed triangle t of a mesh whose vertices are v0 .. v1 of `vertices`, widened; false when an
 // index lies outside the mesh
-MS_NOPK __device__ __forceinline__ bool ms_corners(const int *__restrict__ triangles, int t, int v0, int v1, int ids[3])
+__device__ __forceinline__ bool ms_corners(const int *__restrict__ triangles, int t, int v0, int v1, int ids[3])
 {
     bool ok = true;
 #pragma unroll
@@ -64,7 +56,7 @@ MS_NOPK __device__ __forceinline__ bool ms_corners(const int *__restrict__ trian
 }
 
 // n = e1 x e2, each component (p q) - (r s), and A2 = sqrt((nx^2 + ny^2) + nz^2), in double
-MS_NOPK __device__ __forceinline__ double ms_normal(const float *__restrict__ vertices, const int ids[3], double n[3])
+__device__ __forceinline__ double ms_normal(const float *__restrict__ vertices, const int ids[3], double n[3])
 {
     double a[3], e1[3], e2[3];
 #pragma unroll
@@ -80,8 +72,8 @@ MS_NOPK __device__ __forceinline__ double ms_normal(const float *__restrict__ ve
 }
 
 // a mesh's ranges, taken as empty when the offsets do not describe ranges inside the packed arrays
-MS_NOPK __device__ __forceinline__ bool ms_ranges(const int *__restrict__ vert_offsets, const int *__restrict__ tri_offsets, int s, int nv,
-                                          int nt, int &v0, int &v1, int &t0, int &t1)
+__device__ __forceinline__ bool ms_ranges(const int *__restrict__ vert_offsets, const int *__restrict__ tri_offsets, int s, int nv,
+                                  int nt, int &v0, int &v1, int &t0, int &t1)
 {
     v0 = vert_offsets[s];
     v1 = vert_offsets[s + 1];
@@ -91,11 +83,11 @@ MS_NOPK __device__ __forceinline__ bool ms_ranges(const int *__restrict__ vert_o
 }
 
 // pass 1, one lane per triangle: A2 -> a2 (0 for a triangle that gets no weight), the mesh's maximum, its invalid count
-MS_NOPK __global__ __launch_bounds__(MS_SCAN_BLOCK) void mesh_area_kernel(int s_count, const int *__restrict__ vert_offsets,
-                                                                  const int *__restrict__ tri_offsets, int nv, int nt,
-                                                                  const float *__restrict__ vertices,
-                                                                  const int *__restrict__ triangles, double *__restrict__ a2,
-                                                                  u64 *a2max, int *invalid)
+__global__ __launch_bounds__(MS_SCAN_BLOCK) void mesh_area_kernel(int s_count, const int *__restrict__ vert_offsets,
+                                                          const int *__restrict__ tri_offsets, int nv, int nt,
+                                                          const float *__restrict__ vertices,
+                                                          const int *__restrict__ triangles, double *__restrict__ a2,
+                                                          u64 *a2max, int *invalid)
 {
     const int t = blockIdx.x * MS_SCAN_BLOCK + threadIdx.x;
     double area = 0.0;
@@ -140,7 +132,7 @@ MS_NOPK __global__ __launch_bounds__(MS_SCAN_BLOCK) void mesh_area_kernel(int s_
 }
 
 // inclusive scan of one value per lane over the workgroup
-MS_NOPK __device__ __forceinline__ u64 ms_block_scan(u64 v, u64 (&buf)[2][MS_SCAN_BLOCK])
+__device__ __forceinline__ u64 ms_block_scan(u64 v, u64 (&buf)[2][MS_SCAN_BLOCK])
 {
     const int i = threadIdx.x;
     int cur = 0;
@@ -158,10 +150,10 @@ MS_NOPK __device__ __forceinline__ u64 ms_block_scan(u64 v, u64 (&buf)[2][MS_SCA
 }
 
 // pass 2: w = floor(A2 / A2max * 2^32), its scan inside the block of B packed triangles, the block's sum
-MS_NOPK __global__ __launch_bounds__(MS_SCAN_BLOCK) void mesh_weight_kernel(int s_count, const int *__restrict__ tri_offsets, int nt,
-                                                                    const double *__restrict__ a2,
-                                                                    const u64 *__restrict__ a2max, u64 *__restrict__ weights,
-                                                                    u64 *__restrict__ local, u64 *__restrict__ block_sum)
+__global__ __launch_bounds__(MS_SCAN_BLOCK) void mesh_weight_kernel(int s_count, const int *__restrict__ tri_offsets, int nt,
+                                                            const double *__restrict__ a2,
+                                                            const u64 *__restrict__ a2max, u64 *__restrict__ weights,
+                                                            u64 *__restrict__ local, u64 *__restrict__ block_sum)
 {
     __shared__ u64 buf[2][MS_SCAN_BLOCK];
     const int t = blockIdx.x * MS_SCAN_BLOCK + threadIdx.x;
@@ -183,8 +175,8 @@ MS_NOPK __global__ __launch_bounds__(MS_SCAN_BLOCK) void mesh_weight_kernel(int 
 }
 
 // pass 3, one workgroup: block_prefix = the exclusive scan of the block sums, B at a time with a carry
-MS_NOPK __global__ __launch_bounds__(MS_SCAN_BLOCK) void mesh_block_prefix_kernel(int blocks, const u64 *__restrict__ block_sum,
-                                                                          u64 *__restrict__ block_prefix)
+__global__ __launch_bounds__(MS_SCAN_BLOCK) void mesh_block_prefix_kernel(int blocks, const u64 *__restrict__ block_sum,
+                                                                  u64 *__restrict__ block_prefix)
 {
     __shared__ u64 buf[2][MS_SCAN_BLOCK];
     __shared__ u64 carry_s;
@@ -204,9 +196,9 @@ MS_NOPK __global__ __launch_bounds__(MS_SCAN_BLOCK) void mesh_block_prefix_kerne
 }
 
 // pass 4: cum[t] = (the packed scan at t) - (the packed scan before the mesh's first triangle)
-MS_NOPK __global__ __launch_bounds__(MS_SCAN_BLOCK) void mesh_cum_kernel(int s_count, const int *__restrict__ tri_offsets, int nt,
-                                                                 const u64 *__restrict__ local,
-                                                                 const u64 *__restrict__ block_prefix, u64 *__restrict__ cum)
+__global__ __launch_bounds__(MS_SCAN_BLOCK) void mesh_cum_kernel(int s_count, const int *__restrict__ tri_offsets, int nt,
+                                                         const u64 *__restrict__ local,
+                                                         const u64 *__restrict__ block_prefix, u64 *__restrict__ cum)
 {
     const int t = blockIdx.x * MS_SCAN_BLOCK + threadIdx.x;
     if (t >= nt)
@@ -222,13 +214,13 @@ MS_NOPK __global__ __launch_bounds__(MS_SCAN_BLOCK) void mesh_cum_kernel(int s_c
 }
 
 // one lane per sample: sample j of mesh s
-MS_NOPK __global__ __launch_bounds__(64) void mesh_sample_kernel(int s_count, const int *__restrict__ vert_offsets,
-                                                         const int *__restrict__ tri_offsets, int nv, int nt,
-                                                         const float *__restrict__ vertices, const float *__restrict__ colors,
-                                                         const int *__restrict__ triangles, const u64 *__restrict__ cum,
-                                                         const int *__restrict__ mesh_ids, int n, u64 first, u64 seed,
-                                                         float *__restrict__ xyzrgb, int *__restrict__ tri,
-                                                         double *__restrict__ normal)
+__global__ __launch_bounds__(64) void mesh_sample_kernel(int s_count, const int *__restrict__ vert_offsets,
+                                                 const int *__restrict__ tri_offsets, int nv, int nt,
+                                                 const float *__restrict__ vertices, const float *__restrict__ colors,
+                                                 const int *__restrict__ triangles, const u64 *__restrict__ cum,
+                                                 const int *__restrict__ mesh_ids, int n, u64 first, u64 seed,
+                                                 float *__restrict__ xyzrgb, int *__restrict__ tri,
+                                                 double *__restrict__ normal)
 {
     const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
     if (i >= (long long)s_count * n)
@@ -299,10 +291,10 @@ MS_NOPK __global__ __launch_bounds__(64) void mesh_sample_kernel(int s_count, co
 
 // dst[set, j, c] = src[set, idx[set, j], c]; an index outside the set's rows gives zeros
 template <typename T>
-MS_NOPK __global__ __launch_bounds__(256) void mesh_gather_rows_kernel(long long total, int k, int cols, const int *__restrict__ idx,
-                                                               long long rows_per_set, const T *__restrict__ src,
-                                                               long long src_row_stride, T *__restrict__ dst,
-                                                               long long dst_row_stride)
+__global__ __launch_bounds__(256) void mesh_gather_rows_kernel(long long total, int k, int cols, const int *__restrict__ idx,
+                                                       long long rows_per_set, const T *__restrict__ src,
+                                                       long long src_row_stride, T *__restrict__ dst,
+                                                       long long dst_row_stride)
 {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= total)

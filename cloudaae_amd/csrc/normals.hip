@@ -21,13 +21,6 @@ using namespace cloudaae;
 
 namespace {
 
-// no packed-fp32 instruction in these kernels (tests/test_isa_rules.py; csrc/Makefile says why)
-#ifdef __HIP_DEVICE_COMPILE__
-#define NRM_NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define NRM_NO_PACKED_FP32
-#endif
-
 constexpr int NRM_THREADS = 1024;
 constexpr int NRM_GRID = 16;                               // cells per axis
 constexpr int NRM_CELLS = NRM_GRID * NRM_GRID * NRM_GRID;
@@ -80,7 +73,7 @@ __device__ __forceinline__ int nrm_cell(const NrmGrid &G, float x, float y, floa
            nrm_axis((double)x, G.ox, G.inv_h);
 }
 
-__global__ NRM_NO_PACKED_FP32 __launch_bounds__(NRM_THREADS) void nrm_grid_kernel(
+__global__ __launch_bounds__(NRM_THREADS) void nrm_grid_kernel(
     const int *__restrict__ off, long long m, const float *__restrict__ xyz, int ps, float radius,
     NrmGrid *__restrict__ grids, int *__restrict__ cell_start, float4 *__restrict__ tmp, float4 *__restrict__ sorted)
 {
@@ -254,7 +247,7 @@ __device__ inline void nrm_jacobi3(double a00, double a01, double a02, double a1
     w[1] = fmax(lo01, fmin(hi01, d2));
 }
 
-__global__ NRM_NO_PACKED_FP32 __launch_bounds__(NRM_QBLOCK) void nrm_query_kernel(
+__global__ __launch_bounds__(NRM_QBLOCK) void nrm_query_kernel(
     const int *__restrict__ off, long long m, const NrmGrid *__restrict__ grids, const int *__restrict__ cell_start,
     const float4 *__restrict__ sorted, int k, const float *__restrict__ queries, int qps, long long qss, float radius,
     int min_nb, int has_vp, double vx, double vy, double vz, double *__restrict__ normals, double *__restrict__ eig,

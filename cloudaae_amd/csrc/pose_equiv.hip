@@ -20,14 +20,6 @@
 
 namespace cloudaae {
 
-// no packed-fp32 instruction in this kernel (tests/test_isa_rules.py; csrc/Makefile says why): by attribute, as
-// bop_score.hip and symmetry.hip do
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PE_NOPK __attribute__((target("no-packed-fp32-ops")))
-#else
-#define PE_NOPK
-#endif
-
 constexpr int PE_BLOCK = 256;
 constexpr int PE_SAMPLES = PE_BLOCK / 64;          // one wave per sample
 constexpr int PE_MAX_B = 1 << 24;
@@ -66,7 +58,7 @@ __device__ __forceinline__ void pe_exp(double x, double y, double z, double R[3]
             R[i][j] = D[i][j].v;
 }
 
-PE_NOPK __global__ __launch_bounds__(PE_BLOCK) void nearest_equivalent_pose_kernel(
+__global__ __launch_bounds__(PE_BLOCK) void nearest_equivalent_pose_kernel(
     int b, const void *__restrict__ rot_pred, int rot_pred_is_f64, const double *__restrict__ rot_label,
     const float *__restrict__ trans_label, const long long *__restrict__ class_id, int num_class,
     const int *__restrict__ sym_index, const double *__restrict__ sym_centre, const double *__restrict__ sym_axis, int num_rot,

@@ -36,23 +36,12 @@ struct Camera {
 // uniform over n entries from 32 raw bits: floor(r n / 2^32)
 __device__ __forceinline__ int ps_pick(unsigned r, int n) { return (int)(((unsigned long long)r * (unsigned long long)n) >> 32); }
 
-// Both kernels are compiled without the packed-fp32 feature (the rule of the Makefile's NOPK objects: no packed instruction
-// may take a low half from a high register; the compiler formed one in the occluder's dot product).  By attribute and not
-// by a line in NOPK_OBJS: profiles/roofline_traffic.json pins the Makefile's blob hash (tests/test_profiles_fresh.py), so
-// a new line there would void the recorded traffic figures until the counter passes are collected again.  When they next
-// are, this object belongs in NOPK_OBJS and the attribute goes.  tests/test_isa_rules.py reads the result either way.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PS_NOPK __attribute__((target("no-packed-fp32-ops")))
-#else
-#define PS_NOPK
-#endif
-
 // one lane per sample
-PS_NOPK __global__ __launch_bounds__(64) void sample_poses_kernel(int b, unsigned long long first, unsigned long long seed,
-                                                          ClassList classes, Camera cam, long long *__restrict__ class_id,
-                                                          double *__restrict__ axisangle, double *__restrict__ rot,
-                                                          float *__restrict__ rot32, float *__restrict__ trans, unsigned char *__restrict__ in_fov,
-                                                          float *__restrict__ drawn, unsigned *__restrict__ raw)
+__global__ __launch_bounds__(64) void sample_poses_kernel(int b, unsigned long long first, unsigned long long seed,
+                                                  ClassList classes, Camera cam, long long *__restrict__ class_id,
+                                                  double *__restrict__ axisangle, double *__restrict__ rot,
+                                                  float *__restrict__ rot32, float *__restrict__ trans, unsigned char *__restrict__ in_fov,
+                                                  float *__restrict__ drawn, unsigned *__restrict__ raw)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= b)
@@ -116,9 +105,9 @@ PS_NOPK __global__ __launch_bounds__(64) void sample_poses_kernel(int b, unsigne
 // The object occluder of global sample g whose target lies at depth z: its class (the return value) and its centre c,
 // with the raw words r (centre) and q (class).  The one place of the rule: cloudaae_random_object_occluder and
 // cloudaae_rendered_scene both draw through it.
-PS_NOPK __device__ __forceinline__ int ps_occluder_draw(unsigned long long seed, unsigned long long g, const ClassList &classes,
-                                                        float z, float wnear, float hnear, float near_d, unsigned (&r)[4],
-                                                        unsigned (&q)[4], float (&c)[3])
+__device__ __forceinline__ int ps_occluder_draw(unsigned long long seed, unsigned long long g, const ClassList &classes,
+                                                float z, float wnear, float hnear, float near_d, unsigned (&r)[4],
+                                                unsigned (&q)[4], float (&c)[3])
 {
     philox4x32(seed, g, PS_STREAM_OCC_CENTRE, r);
     philox4x32(seed, g, PS_STREAM_OCC_CLASS, q);
@@ -133,12 +122,12 @@ PS_NOPK __device__ __forceinline__ int ps_occluder_draw(unsigned long long seed,
 
 // get_random_object_occluder (generate_occluder.py:5-35): one lane per (sample, point).  The centre and the class are
 // functions of the sample alone, so every lane of a sample derives the same ones.
-PS_NOPK __global__ __launch_bounds__(256) void object_occluder_kernel(int b, unsigned long long first, unsigned long long seed,
-                                                              int npts, const float *__restrict__ models, ClassList classes,
-                                                              const double *__restrict__ rot, const float *__restrict__ trans,
-                                                              int per, float wnear, float hnear, float near_d,
-                                                              float *__restrict__ occ, long long *__restrict__ occ_class,
-                                                              unsigned *__restrict__ raw)
+__global__ __launch_bounds__(256) void object_occluder_kernel(int b, unsigned long long first, unsigned long long seed,
+                                                      int npts, const float *__restrict__ models, ClassList classes,
+                                                      const double *__restrict__ rot, const float *__restrict__ trans,
+                                                      int per, float wnear, float hnear, float near_d,
+                                                      float *__restrict__ occ, long long *__restrict__ occ_class,
+                                                      unsigned *__restrict__ raw)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= b * per)
@@ -171,8 +160,8 @@ PS_NOPK __global__ __launch_bounds__(256) void object_occluder_kernel(int b, uns
 }
 
 // [R | t; 0 0 0 1], row-major: the model -> camera pose the renderer takes
-PS_NOPK __device__ __forceinline__ void ps_pose(const double *__restrict__ R, double tx, double ty, double tz,
-                                                double *__restrict__ out)
+__device__ __forceinline__ void ps_pose(const double *__restrict__ R, double tx, double ty, double tz,
+                                        double *__restrict__ out)
 {
     const double t[3] = {tx, ty, tz};
 #pragma unroll
@@ -190,16 +179,16 @@ PS_NOPK __device__ __forceinline__ void ps_pose(const double *__restrict__ R, do
 // again) and 3i + 2 (the occluder: the class and the centre of ps_occluder_draw, under the sample's own rotation).  The
 // classes live on the device, so instance j's vertex and triangle ranks start at j * max_v and j * max_t; the renderer
 // treats the ranks past a mesh's own counts as absent.  A class outside mesh_index gives mesh -1: nothing is drawn.
-PS_NOPK __global__ __launch_bounds__(64) void rendered_scene_kernel(int b, unsigned long long first, unsigned long long seed,
-                                                                   ClassList classes, int nmodels,
-                                                                   const long long *__restrict__ class_id,
-                                                                   const int *__restrict__ mesh_index,
-                                                                   const double *__restrict__ rot, const float *__restrict__ trans,
-                                                                   float wnear, float hnear, float near_d, int max_v, int max_t,
-                                                                   int *__restrict__ inst_offsets, int *__restrict__ inst_mesh,
-                                                                   int *__restrict__ inst_label, double *__restrict__ inst_pose,
-                                                                   int *__restrict__ vert_base, int *__restrict__ tri_base,
-                                                                   long long *__restrict__ occ_class, float *__restrict__ occ_centre)
+__global__ __launch_bounds__(64) void rendered_scene_kernel(int b, unsigned long long first, unsigned long long seed,
+                                                           ClassList classes, int nmodels,
+                                                           const long long *__restrict__ class_id,
+                                                           const int *__restrict__ mesh_index,
+                                                           const double *__restrict__ rot, const float *__restrict__ trans,
+                                                           float wnear, float hnear, float near_d, int max_v, int max_t,
+                                                           int *__restrict__ inst_offsets, int *__restrict__ inst_mesh,
+                                                           int *__restrict__ inst_label, double *__restrict__ inst_pose,
+                                                           int *__restrict__ vert_base, int *__restrict__ tri_base,
+                                                           long long *__restrict__ occ_class, float *__restrict__ occ_centre)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= b)

@@ -25,13 +25,6 @@ using namespace cloudaae;
 
 namespace {
 
-// no packed-fp32 instruction in these kernels (tests/test_isa_rules.py; csrc/Makefile says why), as in icp.hip
-#ifdef __HIP_DEVICE_COMPILE__
-#define PS_NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define PS_NO_PACKED_FP32
-#endif
-
 constexpr int PS_QUERIES = 64;                    // queries of a workgroup: one per lane
 constexpr int PS_WAVES = 8;
 constexpr int PS_THREADS = PS_QUERIES * PS_WAVES;
@@ -105,7 +98,7 @@ __device__ __forceinline__ double ps_scan(const float *__restrict__ X, int ps, i
 }
 
 // partial [b*p][tiles][2]: the tile's sums of |g_i - e_i| and of sqrt(nn_d2[i]) (lanes in butterfly order)
-__global__ void __launch_bounds__(PS_THREADS) PS_NO_PACKED_FP32
+__global__ void __launch_bounds__(PS_THREADS)
 pose_score_tile_kernel(int p, int m, int tiles, const float *__restrict__ model, int ps, long long cs,
                        const double *__restrict__ est, const double *__restrict__ gt, double *__restrict__ nn_d2,
                        double *__restrict__ partial)
@@ -148,8 +141,8 @@ pose_score_tile_kernel(int p, int m, int tiles, const float *__restrict__ model,
 }
 
 // one lane per (sample, pose): the tiles' sums in ascending tile order, divided by m
-__global__ void PS_NO_PACKED_FP32 pose_score_finish_kernel(int n, int m, int tiles, const double *__restrict__ partial,
-                                                           double *__restrict__ add, double *__restrict__ adds)
+__global__ void pose_score_finish_kernel(int n, int m, int tiles, const double *__restrict__ partial,
+                                         double *__restrict__ add, double *__restrict__ adds)
 {
     const int sp = blockIdx.x * blockDim.x + threadIdx.x;
     if (sp >= n)
@@ -165,7 +158,7 @@ __global__ void PS_NO_PACKED_FP32 pose_score_finish_kernel(int n, int m, int til
 }
 
 // partial [c][tiles]: the largest squared distance from a point of the tile to any point of the cloud
-__global__ void __launch_bounds__(PS_THREADS) PS_NO_PACKED_FP32
+__global__ void __launch_bounds__(PS_THREADS)
 cloud_diameter_tile_kernel(int m, int tiles, const float *__restrict__ model, int ps, long long cs,
                            double *__restrict__ partial)
 {
@@ -186,8 +179,8 @@ cloud_diameter_tile_kernel(int m, int tiles, const float *__restrict__ model, in
     }
 }
 
-__global__ void PS_NO_PACKED_FP32 cloud_diameter_finish_kernel(int n, int tiles, const double *__restrict__ partial,
-                                                               double *__restrict__ diam)
+__global__ void cloud_diameter_finish_kernel(int n, int tiles, const double *__restrict__ partial,
+                                             double *__restrict__ diam)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n)
@@ -198,8 +191,8 @@ __global__ void PS_NO_PACKED_FP32 cloud_diameter_finish_kernel(int n, int tiles,
     diam[c] = sqrt(far);
 }
 
-__global__ void PS_NO_PACKED_FP32 pose_matrix_kernel(int n, const void *__restrict__ rot, int rot_is_f64,
-                                                     const float *__restrict__ trans, double *__restrict__ out)
+__global__ void pose_matrix_kernel(int n, const void *__restrict__ rot, int rot_is_f64,
+                                   const float *__restrict__ trans, double *__restrict__ out)
 {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n)
@@ -222,8 +215,8 @@ __global__ void PS_NO_PACKED_FP32 pose_matrix_kernel(int n, const void *__restri
     T[15] = 1.0;
 }
 
-__global__ void PS_NO_PACKED_FP32 pose_stack_kernel(int n, const double *__restrict__ first,
-                                                    const double *__restrict__ second, double *__restrict__ out)
+__global__ void pose_stack_kernel(int n, const double *__restrict__ first,
+                                  const double *__restrict__ second, double *__restrict__ out)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;     // over n * 32 doubles
     if (i >= n * 32)

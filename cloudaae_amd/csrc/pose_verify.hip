@@ -28,14 +28,6 @@
 
 namespace cloudaae {
 
-// no packed-fp32 instruction in these kernels (tests/test_isa_rules.py; csrc/Makefile says why).  By attribute, as
-// bop_score.hip does; the atomics and the ballot are the compiler's builtins.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PV_NOPK __attribute__((target("no-packed-fp32-ops")))
-#else
-#define PV_NOPK
-#endif
-
 typedef unsigned long long u64;
 typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
 typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
@@ -46,12 +38,12 @@ constexpr long long PV_MAX_TOTAL = 1ll << 28;      // B P H W, B P
 // ---- cloudaae_pose_compose ---------------------------------------------------------------------------------------------
 constexpr int PC_BLOCK = 64;
 
-PV_NOPK __global__ __launch_bounds__(PC_BLOCK) void pose_compose_kernel(int n, int p, const double *__restrict__ base,
-                                                                        const long long *__restrict__ class_id, int nclass,
-                                                                        const int *__restrict__ hyp_index, int n_total,
-                                                                        const double *__restrict__ hyp,
-                                                                        double *__restrict__ pose, double *__restrict__ rot_axag,
-                                                                        float *__restrict__ trans, int *__restrict__ valid)
+__global__ __launch_bounds__(PC_BLOCK) void pose_compose_kernel(int n, int p, const double *__restrict__ base,
+                                                                const long long *__restrict__ class_id, int nclass,
+                                                                const int *__restrict__ hyp_index, int n_total,
+                                                                const double *__restrict__ hyp,
+                                                                double *__restrict__ pose, double *__restrict__ rot_axag,
+                                                                float *__restrict__ trans, int *__restrict__ valid)
 {
     const int e = blockIdx.x * PC_BLOCK + threadIdx.x;
     if (e >= n)
@@ -116,23 +108,9 @@ struct DepthFitArgs {
     long long *abs_sum;
 };
 
-PV_NOPK __device__ __forceinline__ int df_count(bool pred)
-{
-    return __builtin_popcountll(__builtin_amdgcn_ballot_w64(pred));
-}
-
-// __syncthreads as the HIP headers spell it (by the builtins: a function with the no-packed-fp32 attribute does not inline
-// the header's, and the kernel would call it)
-PV_NOPK __device__ __forceinline__ void df_barrier()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 // the lane's eight depths of a run of n pixels: one 16-byte load where the run is aligned and the lane lies inside,
 // else pixel by pixel with zeros past the end
-PV_NOPK __device__ __forceinline__ void df_load8(const unsigned short *run, int n, int off, bool aligned, int v[DF_PIX])
+__device__ __forceinline__ void df_load8(const unsigned short *run, int n, int off, bool aligned, int v[DF_PIX])
 {
     if (aligned && off + DF_PIX <= n) {
         const uint4v q = *reinterpret_cast<const uint4v *>(run + off);
@@ -148,7 +126,7 @@ PV_NOPK __device__ __forceinline__ void df_load8(const unsigned short *run, int 
     }
 }
 
-PV_NOPK __global__ __launch_bounds__(DF_BLOCK) void depth_fit_counts_kernel(DepthFitArgs a)
+__global__ __launch_bounds__(DF_BLOCK) void depth_fit_counts_kernel(DepthFitArgs a)
 {
     __shared__ int red[DF_CHUNK][DF_WAVES][DF_SLOTS];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -184,7 +162,7 @@ PV_NOPK __global__ __launch_bounds__(DF_BLOCK) void depth_fit_counts_kernel(Dept
     int n_seg = 0;
 #pragma unroll
     for (int i = 0; i < DF_PIX; ++i)
-        n_seg += df_count((seg >> i) & 1u);
+        n_seg += wave_count((seg >> i) & 1u);
 
     // the hypotheses, DF_CHUNK at a time: a wave leaves its counts of each in LDS, and the workgroup meets once per chunk.
     // The depths of the next hypothesis are on their way while the current ones are compared.
@@ -211,17 +189,16 @@ PV_NOPK __global__ __launch_bounds__(DF_BLOCK) void depth_fit_counts_kernel(Dept
                     const bool rend = d[i] != 0, both = rend && t[i] != 0;
                     const int diff = d[i] - t[i], mag = diff < 0 ? -diff : diff;
                     const bool cons = both && mag <= tau;
-                    cnt[0] += df_count(rend);
-                    cnt[1] += df_count(cons);
-                    cnt[2] += df_count(both && -diff > tau);
-                    cnt[3] += df_count(both && diff > tau);
-                    cnt[4] += df_count(rend && t[i] == 0);
-                    cnt[5] += df_count(cons && ((seg >> i) & 1u));
+                    cnt[0] += wave_count(rend);
+                    cnt[1] += wave_count(cons);
+                    cnt[2] += wave_count(both && -diff > tau);
+                    cnt[3] += wave_count(both && diff > tau);
+                    cnt[4] += wave_count(rend && t[i] == 0);
+                    cnt[5] += wave_count(cons && ((seg >> i) & 1u));
                     asum += cons ? mag : 0;
                 }
             }
-            // at most 512 * 65535: an int holds the wave's and the workgroup's sum (the builtin instead of __shfl_xor: a
-            // function with the no-packed-fp32 attribute does not inline the header's)
+            // at most 512 * 65535: an int holds the wave's and the workgroup's sum
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1)
                 asum += __builtin_amdgcn_ds_bpermute((lane ^ o) << 2, asum);
@@ -233,7 +210,7 @@ PV_NOPK __global__ __launch_bounds__(DF_BLOCK) void depth_fit_counts_kernel(Dept
                 red[jj][wv][DF_COUNTERS + 1] = asum;
             }
         }
-        df_barrier();
+        __syncthreads();
         if (tid < nj * DF_SLOTS) {                 // one thread per (hypothesis of the chunk, slot)
             const int jj = tid / DF_SLOTS, slot = tid % DF_SLOTS;
             const size_t sp = (size_t)s * a.p + (j0 + jj);
@@ -250,7 +227,7 @@ PV_NOPK __global__ __launch_bounds__(DF_BLOCK) void depth_fit_counts_kernel(Dept
                     __hip_atomic_fetch_add(a.abs_sum + sp, (long long)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
-        df_barrier();                              // red is written again for the next chunk
+        __syncthreads();                           // red is written again for the next chunk
     }
 }
 
@@ -258,8 +235,8 @@ PV_NOPK __global__ __launch_bounds__(DF_BLOCK) void depth_fit_counts_kernel(Dept
 constexpr int SP_BLOCK = 64;
 
 // num and den of hypothesis j (0 / 1 for "no score"): the segment rule or the silhouette rule
-PV_NOPK __device__ __forceinline__ void sp_fraction(const int *c, int seg_total, int valid, int mode, long long &num,
-                                                    long long &den)
+__device__ __forceinline__ void sp_fraction(const int *c, int seg_total, int valid, int mode, long long &num,
+                                            long long &den)
 {
     if (mode == 0) {
         num = c[5];
@@ -274,12 +251,12 @@ PV_NOPK __device__ __forceinline__ void sp_fraction(const int *c, int seg_total,
     }
 }
 
-PV_NOPK __global__ __launch_bounds__(SP_BLOCK) void select_pose_kernel(int b, int p, const int *__restrict__ counts,
-                                                                       const int *__restrict__ seg_total,
-                                                                       const int *__restrict__ valid,
-                                                                       const double *__restrict__ pose, int mode,
-                                                                       int *__restrict__ best, double *__restrict__ score,
-                                                                       double *__restrict__ pose_best, double *__restrict__ margin)
+__global__ __launch_bounds__(SP_BLOCK) void select_pose_kernel(int b, int p, const int *__restrict__ counts,
+                                                               const int *__restrict__ seg_total,
+                                                               const int *__restrict__ valid,
+                                                               const double *__restrict__ pose, int mode,
+                                                               int *__restrict__ best, double *__restrict__ score,
+                                                               double *__restrict__ pose_best, double *__restrict__ margin)
 {
     const int i = blockIdx.x * SP_BLOCK + threadIdx.x;
     if (i >= b)

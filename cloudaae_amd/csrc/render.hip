@@ -36,14 +36,6 @@ constexpr int RN_MAX_MESHES = 65535;
 typedef unsigned long long u64;
 constexpr u64 RN_EMPTY = ~0ull;
 
-// no packed-fp32 instruction in these kernels (tests/test_isa_rules.py; csrc/Makefile says why).  By attribute, as
-// mesh_sample.hip does: the Makefile's blob hash is pinned by profiles/roofline_traffic.json.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define RN_NOPK __attribute__((target("no-packed-fp32-ops")))
-#else
-#define RN_NOPK
-#endif
-
 struct RenderArgs {
     int s, nv, nt;                         // the packed meshes
     const int *vert_offsets, *tri_offsets;
@@ -68,7 +60,7 @@ struct RenderArgs {
 };
 
 // the last i in [0, n) with base[i] <= g (entries with an empty range are stepped over); -1 when there is none
-RN_NOPK __device__ __forceinline__ int rn_owner(const int *__restrict__ base, int n, int g)
+__device__ __forceinline__ int rn_owner(const int *__restrict__ base, int n, int g)
 {
     int lo = 0, hi = n;
     while (lo < hi) {
@@ -83,7 +75,7 @@ RN_NOPK __device__ __forceinline__ int rn_owner(const int *__restrict__ base, in
 
 // the ranges of instance j's mesh; false (an instance without vertices and triangles) when the mesh id or its offsets
 // do not describe ranges inside the packed arrays
-RN_NOPK __device__ __forceinline__ bool rn_mesh(const RenderArgs &a, int j, int &v0, int &v1, int &t0, int &t1)
+__device__ __forceinline__ bool rn_mesh(const RenderArgs &a, int j, int &v0, int &v1, int &t0, int &t1)
 {
     const int m = a.inst_mesh[j];
     if (m < 0 || m >= a.s)
@@ -96,7 +88,7 @@ RN_NOPK __device__ __forceinline__ bool rn_mesh(const RenderArgs &a, int j, int 
 }
 
 // one lane per (instance, vertex): the pose, the projection, the fixed-point grid
-RN_NOPK __global__ __launch_bounds__(RN_BLOCK) void render_vertex_kernel(RenderArgs a)
+__global__ __launch_bounds__(RN_BLOCK) void render_vertex_kernel(RenderArgs a)
 {
     const long long gl = (long long)blockIdx.x * RN_BLOCK + threadIdx.x;
     if (gl >= a.sum_v)
@@ -139,7 +131,7 @@ struct RenderTri {
 
 // the setup of draw rank g.  0: drawable (tri is filled in); 1: no such triangle; 2: dropped; 3: degenerate.  j is the
 // instance (for the counts).
-RN_NOPK __device__ __forceinline__ int rn_setup(const RenderArgs &a, int g, RenderTri &tri, int &j)
+__device__ __forceinline__ int rn_setup(const RenderArgs &a, int g, RenderTri &tri, int &j)
 {
     j = rn_owner(a.tri_base, a.j, g);
     int v0, v1, t0, t1;
@@ -188,7 +180,7 @@ RN_NOPK __device__ __forceinline__ int rn_setup(const RenderArgs &a, int g, Rend
 }
 
 // one sample of one triangle: coverage, depth, the depth test
-RN_NOPK __device__ __forceinline__ void rn_sample(const RenderArgs &a, const RenderTri &t, int rank, int u, int v)
+__device__ __forceinline__ void rn_sample(const RenderArgs &a, const RenderTri &t, int rank, int u, int v)
 {
     const long long px = (long long)u << RN_FRAC, py = (long long)v << RN_FRAC;
     const long long wa = (t.cx - t.bx) * (py - t.by) - (t.cy - t.by) * (px - t.bx);
@@ -204,14 +196,12 @@ RN_NOPK __device__ __forceinline__ void rn_sample(const RenderArgs &a, const Ren
     const u64 key = ((u64)(unsigned)(int)du << 32) | (u64)(unsigned)rank;
     u64 *cell = a.zbuf + ((size_t)t.frame * a.h + v) * a.w + u;
     // the plain read only spares atomics: the cell never grows, so what it shows is never below the final minimum
-    // (the builtins instead of atomicMin / __ballot / __shfl: a function with the no-packed-fp32 attribute does not inline
-    // the header's wrappers, it calls them)
     if (key < __atomic_load_n(cell, __ATOMIC_RELAXED))
         __hip_atomic_fetch_min(cell, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // one lane per (instance, triangle) = per draw rank: the setup, the counts, the small boxes; the others are queued
-RN_NOPK __global__ __launch_bounds__(RN_BLOCK) void render_setup_kernel(RenderArgs a)
+__global__ __launch_bounds__(RN_BLOCK) void render_setup_kernel(RenderArgs a)
 {
     const long long gl = (long long)blockIdx.x * RN_BLOCK + threadIdx.x;
     bool large = false;
@@ -253,7 +243,7 @@ RN_NOPK __global__ __launch_bounds__(RN_BLOCK) void render_setup_kernel(RenderAr
 }
 
 // a fixed grid of waves strides over the queue: one wave per triangle, its lanes tile the clamped box in 8 x 8 blocks
-RN_NOPK __global__ __launch_bounds__(RN_BLOCK) void render_queue_kernel(RenderArgs a)
+__global__ __launch_bounds__(RN_BLOCK) void render_queue_kernel(RenderArgs a)
 {
     const int len = min(*a.queue_len, a.sum_t);
     const int waves = gridDim.x * (RN_BLOCK / 64);
@@ -276,11 +266,11 @@ RN_NOPK __global__ __launch_bounds__(RN_BLOCK) void render_queue_kernel(RenderAr
 }
 
 // one lane per pixel: key -> depth, label, rank
-RN_NOPK __global__ __launch_bounds__(RN_BLOCK) void render_resolve_kernel(long long pixels, const u64 *__restrict__ zbuf, int j,
-                                                                  const int *__restrict__ tri_base,
-                                                                  const int *__restrict__ inst_label,
-                                                                  unsigned short *__restrict__ depth,
-                                                                  unsigned char *__restrict__ label, int *__restrict__ tri)
+__global__ __launch_bounds__(RN_BLOCK) void render_resolve_kernel(long long pixels, const u64 *__restrict__ zbuf, int j,
+                                                          const int *__restrict__ tri_base,
+                                                          const int *__restrict__ inst_label,
+                                                          unsigned short *__restrict__ depth,
+                                                          unsigned char *__restrict__ label, int *__restrict__ tri)
 {
     const long long p = (long long)blockIdx.x * RN_BLOCK + threadIdx.x;
     if (p >= pixels)

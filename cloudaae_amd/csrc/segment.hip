@@ -31,14 +31,6 @@ using namespace cloudaae;
 
 namespace {
 
-// no packed-fp32 instruction in these kernels (tests/test_isa_rules.py; csrc/Makefile says why).  The host pass
-// does not know the feature: the attribute goes to the device pass only.
-#ifdef __HIP_DEVICE_COMPILE__
-#define SEG_NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
-#else
-#define SEG_NO_PACKED_FP32
-#endif
-
 constexpr int SEG_BLOCK = 256;             // pixels / points per block of the pixel and compaction passes
 constexpr int SEG_CLASSES = 256;           // label values 1..255 -> classes 0..254
 constexpr int SEG_SCAN_THREADS = 1024;
@@ -158,7 +150,7 @@ __global__ __launch_bounds__(SEG_SCAN_THREADS) void scan_kernel(const int *in, i
     block_exclusive_scan(in, 1, n, out, lds);
 }
 
-__global__ SEG_NO_PACKED_FP32 __launch_bounds__(SEG_BLOCK) void fs_scatter_kernel(
+__global__ __launch_bounds__(SEG_BLOCK) void fs_scatter_kernel(
     int hw, int w, int nblk, const uint16_t *depth, const uint8_t *label, const float *intr, const int *table,
     const int *seg_blk_off, const int *mask_off, float *mxyz, int *mseg)
 {
@@ -213,7 +205,7 @@ __global__ void fs_mean_kernel(int s, const int *mask_off, const float *mxyz, fl
 }
 
 // flag = sqrtf((dx^2 + dy^2) + dz^2) <= threshold in fp32 (:219-223); one count per block
-__global__ SEG_NO_PACKED_FP32 __launch_bounds__(SEG_BLOCK) void fs_filter_flags_kernel(
+__global__ __launch_bounds__(SEG_BLOCK) void fs_filter_flags_kernel(
     const int *total, long long m, const float *mxyz, const int *mseg, const float *mean, float threshold, uint8_t *flags,
     int *blk_count)
 {
@@ -404,7 +396,7 @@ __global__ __launch_bounds__(RO_THREADS) void ro_grid_kernel(const int *off, lon
 }
 
 // per point: neighbours (itself included) with d^2 < r^2, counted cell by cell until the count passes nb_points
-__global__ SEG_NO_PACKED_FP32 __launch_bounds__(SEG_BLOCK) void ro_count_kernel(
+__global__ __launch_bounds__(SEG_BLOCK) void ro_count_kernel(
     const int *total, long long m, const int *off, const int *seg, const float *xyz, const RoGrid *grids, const int *cell_start,
     const float4 *sorted, int nb_points, float radius, uint8_t *flags, int *seg_count)
 {
@@ -501,7 +493,7 @@ __device__ __forceinline__ void fps_better(double d, int k, double &bd, int &bk)
 }
 
 // one workgroup per set: idx[0] = start, idx[j] = first argmax of dist, dist = min(dist, d(idx[j]))
-__global__ SEG_NO_PACKED_FP32 __launch_bounds__(FPS_THREADS) void fps_ragged_kernel(
+__global__ __launch_bounds__(FPS_THREADS) void fps_ragged_kernel(
     const int *off, long long m, const float *xyz, int k, const int *starts, double *dist_ws, int *idx, float *out_xyz)
 {
     __shared__ double cand_d[2][FPS_WAVES];

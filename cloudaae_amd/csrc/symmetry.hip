@@ -24,14 +24,6 @@
 
 namespace cloudaae {
 
-// no packed-fp32 instruction in these kernels (tests/test_isa_rules.py; csrc/Makefile says why): by attribute, as
-// bop_score.hip and render.hip do
-#if defined(__HIP_DEVICE_COMPILE__)
-#define SY_NOPK __attribute__((target("no-packed-fp32-ops")))
-#else
-#define SY_NOPK
-#endif
-
 typedef unsigned long long u64;
 
 constexpr int SY_BLOCK = 128;                      // queries of a workgroup: one per lane
@@ -43,11 +35,11 @@ constexpr int SY_MAX_POINTS = 1 << 24;             // m and n
 constexpr size_t SY_LDS_BYTES = sizeof(double) * 3 * SY_TILE + sizeof(u64) * SY_WAVES * SY_R;
 
 // acc [c]: the bit pattern of max_i min_j |T_c x_i - y_j|^2, zeroed before the launch
-SY_NOPK __global__ __launch_bounds__(SY_BLOCK) void transform_hausdorff_kernel(int c, int m, int groups,
-                                                                              const float *__restrict__ queries, int qs, int n,
-                                                                              const float *__restrict__ targets, int ts,
-                                                                              const double *__restrict__ transforms,
-                                                                              double limit2, u64 *acc)
+__global__ __launch_bounds__(SY_BLOCK) void transform_hausdorff_kernel(int c, int m, int groups,
+                                                                      const float *__restrict__ queries, int qs, int n,
+                                                                      const float *__restrict__ targets, int ts,
+                                                                      const double *__restrict__ transforms,
+                                                                      double limit2, u64 *acc)
 {
     extern __shared__ __attribute__((aligned(16))) char sy_lds[];
     double *tx = reinterpret_cast<double *>(sy_lds), *ty = tx + SY_TILE, *tz = ty + SY_TILE;
@@ -123,8 +115,8 @@ SY_NOPK __global__ __launch_bounds__(SY_BLOCK) void transform_hausdorff_kernel(i
 }
 
 // one lane per candidate: the square root, or +inf above limit2
-SY_NOPK __global__ void transform_hausdorff_finish_kernel(int c, const u64 *__restrict__ acc, double limit2,
-                                                          double *__restrict__ out)
+__global__ void transform_hausdorff_finish_kernel(int c, const u64 *__restrict__ acc, double limit2,
+                                                  double *__restrict__ out)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= c)

@@ -5,8 +5,8 @@ a pair (`v_pk_add_f32 ... op_sel:[0,1]`, the squared norms of the kNN / Chamfer 
 `src0 + 0` in lanes 48-63 -- only while a wave of ANOTHER process shared the SIMD, about 62 launches of 9600 at these shapes.
 tests/test_isa_rules.py checks the built code for the instruction; this is the behaviour: next to a process that runs training
 steps on the same GPU, a process issues the same launches over and over and every result must equal the first (the reference op, utils/tf_util.py:621-632, is
-deterministic).  Measured with a build that has the instruction (the five files of csrc/Makefile's NOPK_OBJS compiled without the
-flag): 803 of 66 640 launches of the [32,128] kNN wrong in its five seconds; the shipped build: 0 of 314 000 over the six cases."""
+deterministic).  Measured with a build that has the instruction (knn, nn_distance, sampling, step and synth, then the only files csrc/Makefile built without packed fp32,
+compiled without the flag): 803 of 66 640 launches of the [32,128] kNN wrong in its five seconds; the shipped build: 0 of 314 000 over the six cases."""
 import time
 
 import pytest

@@ -43,3 +43,17 @@ def test_chamfer_digest_reads_no_xdl_result_too_early(instructions):
     assert len(reads) >= 16, "the digest's v_min3_f32 were not found in the disassembly"
     early = isa_scan.xdl_results_read_too_early(instructions, "nn_distance_filter_kernel")
     assert not early, early[:5]
+
+
+def test_no_kernel_calls_a_function(instructions):
+    """Rule 3: the built library holds no `s_swappc_b64`.  Every device function here is meant to be inlined; a call goes
+    through the call ABI and spills to scratch (icp_kernel: one call and 80 B of scratch per barrier of every update).  Before
+    csrc/Makefile set the target features per file, thirteen files kept packed fp32 out of their kernels with a per-function
+    target attribute, and a function that carries one cannot inline a callee that does not -- __syncthreads, __shfl*,
+    __ballot, atomicAdd, make_float4 and the helpers of pose_math.h and so3_dual.h all became calls.  On that build this test
+    found 190 calls in 26 kernels of 12 files: normals 69, icp 46, mesh_sample 32, frame_clouds 12, pose_score 8, segment 8,
+    symmetry 5, bop_score 4, depth_noise 2, pose_equiv 2, pose_sample 1, pose_verify 1.  A function the compiler itself
+    declines to inline trips it too: mark that function __forceinline__."""
+    assert len(instructions) > 100000, "disassembly looks empty"
+    calls = isa_scan.function_calls(instructions)
+    assert not calls, "%d function calls:\n" % len(calls) + "\n".join("%s | %s" % c for c in calls[:20])

@@ -5,6 +5,11 @@ Rule 1 (profiles/notes_two_processes_one_gpu.md, round 6): no packed-fp32 instru
 the HIGH register of a source pair -- `op_sel:[...]` with a 1 in it on v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32.  On MI355X
 such an instruction now and then returns `src0 + 0` in lanes 48-63 when a wave of another process shares the SIMD.
 
+Rule 3: no kernel calls a function (`s_swappc_b64`).  Every device function of this library is meant to be inlined; a call
+goes through the call ABI and spills to scratch.  What made them here was a per-function target attribute: a function whose
+target features differ from its callee's cannot inline it, so __syncthreads, __shfl, atomicAdd and every shared header's
+helper became calls.  csrc/Makefile sets the target features per file instead.
+
 Needs llvm-objcopy, clang-offload-bundler and llvm-objdump of the ROCm LLVM (/opt/rocm/lib/llvm/bin); no GPU."""
 import os
 import re
@@ -116,6 +121,11 @@ def packed_f32_low_from_high(instructions):
     return bad
 
 
+def function_calls(instructions):
+    """the instructions rule 3 forbids: [(function, instruction)]"""
+    return [(fn, ins) for fn, ins in instructions if ins.startswith("s_swappc_b64")]
+
+
 _MFMA = re.compile(r"^(v_mfma_\S+)\s+([av])\[(\d+):(\d+)\]")
 _REG = re.compile(r"\b([av])(?:\[(\d+):(\d+)\]|(\d+))\b")
 _NOP = re.compile(r"^s_nop\s+(\d+)")
@@ -173,7 +183,11 @@ def main():
     print("nn_distance_filter_kernel: %d v_min3_f32, %d of them read an XDL result less than 11 wait states after its v_mfma" % (reads, len(early)))
     for e in early[:10]:
         print("   ", e)
-    return 1 if (bad or early) else 0
+    calls = function_calls(ins)
+    print("%d function calls (s_swappc_b64) in %d functions" % (len(calls), len(set(fn for fn, _ in calls))))
+    for fn, i in calls[:10]:
+        print("   ", fn, "|", i)
+    return 1 if (bad or early or calls) else 0
 
 
 if __name__ == "__main__":
