@@ -414,6 +414,8 @@ def lib():
         cdll.cloudaae_loss_tail_workspace_bytes.argtypes = []
         cdll.cloudaae_fc_forward_partials.argtypes = [_I, _I, _I, _I]
         cdll.cloudaae_fc_forward_partials.restype = ctypes.c_longlong
+        cdll.cloudaae_fc_plan.argtypes = [_I, _I, _I, _I, _I, _I, _I, _P]
+        cdll.cloudaae_fc_plan.restype = ctypes.c_int
         cdll.cloudaae_edgeconv_workspace_bytes.argtypes = [_I]
         for q in ("cloudaae_set_knob", "cloudaae_unset_knob"):
             getattr(cdll, q).restype = ctypes.c_int

@@ -720,10 +720,15 @@ struct FcBwdGroup {
     FcBwdArgs p[FC_MAX_GROUP];
 };
 
+// What the kernel, the launch and cloudaae_fc_plan must agree on.  The row tiles a backward kernel is built for (there is
+// none for three: 65..96 rows run the one for four), and whether W reaches the dX product in whole lines through LDS
+// (fc_bwd_dx_staged): whole quads, one row tile, a wave per tile.
+__host__ __device__ constexpr int fc_bwd_rt(int rts) { return rts <= 2 ? rts : 4; }
+__host__ __device__ constexpr bool fc_bwd_stages(bool vec, int rt, int parts) { return vec && rt == 1 && parts == 2; }
+
 // One workgroup (four waves) = (128-column slice of the output, group of 32-row tiles of W), all RT row tiles of the batch.
-// parts = 1: a wave does both products of a tile (the wide output layer);
-// parts = 2: the same tiles, but waves 0, 1 write dW and waves 2, 3 gather dX: the two streams (W read + atomics, dW
-//            written) run side by side on different SIMDs instead of one after the other in every wave;
+// parts = 2: a wave per tile (the wide output layer); waves 0, 1 write dW and waves 2, 3 gather dX: the two streams (W
+//            read + atomics, dW written) run side by side on different SIMDs instead of one after the other in every wave;
 // parts = 4: the four waves share a tile -- dW columns 0..63 | 64..127, dX over columns 0..63 | 64..127 --
 //            for the layers whose whole backward is a few hundred tiles (one tile per workgroup, every
 //            workgroup resident at once).
@@ -739,13 +744,13 @@ __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs &a, int slice_x, int
     const int ktiles = (a.K + 31) / 32;
     const int t_end = min(ktiles, (group_y + 1) * a.tiles_per_block);
     // one row tile, a tile per wave, W in whole quads: the first tile's operands are requested NOW
-    constexpr bool STAGED = VEC && RT == 1;
-    const bool ahead = STAGED && a.parts <= 2;
-    // parts = 2: waves 0, 1 write dW and waves 2, 3 gather dX, each pair over the workgroup's tiles alternately
-    const int role = a.parts == 2 ? wv >> 1 : -1;       // -1: both products
-    const int t_first = group_y * a.tiles_per_block + (a.parts == 2 ? (wv & 1) : wv);
-    const int t_step = a.parts == 2 ? 2 : 4;
-    const bool do_dw = a.dw != nullptr && role != 1, do_dx = a.dx != nullptr && role != 0;
+    constexpr bool STAGED = fc_bwd_stages(VEC, RT, 2);
+    const bool ahead = fc_bwd_stages(VEC, RT, a.parts);
+    // parts = 2 ONLY (they stand here because the staged loads above the dY phase need them; the parts = 4 branch below
+    // uses none of them): waves 0, 1 write dW and waves 2, 3 gather dX, each pair over the workgroup's tiles alternately
+    const int role = wv >> 1;
+    const int t_first = group_y * a.tiles_per_block + (wv & 1);
+    const bool do_dw = a.dw != nullptr && role == 0, do_dx = a.dx != nullptr && role == 1;
     float4v wq[STAGED ? 2 : 1][8];
     float xa0[16 * RT];
     if constexpr (STAGED) {
@@ -863,8 +868,8 @@ __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs &a, int slice_x, int
     }
     FC_STAMP(1);
 
-    if (a.parts <= 2) {
-        for (int t = t_first; t < t_end; t += t_step) {
+    if (a.parts == 2) {
+        for (int t = t_first; t < t_end; t += 2) {
             if constexpr (STAGED) {
                 if (t != t_first) {
                     if (do_dx)
@@ -970,6 +975,38 @@ static FcFwdPlan fc_fwd_plan(int M, int K, int N, bool bn, bool no_scratch)
     return p;
 }
 
+// Workgroups of one backward layer: `slices` 128-column slices of the output times `by` groups of `tiles_per_block`
+// 32-row tiles of W.
+struct FcBwdPlan {
+    int rts, slices, fine, parts, tiles_per_block, by;
+};
+static FcBwdPlan fc_bwd_plan(int M, int K, int N)
+{
+    FcBwdPlan p;
+    p.rts = ceil_div(M, FC_ROWS);
+    p.slices = ceil_div(N, FC_TN);
+    const int ktiles = ceil_div(K, 32);
+    // Few tiles (every layer but the wide output one): one tile per workgroup, its four waves share
+    // it, everything resident at once.  Many tiles: a wave per tile, workgroups for the resident set.
+    p.fine = (long long)p.slices * ktiles <= 1024;
+    int by;
+    if (p.fine) {
+        // (several row tiles: every workgroup of a slice derives dY for all rows of the slice again -- 128 KB of
+        // L2 reads at 128 rows -- so a workgroup keeps two tiles)
+        by = ceil_div(ktiles, p.rts > 1 ? 2 : 1);
+    } else {
+        const int want = 384;
+        by = ceil_div(want, p.slices);
+        const int most = ceil_div(ktiles, 4);
+        by = by > most ? most : by;
+        by = by < 1 ? 1 : by;
+    }
+    p.tiles_per_block = ceil_div(ktiles, by);
+    p.by = ceil_div(ktiles, p.tiles_per_block);
+    p.parts = p.fine ? 4 : 2;
+    return p;
+}
+
 } // namespace cloudaae
 
 using namespace cloudaae;
@@ -1000,6 +1037,21 @@ CLOUDAAE_API long long cloudaae_fc_forward_partials(int M, int K, int N, int bat
         return 0;
     const FcFwdPlan p = fc_fwd_plan(M, K, N, batch_norm != 0, false);
     return p.combine ? (long long)p.tiles * p.rts * p.splits * FC_ROWS * (32 * p.cq) : 0;
+}
+
+CLOUDAAE_API int cloudaae_fc_plan(int backward, int M, int K, int N, int batch_norm, int vec, int scratch, int *out)
+{
+    if (M <= 0 || M > FC_ROWS * FC_MAX_RT || K <= 0 || N <= 0 || out == nullptr)
+        return 1;
+    if (!backward) {
+        const FcFwdPlan p = fc_fwd_plan(M, K, N, batch_norm != 0, scratch == 0);
+        out[0] = p.cq; out[1] = p.tiles; out[2] = p.rts; out[3] = p.splits; out[4] = p.kslice; out[5] = p.combine;
+    } else {
+        const FcBwdPlan p = fc_bwd_plan(M, K, N);
+        out[0] = fc_bwd_rt(p.rts); out[1] = p.fine; out[2] = p.parts; out[3] = p.tiles_per_block; out[4] = p.by;
+        out[5] = fc_bwd_stages(vec != 0, fc_bwd_rt(p.rts), p.parts);
+    }
+    return 0;
 }
 
 CLOUDAAE_API int cloudaae_fc_forward_group(int M, int count, const cloudaae_fc_layer *layers, int training,
@@ -1064,7 +1116,7 @@ CLOUDAAE_API int cloudaae_fc_backward_group(int M, int count, const cloudaae_fc_
     CLOUDAAE_REQUIRE(M > 0 && M <= FC_ROWS * FC_MAX_RT, name, "bad size (rows must be <= 128)");
     CLOUDAAE_REQUIRE(count > 0 && count <= FC_MAX_GROUP && layers, name, "1 to 4 layers per call");
     hipStream_t s = (hipStream_t)stream;
-    const int rts = ceil_div(M, FC_ROWS);
+    const int rts = ceil_div(M, FC_ROWS);      // (a property of the batch: the same for every layer's plan)
     FcBwdGroup g;
     g.count = count;
     int blocks = 0;
@@ -1076,40 +1128,22 @@ CLOUDAAE_API int cloudaae_fc_backward_group(int M, int count, const cloudaae_fc_
         if (l.gamma != nullptr)
             CLOUDAAE_REQUIRE(l.y && l.beta && l.save_mean && l.save_var, name,
                              "batch norm needs y, beta and the saved moments");
-        const int slices = ceil_div(l.N, FC_TN), ktiles = ceil_div(l.K, 32);
-        // Few tiles (every layer but the wide output one): one tile per workgroup, its four waves share
-        // it, everything resident at once.  Many tiles: a wave per tile, workgroups for the resident set.
-        const bool fine = (long long)slices * ktiles <= 1024;
-        int by;
-        if (fine) {
-            // (several row tiles: every workgroup of a slice derives dY for all rows of the slice again -- 128 KB of
-            // L2 reads at 128 rows -- so a workgroup keeps two tiles)
-            by = ceil_div(ktiles, rts > 1 ? 2 : 1);
-        } else {
-            const int want = 384;
-            by = ceil_div(want, slices);
-            const int most = ceil_div(ktiles, 4);
-            by = by > most ? most : by;
-            by = by < 1 ? 1 : by;
-        }
-        const int tpb = ceil_div(ktiles, by);
-        by = ceil_div(ktiles, tpb);
+        const FcBwdPlan p = fc_bwd_plan(M, l.K, l.N);
         FcBwdArgs &a = g.p[i];
-        a.M = M; a.K = l.K; a.N = l.N; a.ldx = l.ldx; a.lddo = l.lddo; a.lddx = l.lddx; a.tiles_per_block = tpb;
+        a.M = M; a.K = l.K; a.N = l.N; a.ldx = l.ldx; a.lddo = l.lddo; a.lddx = l.lddx; a.tiles_per_block = p.tiles_per_block;
         a.acc_dw = l.accumulate_dw; a.acc_pg = l.accumulate_param_grads; a.training = training; a.relu = l.relu;
-        a.block0 = blocks; a.slices = slices; a.parts = fine ? 4 : 2;
+        a.block0 = blocks; a.slices = p.slices; a.parts = p.parts;
         a.vec = l.N % 4 == 0 && aligned16(l.w) && (l.dw == nullptr || aligned16(l.dw));
         a.x = l.x; a.w = l.w; a.y = l.y; a.gamma = l.gamma; a.beta = l.beta; a.save_mean = l.save_mean;
         a.save_var = l.save_var; a.dout = l.dout; a.dx = l.dx; a.dw = l.dw; a.dgamma = l.dgamma;
         a.dbeta = l.dbeta; a.dbias = l.dbias;
-        blocks += slices * by;
+        blocks += p.slices * p.by;
     }
-    if (rts == 1)
-        hipLaunchKernelGGL(fc_bwd_kernel<1>, dim3(blocks), dim3(256), 0, s, g);
-    else if (rts == 2)
-        hipLaunchKernelGGL(fc_bwd_kernel<2>, dim3(blocks), dim3(256), 0, s, g);
-    else
-        hipLaunchKernelGGL(fc_bwd_kernel<4>, dim3(blocks), dim3(256), 0, s, g);
+    switch (fc_bwd_rt(rts)) {
+    case 1: hipLaunchKernelGGL(fc_bwd_kernel<1>, dim3(blocks), dim3(256), 0, s, g); break;
+    case 2: hipLaunchKernelGGL(fc_bwd_kernel<2>, dim3(blocks), dim3(256), 0, s, g); break;
+    default: hipLaunchKernelGGL(fc_bwd_kernel<4>, dim3(blocks), dim3(256), 0, s, g); break;
+    }
     CLOUDAAE_CHECK_LAUNCH(name);
     return 0;
 }

@@ -54,7 +54,7 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * cloudaae_vsd_counts and cloudaae_pose_max_dist with its workspace query; cloudaae_depth_normals and
  * cloudaae_depth_sensor_noise; cloudaae_frame_clouds with its workspace query and cloudaae_rendered_scene;
  * cloudaae_transform_hausdorff with its workspace query; cloudaae_nearest_equivalent_pose; cloudaae_pose_compose,
- * cloudaae_depth_fit_counts and cloudaae_select_pose. */
+ * cloudaae_depth_fit_counts and cloudaae_select_pose; cloudaae_fc_plan (host-only path query). */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -463,7 +463,8 @@ int cloudaae_colsum_f32(int M, int C, const float *x, int ldx, float *out, int a
  *
  * forward: y[M,N] = x[M,K] w[K,N] + bias (bias may be NULL); with gamma != NULL also the batch norm of
  * y (arguments as cloudaae_bn_forward) into out[M,N], y keeping the pre-normalisation values the
- * backward needs.  gamma == NULL: no batch norm, only y is written.
+ * backward needs.  gamma == NULL: no batch norm, only y is written, and `relu` is ignored in both directions
+ * (there is no activation without the batch norm: dout is then the gradient of y as it is).
  * tickets: cloudaae_fc_forward_tickets(M, N) ints holding ZERO, left zero by the call (arrival counters:
  * the product is cut over K -- and over 32-row tiles of the batch -- across workgroups; the last to
  * arrive at a column tile sums the pieces and, with batch norm, normalises the column tile);
@@ -477,6 +478,17 @@ int cloudaae_colsum_f32(int M, int C, const float *x, int ldx, float *out, int a
 int cloudaae_fc_max_rows(void);
 int cloudaae_fc_forward_tickets(int M, int N);
 long long cloudaae_fc_forward_partials(int M, int K, int N, int batch_norm);
+/* Which kernel path a layer of these sizes takes (host only, launches nothing; what the launch code derives, from the
+ * same helpers).  batch_norm: gamma != NULL; vec: the launch would find its pointers 16-byte aligned and its sizes whole
+ * quads (forward: K % 8 == 0, ldx % 4 == 0, N % 4 == 0, x and w aligned; backward: N % 4 == 0, w and dw aligned);
+ * scratch: tickets and partials are given.  Six ints into out:
+ *   forward : cq (columns per lane: tiles of 32 cq columns), tiles (column tiles), rts (32-row tiles), splits (K slices),
+ *             kslice (k per slice), combine (partial tiles meet in the scratch)
+ *   backward: RT (row tiles the kernel is built for: 1, 2 or 4), fine (four waves share a tile of W) or not (a wave per
+ *             tile), parts (4 or 2 accordingly), tiles_per_block, by (workgroups per 128-column slice), staged (W read
+ *             in whole lines through LDS: vec, one row tile, not fine)
+ * Returns 0, or 1 for sizes the entry points refuse. */
+int cloudaae_fc_plan(int backward, int M, int K, int N, int batch_norm, int vec, int scratch, int *out);
 int cloudaae_fc_forward(int M, int K, int N, const float *x, int ldx, const float *w, const float *bias,
                         const float *gamma, const float *beta, int training, const float *decay,
                         float *ema_mean, float *ema_var, float *save_mean, float *save_var, int relu,

@@ -22,6 +22,7 @@ def test_library_exports_every_declared_symbol():
     lib = ctypes.CDLL(path)
     declared = _declared()
     assert len(declared) >= 8
+    assert "cloudaae_fc_plan" in declared       # the path query tests/test_35_fc_paths_gpu.py states its coverage with
     missing = [n for n in declared if not hasattr(lib, n)]
     assert not missing, missing
     # one ABI revision: the header's, the library's and the Python host's signature table (cloudaae_amd/_lib.py)
