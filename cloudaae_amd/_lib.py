@@ -152,6 +152,10 @@ _SIGNATURES = {
     "cloudaae_ppf_vote": [_I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P,
                           _P, _P, _P, _P, _P, _P],
     "cloudaae_ppf_cluster": [_I, _I, _P, _P, _P, _I, _P, _D, _I, _P, _P, _P, _P, _P, _P],
+    "cloudaae_depth_plane": [_I, _I, _I, _P, _P, _U, _L, _I, _I, _D, _I, _P, _P, _P, _P, _P],
+    "cloudaae_depth_foreground": [_I, _I, _I, _P, _P, _P, _P, _D, _D, _P, _P],
+    "cloudaae_depth_components": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P],
+    "cloudaae_component_labels": [_I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P],
 }
 
 
@@ -375,7 +379,9 @@ def lib():
                        ("cloudaae_pose_max_dist_workspace_bytes", [_I, _I, _I]),
                        ("cloudaae_transform_hausdorff_workspace_bytes", [_I]),
                        ("cloudaae_estimate_normals_workspace_bytes", [_I, _L]),
-                       ("cloudaae_cloud_diameter_workspace_bytes", [_I, _I])):
+                       ("cloudaae_cloud_diameter_workspace_bytes", [_I, _I]),
+                       ("cloudaae_depth_components_workspace_bytes", [_I, _I, _I]),
+                       ("cloudaae_component_labels_workspace_bytes", [_I, _I, _I])):
             getattr(cdll, q).argtypes = sig
             getattr(cdll, q).restype = ctypes.c_longlong
         cdll.cloudaae_gemm_f32_splits.argtypes = [_I, _I, _I]

@@ -420,7 +420,7 @@ VALID_SEQ_ID = [[48, 51, 55, 56], [50, 54, 59], [49, 51, 54, 55, 58], [50, 51, 5
 
 
 def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, device=None, keep_frames=False,
-                        keep_labels=False):
+                        keep_labels=False, labels="record", components=None, counts=None):
     """create_tfrecord_dataset (:287-335) on decoded frame records (tfrecord_io.decode_frame): the frames that hold
     target_cls, their target_cls segment, the mean-distance filter, radius outlier removal, FPS_random of the inliers
     and of the filtered points from seeded starts, the > 100 and >= num_point rules, quat2axangle, the object model,
@@ -431,18 +431,56 @@ def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, devic
     sample's own frame, frame_depth [B,H,W] int16 (the uint16 bits) and frame_intrinsics [B,5] float32 (device tensors):
     what evaluate_batch(bop=...) compares the rendered object with.  keep_labels=True adds frame_label [B,H,W] uint8, the
     same frame's label image, and frame_want [B] int32, the label value by which extract_segments selects target_cls
-    (target_cls + 1): what evaluate_batch(verify=...) takes the object's segment from."""
+    (target_cls + 1): what evaluate_batch(verify=...) takes the object's segment from.
+    labels="components" (the default "record" uses the records' label images): the label images are found from the depth
+    alone by utils.depth_components.segment_depth(depth, intrinsics, **components) -- components: its parameters, seed and
+    first_frame among them -- on every frame of the call, so that frame i of `frames` draws its plane hypotheses from
+    first_frame + i whether or not its neighbours hold the class.  The record's label serves for association only: the component with the largest IoU against
+    its target_cls + 1 pixels (match_components) takes their place, as value target_cls + 1 of an otherwise empty label
+    image, and everything after is unchanged.  Frames without such a component are dropped.  The element gains
+    segment_iou [B] float64 (numpy), and with keep_labels frame_label is the found image; counts, a dict, has the frames
+    that hold the class added to its 'frames' and those with a component to its 'matched'."""
     from .train_cloudAAE_ycbv import get_object_model, get_rotation_matrix, transform_object_model
     from .utils import hidden_point_removal as hpr
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    frames = [f for f in frames if int(f["class_one_hot"][target_cls]) == 1]      # :294
+    require(labels in ("record", "components"), "labels must be 'record' or 'components'")
+    require(components is None or labels == "components", "components= needs labels='components'")
+    position = [i for i, f in enumerate(frames) if int(f["class_one_hot"][target_cls]) == 1]
+    chunk = frames                                                                # (components mode segments all of it)
+    frames = [frames[i] for i in position]                                        # :294
     if not frames:
         return None
-    shapes = {f["depth"].shape for f in frames}
+    shapes = {f["depth"].shape for f in (chunk if labels == "components" else frames)}
     require(len(shapes) == 1, "frames of one call must share their size")
     depth = np.stack([f["depth"] for f in frames])
     label = np.stack([f["label"] for f in frames])
     intr = np.array([[f["fx"], f["fy"], f["cx"], f["cy"], f["factor_depth"]] for f in frames], np.float32)
+    segment_iou = None
+    if labels == "components":
+        from .utils import depth_components as dc_util
+        # every frame of the call is segmented, also those without the class: frame i of the call then has the global
+        # index first_frame + i whatever its neighbours hold
+        found = dc_util.segment_depth(
+            np.stack([f["depth"] for f in chunk]),
+            np.array([[f["fx"], f["fy"], f["cx"], f["cy"], f["factor_depth"]] for f in chunk], np.float32), device=device,
+            **(components or {}))
+        found_label = found.label.index_select(0, torch.tensor(position, dtype=torch.int64, device=device))
+        ks, ious = dc_util.match_components(found_label, torch.from_numpy(np.ascontiguousarray(label, np.uint8)).to(device),
+                                            depth, int(target_cls) + 1)
+        hit = np.nonzero(ks > 0)[0]
+        if counts is not None:
+            counts["frames"] = counts.get("frames", 0) + len(frames)
+            counts["matched"] = counts.get("matched", 0) + len(hit)
+        if len(hit) == 0:
+            return None
+        k_dev = torch.from_numpy(ks[hit]).to(device=device, dtype=torch.uint8)[:, None, None]
+        sel_f = torch.from_numpy(hit).to(device)
+        relabelled = torch.where(found_label.index_select(0, sel_f) == k_dev,
+                                 torch.full((), int(target_cls) + 1, dtype=torch.uint8, device=device),
+                                 torch.zeros((), dtype=torch.uint8, device=device))
+        frames = [frames[int(i)] for i in hit]
+        depth, intr, segment_iou = depth[hit], intr[hit], ious[hit]
+        label = relabelled.cpu().numpy()
     r = seg_util.extract_segments(depth, label, intr, classes=[[target_cls]] * len(frames),
                                   quaternions=np.stack([f["quaternions"] for f in frames]),
                                   translations=np.stack([f["translations"] for f in frames]), num_point=num_point,
@@ -476,6 +514,8 @@ def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, devic
         of = np.asarray(r.frame, np.int64)[keep]
         el["frame_label"] = torch.from_numpy(np.ascontiguousarray(label[of].astype(np.uint8))).to(device)
         el["frame_want"] = torch.full((B,), int(target_cls) + 1, dtype=torch.int32, device=device)
+    if segment_iou is not None:
+        el["segment_iou"] = segment_iou[np.asarray(r.frame, np.int64)[keep]]
     return el
 
 
@@ -538,9 +578,12 @@ def main(argv=None):
     in every summary, and after the summaries one line per class says how often which hypothesis was kept.  --propose ppf
     (with --verify --meshes): --propose_top pose proposals by point-pair-feature voting on --propose_points oriented
     points of the class's mesh (utils/ppf.py) join the candidates, and a last line per class says how many winners came
-    from the prediction, from a flip and from a proposal."""
+    from the prediction, from a flip and from a proposal.  --labels components (with the --components_* parameters): the
+    label images are found from the depth alone (element_from_frames(labels="components")); a last line says how many
+    frames held the class, how many of them had a matching component, and the mean IoU of the segments that were kept."""
     from . import tfrecord_io
     from . import train_cloudAAE_ycbv as T
+    from .utils import depth_components as dc_util
     p = argparse.ArgumentParser()
     p.add_argument("--data_dir", default="ycb_video_data_tfRecords")
     p.add_argument("--files", default=None,
@@ -570,6 +613,18 @@ def main(argv=None):
                    help="add pose proposals by point-pair-feature voting to the candidates of --verify (needs --verify --meshes)")
     p.add_argument("--propose_top", type=int, default=4, help="proposals per sample")
     p.add_argument("--propose_points", type=int, default=256, help="oriented points of the class's mesh in the pair table")
+    p.add_argument("--labels", default="record", choices=("record", "components"),
+                   help="record: the records' label images; components: label images found from the depth alone "
+                        "(utils/depth_components.py), the record's label associating the class with a component")
+    p.add_argument("--components_n_hyp", type=int, default=dc_util.N_HYP, help="plane hypotheses per frame")
+    p.add_argument("--components_stride", type=int, default=dc_util.STRIDE, help="every stride-th pixel votes for the plane")
+    p.add_argument("--components_tol", type=float, default=dc_util.TOL, help="distance of a plane inlier, metres")
+    p.add_argument("--components_max_height", type=float, default=dc_util.MAX_HEIGHT, help="foreground height above the plane, metres")
+    p.add_argument("--components_min_plane_percent", type=int, default=dc_util.MIN_PLANE_PERCENT,
+                   help="a plane needs this share of the tested pixels")
+    p.add_argument("--components_jump", type=float, default=dc_util.JUMP, help="depth step that cuts a component, metres")
+    p.add_argument("--components_min_pixels", type=int, default=dc_util.MIN_PIXELS)
+    p.add_argument("--components_max", type=int, default=dc_util.MAX_COMPONENTS, help="components kept per frame")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--frames_per_launch", type=int, default=8)
     p.add_argument("--gpu", type=int, default=0)
@@ -665,10 +720,22 @@ def main(argv=None):
             if buf:
                 yield buf
 
+    comp_counts, comp_iou, n_frames_seen = {}, [], 0
     for chunk in frames():
+        comp = {}
+        if args.labels == "components":
+            comp = dict(labels="components", counts=comp_counts,
+                        components=dict(seed=args.seed, first_frame=n_frames_seen, n_hyp=args.components_n_hyp,
+                                        stride=args.components_stride, tol=args.components_tol,
+                                        max_height=args.components_max_height,
+                                        min_plane_percent=args.components_min_plane_percent, jump=args.components_jump,
+                                        min_pixels=args.components_min_pixels, max_components=args.components_max))
         el = element_from_frames(chunk, args.target_cls, args.num_point, models, seed=args.seed + n_launch,
-                                 keep_frames=args.bop or args.verify, keep_labels=args.verify)
+                                 keep_frames=args.bop or args.verify, keep_labels=args.verify, **comp)
         n_launch += 1
+        n_frames_seen += len(chunk)
+        if el is not None and "segment_iou" in el:
+            comp_iou.append(el["segment_iou"])
         if el is None:
             continue
         pending = el if pending is None else {k: (torch.cat([pending[k], v]) if isinstance(v, torch.Tensor)
@@ -724,6 +791,11 @@ def main(argv=None):
     if propose is not None:
         for line in propose_lines([r[:2] for r in verify_rows], verify['hypotheses'].max_members):
             print(line)
+    if args.labels == "components":
+        iou = np.concatenate(comp_iou) if comp_iou else np.zeros(0)
+        print("components class %d frames %d matched %d mean_iou %f" % (args.target_cls, comp_counts.get("frames", 0),
+                                                                        comp_counts.get("matched", 0),
+                                                                        float(iou.mean()) if len(iou) else 0.0))
     sys.stdout.flush()
     return 0
 

@@ -54,7 +54,8 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * cloudaae_vsd_counts and cloudaae_pose_max_dist with its workspace query; cloudaae_depth_normals and
  * cloudaae_depth_sensor_noise; cloudaae_frame_clouds with its workspace query and cloudaae_rendered_scene;
  * cloudaae_transform_hausdorff with its workspace query; cloudaae_nearest_equivalent_pose; cloudaae_pose_compose,
- * cloudaae_depth_fit_counts and cloudaae_select_pose; cloudaae_fc_plan (host-only path query). */
+ * cloudaae_depth_fit_counts and cloudaae_select_pose; cloudaae_fc_plan (host-only path query); cloudaae_depth_plane,
+ * cloudaae_depth_foreground, cloudaae_depth_components and cloudaae_component_labels, the last two with a workspace query. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -1290,6 +1291,53 @@ int cloudaae_ppf_vote(int b, int n, const float *scene, const double *scene_norm
 int cloudaae_ppf_cluster(int b, int c, const int *votes, const double *pose, const long long *class_id, int nclass,
                          const double *trans_thresh2, double rot_bound, int top, double *pose_out, double *rot_axag, float *trans,
                          int *score, int *valid, cloudaae_stream_t stream);
+
+/* ---- object candidates from unlabelled depth frames ("Depth components", has the definition) ---- */
+
+/* Shared by the calls below.  depth [f,h,w] uint16, intrinsics [f,5] float (fx, fy, cx, cy, factor_depth); pixel (u, v) has
+ * index p = v w + u within its frame and is valid when its depth is not 0.  Points are back-projected in fp32 as
+ * cloudaae_frame_segments does, then widened; everything after is double, + - * in the written order, no fma.  All
+ * memory is device memory.  Limits of every call: f >= 0; h, w >= 1; h w <= 2^24; f h w <= 2^28; outside them, or with a
+ * null pointer, an error and no launch.  f = 0 is not an error: nothing is launched and nothing written. */
+
+/* The dominant plane of each frame.  Hypothesis hy of frame fr: r = philox4x32(seed, ((first_frame + fr) << 20) | hy, stream
+ * 25); its pixels p_k = (r[k] (h w)) >> 32, k = 0, 1, 2; void when one of them is invalid; n = (P1 - P0) x (P2 - P0), each
+ * component a b - c d; q = (nx nx + ny ny) + nz nz, void unless q > 0; d = -((nx P0x + ny P0y) + nz P0z); n and d change sign
+ * when d < 0.  The tested pixels are the valid ones with u and v multiples of stride; P is an inlier when s s <= (tol tol) q,
+ * s = ((nx Px + ny Py) + nz Pz) + d.  count [f,n_hyp] int (0 for a void hypothesis) and tested [f] int are zeroed by the
+ * call.  The winner is the largest count, ties to the lowest hy; the frame has a plane when count >= 3 and count 100 >=
+ * min_plane_percent tested: plane [f,4] double = (n, d) of the winner, un-normalised, and plane_hyp [f] int = hy; otherwise
+ * zeros and -1.  Two memsets and two launches; integer atomics only.  Limits: 1 <= n_hyp <= 4096; stride >= 1;
+ * 0 <= first_frame <= 2^40; 0 <= min_plane_percent <= 100; tol >= 0. */
+int cloudaae_depth_plane(int f, int h, int w, const uint16_t *depth, const float *intrinsics, unsigned long long seed,
+                         long long first_frame, int n_hyp, int stride, double tol, int min_plane_percent, int *count,
+                         int *tested, double *plane, int *plane_hyp, cloudaae_stream_t stream);
+
+/* fg [f,h,w] uint8 (1 or 0).  A frame with plane_hyp >= 0: valid and s > 0 and s s > (tol tol) q and s s <= (max_height
+ * max_height) q, with q formed again from plane [f,4]; a frame with plane_hyp < 0: valid.  One launch.  tol, max_height >= 0. */
+int cloudaae_depth_foreground(int f, int h, int w, const uint16_t *depth, const float *intrinsics, const double *plane,
+                              const int *plane_hyp, double tol, double max_height, uint8_t *fg, cloudaae_stream_t stream);
+
+/* Connected components.  Two 4-adjacent pixels are joined when both have fg != 0 and their depths, widened to int, differ by
+ * at most jump_units [f] int (a negative entry joins nothing).  root [f,h,w] int = the smallest pixel index of the pixel's
+ * component, -1 where fg = 0: a pure function of the input.  status [f] int is zeroed by the call; a bit is set when a
+ * bounded walk ran into its bound (1: inside a tile, 2: across tile borders, 4: the final walk), which no input should
+ * cause -- the roots of that frame are then not to be trusted.  One memset and three launches (32 x 32 tiles in LDS, the
+ * pixel pairs across tile borders, the final roots); no workgroup waits for another. */
+long long cloudaae_depth_components_workspace_bytes(int f, int h, int w);
+int cloudaae_depth_components(int f, int h, int w, const uint16_t *depth, const uint8_t *fg, const int *jump_units, int *root,
+                              int *status, void *workspace, long long workspace_bytes, cloudaae_stream_t stream);
+
+/* The component table of root [f,h,w] int as cloudaae_depth_components writes it (an entry outside [0, h w) counts as
+ * background).  The candidates of a frame are the components of at least min_pixels pixels, ordered by (size descending,
+ * root ascending); the first K = min(candidates, max_components) are kept.  label [f,h,w] uint8 = k + 1 on the pixels of
+ * component k, else 0; n_components [f] int = K; n_candidates [f] int = the candidates before the cap; comp_root, comp_size
+ * [f,max_components] int and comp_box [f,max_components,4] int = (u_min, v_min, u_max, v_max), -1 past K.  One memset and
+ * four launches; integer atomics only.  Limits: min_pixels >= 1; 1 <= max_components <= 254. */
+long long cloudaae_component_labels_workspace_bytes(int f, int h, int w);
+int cloudaae_component_labels(int f, int h, int w, const int *root, int min_pixels, int max_components, uint8_t *label,
+                              int *n_components, int *n_candidates, int *comp_root, int *comp_size, int *comp_box,
+                              void *workspace, long long workspace_bytes, cloudaae_stream_t stream);
 
 #ifdef __cplusplus
 }
