@@ -156,6 +156,9 @@ _SIGNATURES = {
     "cloudaae_depth_foreground": [_I, _I, _I, _P, _P, _P, _P, _D, _D, _P, _P],
     "cloudaae_depth_components": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P],
     "cloudaae_component_labels": [_I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P],
+    "cloudaae_depth_fit_counts_window": [_I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
+    "cloudaae_detect_assign": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                               _P, _P, _P, _P, _P],
 }
 
 

@@ -420,7 +420,7 @@ VALID_SEQ_ID = [[48, 51, 55, 56], [50, 54, 59], [49, 51, 54, 55, 58], [50, 51, 5
 
 
 def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, device=None, keep_frames=False,
-                        keep_labels=False, labels="record", components=None, counts=None):
+                        keep_labels=False, labels="record", components=None, counts=None, choose="record", detector=None):
     """create_tfrecord_dataset (:287-335) on decoded frame records (tfrecord_io.decode_frame): the frames that hold
     target_cls, their target_cls segment, the mean-distance filter, radius outlier removal, FPS_random of the inliers
     and of the filtered points from seeded starts, the > 100 and >= num_point rules, quat2axangle, the object model,
@@ -439,12 +439,24 @@ def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, devic
     its target_cls + 1 pixels (match_components) takes their place, as value target_cls + 1 of an otherwise empty label
     image, and everything after is unchanged.  Frames without such a component are dropped.  The element gains
     segment_iou [B] float64 (numpy), and with keep_labels frame_label is the found image; counts, a dict, has the frames
-    that hold the class added to its 'frames' and those with a component to its 'matched'."""
+    that hold the class added to its 'frames' and those with a component to its 'matched'.
+    choose="detect" (with labels="components"; the default "record" is the above): the component is chosen without the
+    record's label, by utils.detect.detect_objects(depth, intrinsics, segments=the found ones, seed and first_frame of
+    components, **detector) on every frame of the call -- detector: its meshes, ppf_models and parameters -- as the
+    component it assigned to target_cls (the earliest round when there are several).  The record's label is read only to
+    report: segment_iou is the chosen component's IoU against the record's target_cls + 1 pixels, detect_agree [B] bool
+    (numpy) says whether match_components would have picked the same component, and counts gains 'detected' (in place of
+    'matched') and 'agree'.  Frames in which nothing was assigned to the class are dropped.  (The element is formed before
+    evaluate_batch runs, so replay=True there neither sees nor records the detection.)"""
     from .train_cloudAAE_ycbv import get_object_model, get_rotation_matrix, transform_object_model
     from .utils import hidden_point_removal as hpr
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     require(labels in ("record", "components"), "labels must be 'record' or 'components'")
     require(components is None or labels == "components", "components= needs labels='components'")
+    require(choose in ("record", "detect"), "choose must be 'record' or 'detect'")
+    require(choose == "record" or (labels == "components" and detector is not None),
+            "choose='detect' needs labels='components' and detector=dict(meshes=..., ppf_models=...)")
+    require(detector is None or choose == "detect", "detector= needs choose='detect'")
     position = [i for i, f in enumerate(frames) if int(f["class_one_hot"][target_cls]) == 1]
     chunk = frames                                                                # (components mode segments all of it)
     frames = [frames[i] for i in position]                                        # :294
@@ -455,7 +467,7 @@ def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, devic
     depth = np.stack([f["depth"] for f in frames])
     label = np.stack([f["label"] for f in frames])
     intr = np.array([[f["fx"], f["fy"], f["cx"], f["cy"], f["factor_depth"]] for f in frames], np.float32)
-    segment_iou = None
+    segment_iou, agree = None, None
     if labels == "components":
         from .utils import depth_components as dc_util
         # every frame of the call is segmented, also those without the class: frame i of the call then has the global
@@ -467,10 +479,17 @@ def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, devic
         found_label = found.label.index_select(0, torch.tensor(position, dtype=torch.int64, device=device))
         ks, ious = dc_util.match_components(found_label, torch.from_numpy(np.ascontiguousarray(label, np.uint8)).to(device),
                                             depth, int(target_cls) + 1)
+        if choose == "detect":
+            ks_record = ks
+            ks, ious = _detected_components(chunk, position, found, found_label, label, depth, target_cls, components, detector)
+            agree = ks == ks_record
         hit = np.nonzero(ks > 0)[0]
         if counts is not None:
             counts["frames"] = counts.get("frames", 0) + len(frames)
-            counts["matched"] = counts.get("matched", 0) + len(hit)
+            key = "matched" if choose == "record" else "detected"
+            counts[key] = counts.get(key, 0) + len(hit)
+            if agree is not None:
+                counts["agree"] = counts.get("agree", 0) + int(agree[hit].sum())
         if len(hit) == 0:
             return None
         k_dev = torch.from_numpy(ks[hit]).to(device=device, dtype=torch.uint8)[:, None, None]
@@ -480,6 +499,7 @@ def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, devic
                                  torch.zeros((), dtype=torch.uint8, device=device))
         frames = [frames[int(i)] for i in hit]
         depth, intr, segment_iou = depth[hit], intr[hit], ious[hit]
+        agree = None if agree is None else agree[hit]
         label = relabelled.cpu().numpy()
     r = seg_util.extract_segments(depth, label, intr, classes=[[target_cls]] * len(frames),
                                   quaternions=np.stack([f["quaternions"] for f in frames]),
@@ -516,7 +536,31 @@ def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, devic
         el["frame_want"] = torch.full((B,), int(target_cls) + 1, dtype=torch.int32, device=device)
     if segment_iou is not None:
         el["segment_iou"] = segment_iou[np.asarray(r.frame, np.int64)[keep]]
+    if agree is not None:
+        el["detect_agree"] = agree[np.asarray(r.frame, np.int64)[keep]]
     return el
+
+
+def _detected_components(chunk, position, found, found_label, label, depth, target_cls, components, detector):
+    """For the frames `position` of the call: the label value (k + 1; 0: none) of the component that detect_objects assigned
+    to target_cls, and that component's IoU against the record's target_cls + 1 pixels with depth (the report)."""
+    from .utils import detect as detect_util
+    device = found_label.device
+    comp = components or {}
+    det = detect_util.detect_objects(
+        np.stack([f["depth"] for f in chunk]),
+        np.array([[f["fx"], f["fy"], f["cx"], f["cy"], f["factor_depth"]] for f in chunk], np.float32), segments=found,
+        seed=comp.get("seed", 0), first_frame=comp.get("first_frame", 0), **detector)
+    ks = np.zeros(len(position), np.int64)
+    for i, f in enumerate(position):
+        mine = np.nonzero(det.table["det_class"][f] == int(target_cls))[0]
+        if len(mine):
+            ks[i] = int(mine[np.argmin(det.table["det_rank"][f][mine])]) + 1
+    chosen = (found_label == torch.from_numpy(ks).to(device=device, dtype=torch.uint8)[:, None, None]) & (found_label != 0)
+    target = (torch.from_numpy(np.ascontiguousarray(label, np.uint8)).to(device) == int(target_cls) + 1) & \
+        (torch.from_numpy(np.ascontiguousarray(depth).view(np.int16)).to(device) != 0)
+    both = torch.stack([(chosen & target).sum(dim=(1, 2)), (chosen | target).sum(dim=(1, 2))]).cpu().numpy().astype(np.float64)
+    return ks, np.where(ks > 0, both[0] / np.maximum(both[1], 1.0), 0.0)
 
 
 def verify_lines(rows):
@@ -580,10 +624,16 @@ def main(argv=None):
     points of the class's mesh (utils/ppf.py) join the candidates, and a last line per class says how many winners came
     from the prediction, from a flip and from a proposal.  --labels components (with the --components_* parameters): the
     label images are found from the depth alone (element_from_frames(labels="components")); a last line says how many
-    frames held the class, how many of them had a matching component, and the mean IoU of the segments that were kept."""
+    frames held the class, how many of them had a matching component, and the mean IoU of the segments that were kept.
+    --choose detect (with --labels components --meshes DIR; --detect_classes, --detect_top, --detect_min_score N/D,
+    --detect_margin): the component is chosen by utils.detect.detect_objects among the meshes' classes instead of by the
+    record's label (element_from_frames(choose="detect")); the last line then reads `detect class c frames n detected m
+    agree a mean_iou x`: the frames that held the class, those in which a component was assigned to it, those of them in
+    which the record's label would have picked the same component, and the mean IoU of the segments that were kept."""
     from . import tfrecord_io
     from . import train_cloudAAE_ycbv as T
     from .utils import depth_components as dc_util
+    from .utils import detect as detect_util
     p = argparse.ArgumentParser()
     p.add_argument("--data_dir", default="ycb_video_data_tfRecords")
     p.add_argument("--files", default=None,
@@ -625,6 +675,13 @@ def main(argv=None):
     p.add_argument("--components_jump", type=float, default=dc_util.JUMP, help="depth step that cuts a component, metres")
     p.add_argument("--components_min_pixels", type=int, default=dc_util.MIN_PIXELS)
     p.add_argument("--components_max", type=int, default=dc_util.MAX_COMPONENTS, help="components kept per frame")
+    p.add_argument("--choose", default="record", choices=("record", "detect"),
+                   help="with --labels components: record associates the class with a component by the record's label; "
+                        "detect decides it without the label (utils/detect.py; needs --meshes DIR)")
+    p.add_argument("--detect_classes", default=None, help="comma-separated class ids the detector knows [default: every mesh]")
+    p.add_argument("--detect_top", type=int, default=detect_util.TOP, help="pose proposals per (component, class)")
+    p.add_argument("--detect_min_score", default="%d/%d" % detect_util.MIN_SCORE, help="N/D: a pair below this fraction is not assigned")
+    p.add_argument("--detect_margin", type=float, default=detect_util.MARGIN, help="of a component's box, added on either side")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--frames_per_launch", type=int, default=8)
     p.add_argument("--gpu", type=int, default=0)
@@ -635,6 +692,8 @@ def main(argv=None):
         p.error("--verify needs --meshes DIR")
     if args.propose and not (args.verify and args.meshes):
         p.error("--propose needs --verify and --meshes DIR")
+    if args.choose == "detect" and not (args.labels == "components" and args.meshes):
+        p.error("--choose detect needs --labels components and --meshes DIR")
     args.icp = args.icp or args.icp_plane
     torch.cuda.set_device(args.gpu)
     obj_path = args.object_model or os.path.join(os.path.dirname(os.path.abspath(args.data_dir)),
@@ -709,6 +768,20 @@ def main(argv=None):
                                                               scale=args.mesh_scale, classes=[c], num_class=len(models)),
                        top=args.propose_top)
 
+    detector = None
+    if args.choose == "detect":
+        from .utils import mesh_models
+        mesh_paths = mesh_models.mesh_files(args.meshes)
+        det_classes = (list(range(len(mesh_paths))) if args.detect_classes is None
+                       else [int(c) for c in args.detect_classes.split(",") if c])
+        num, den = (int(x) for x in args.detect_min_score.split("/"))
+        detector = dict(meshes=mesh_models.pack_meshes(mesh_paths, args.mesh_scale),
+                        ppf_models=ppf_util.PPFModels.from_meshes([mesh_paths[c] for c in det_classes],
+                                                                  num_point=args.propose_points, scale=args.mesh_scale,
+                                                                  classes=det_classes, num_class=len(mesh_paths)),
+                        classes=det_classes, top=args.detect_top, min_score=(num, den), margin=args.detect_margin,
+                        num_point=args.num_point)
+
     def frames():
         for fn in files:
             buf = []
@@ -730,6 +803,8 @@ def main(argv=None):
                                         max_height=args.components_max_height,
                                         min_plane_percent=args.components_min_plane_percent, jump=args.components_jump,
                                         min_pixels=args.components_min_pixels, max_components=args.components_max))
+            if detector is not None:
+                comp.update(choose="detect", detector=detector)
         el = element_from_frames(chunk, args.target_cls, args.num_point, models, seed=args.seed + n_launch,
                                  keep_frames=args.bop or args.verify, keep_labels=args.verify, **comp)
         n_launch += 1
@@ -791,7 +866,13 @@ def main(argv=None):
     if propose is not None:
         for line in propose_lines([r[:2] for r in verify_rows], verify['hypotheses'].max_members):
             print(line)
-    if args.labels == "components":
+    if args.choose == "detect":
+        iou = np.concatenate(comp_iou) if comp_iou else np.zeros(0)
+        print("detect class %d frames %d detected %d agree %d mean_iou %f" % (args.target_cls, comp_counts.get("frames", 0),
+                                                                              comp_counts.get("detected", 0),
+                                                                              comp_counts.get("agree", 0),
+                                                                              float(iou.mean()) if len(iou) else 0.0))
+    elif args.labels == "components":
         iou = np.concatenate(comp_iou) if comp_iou else np.zeros(0)
         print("components class %d frames %d matched %d mean_iou %f" % (args.target_cls, comp_counts.get("frames", 0),
                                                                         comp_counts.get("matched", 0),

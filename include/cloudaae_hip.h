@@ -55,7 +55,8 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * cloudaae_depth_sensor_noise; cloudaae_frame_clouds with its workspace query and cloudaae_rendered_scene;
  * cloudaae_transform_hausdorff with its workspace query; cloudaae_nearest_equivalent_pose; cloudaae_pose_compose,
  * cloudaae_depth_fit_counts and cloudaae_select_pose; cloudaae_fc_plan (host-only path query); cloudaae_depth_plane,
- * cloudaae_depth_foreground, cloudaae_depth_components and cloudaae_component_labels, the last two with a workspace query. */
+ * cloudaae_depth_foreground, cloudaae_depth_components and cloudaae_component_labels, the last two with a workspace query;
+ * cloudaae_depth_fit_counts_window and cloudaae_detect_assign. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -1338,6 +1339,52 @@ long long cloudaae_component_labels_workspace_bytes(int f, int h, int w);
 int cloudaae_component_labels(int f, int h, int w, const int *root, int min_pixels, int max_components, uint8_t *label,
                               int *n_components, int *n_candidates, int *comp_root, int *comp_size, int *comp_box,
                               void *workspace, long long workspace_bytes, cloudaae_stream_t stream);
+
+/* ---- detections: which component is which object ("Detections", has the definition) ---- */
+
+/* cloudaae_depth_fit_counts over a window of wh x ww pixels per sample.  depth_test [f,h,w] uint16; label [f,h,w] uint8 or
+ * NULL; frame_of, want, tau [b] int as there; origin [b,2] int = (u0, v0), any values, negative or past the frame included;
+ * depth_hyp [b,p,wh,ww] uint16: the hypothesis rendered into the window (intrinsics with cx - u0, cy - v0).  All device
+ * memory.  Window pixel (x, y), 0 <= x < ww, 0 <= y < wh, is frame pixel (u0 + x, v0 + y); where that lies outside the frame
+ * t = 0 and the pixel is not in the segment, and nothing is read.  Per window pixel t, d, seg and the six predicates are
+ * those of cloudaae_depth_fit_counts; hypothesis pixels outside the window do not exist for this call.  Outputs (zeroed
+ * by the call): counts [b,p,6] int, seg_total [b] int = #seg inside the window, abs_sum [b,p] long long.  With origin (0, 0),
+ * wh = h and ww = w every output equals cloudaae_depth_fit_counts's.  Three memsets and one launch; integer atomics only,
+ * so the results do not depend on the order of execution, the batch or the run.  A frame_of entry outside [0, f) leaves
+ * that sample's counts 0 and causes no access.  Any ww >= 1 is taken (a lane's eight pixels may straddle rows); 16-byte
+ * loads are used only where an address allows it.  Limits: f, h, w, b, p, wh, ww >= 1; h * w <= 2^24; wh * ww <= 2^24;
+ * b * p * wh * ww <= 2^28; outside them, or with a null pointer other than label (and want with it), the call returns an
+ * error and launches nothing. */
+int cloudaae_depth_fit_counts_window(int f, int h, int w, const uint16_t *depth_test, const uint8_t *label, int b, int p,
+                                     const int *frame_of, const int *want, const int *origin, int wh, int ww,
+                                     const uint16_t *depth_hyp, const int *tau, int *counts, int *seg_total, long long *abs_sum,
+                                     cloudaae_stream_t stream);
+
+/* The decision over the (component, class) pairs of each frame.  counts [f,k,c,p,6] and seg_total [f,k,c] int as
+ * cloudaae_depth_fit_counts_window writes them for sample (fr k + kk) c + cc; valid [f,k,c,p] int; pose [f,k,c,p,16] double;
+ * n_components [f] int (clamped into [0, k]); mode 0 or 1: the two rules of cloudaae_select_pose; the threshold min_num /
+ * min_den; max_per_class.  All device memory.
+ * Step 1.  The fraction of a hypothesis is cloudaae_select_pose's (num, den), and 0 / 1 when den <= 0, num < 0, valid = 0 or
+ * kk >= n_components.  Hypothesis j beats i when num_j den_i > num_i den_j in 64-bit integers (exact for counts that
+ * cloudaae_depth_fit_counts_window wrote: num <= 2^24, den < 2^26); pair_hyp [f,k,c] int is the lowest index that no other
+ * beats, pair_num, pair_den [f,k,c] int its fraction and pair_score [f,k,c] double = (double)num / (double)den.
+ * Step 2, at most n_components rounds.  A pair is eligible when its component is unassigned, its class has been assigned
+ * fewer than max_per_class times, num > 0 and num min_den >= min_num den.  The eligible pair with the largest fraction,
+ * compared as above, ties to the lowest kk and then the lowest cc, is assigned in round r = 0, 1, ...; the rounds end
+ * when nothing is eligible.
+ * Outputs per (fr, kk), all written: det_class int (-1: none), det_hyp int = pair_hyp of the assigned pair (-1), det_num,
+ * det_den int (0, 1), det_score double = (double)det_num / (double)det_den, det_rank int = r (-1), det_pose [16] double =
+ * pose of the chosen hypothesis bit for bit (zeros); alt_class, alt_num, alt_den int: the pair of the same component with
+ * the largest fraction among the classes other than det_class (all classes when there is none), availability and the
+ * threshold ignored, ties to the lowest cc; -1, 0, 1 when c = 1 leaves no other class.  n_det [f] int = the assignments.
+ * One launch, one workgroup per frame, no atomics; no workgroup waits for another and every loop is bounded.
+ * Limits: f >= 1; 1 <= k <= 254; 1 <= c <= 256; 1 <= p <= 64; f k c p <= 2^28; 0 <= min_num <= min_den; 1 <= min_den <=
+ * 2^20; max_per_class >= 1; outside them, or with a null pointer, the call returns an error and launches nothing. */
+int cloudaae_detect_assign(int f, int k, int c, int p, const int *counts, const int *seg_total, const int *valid,
+                           const double *pose, const int *n_components, int mode, int min_num, int min_den, int max_per_class,
+                           int *pair_hyp, int *pair_num, int *pair_den, double *pair_score, int *det_class, int *det_hyp,
+                           int *det_num, int *det_den, double *det_score, int *det_rank, double *det_pose, int *alt_class,
+                           int *alt_num, int *alt_den, int *n_det, cloudaae_stream_t stream);
 
 #ifdef __cplusplus
 }
