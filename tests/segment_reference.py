@@ -128,6 +128,34 @@ def extract(frames, classes_per_frame, threshold=THRESHOLD, nb_points=NB_POINTS,
     return out
 
 
+def extract_listed(frames, seg_frame, seg_class, threshold=THRESHOLD, nb_points=NB_POINTS, radius=RADIUS,
+                   min_keep=MIN_KEEP):
+    """The table rule of cloudaae_frame_segments for any segment list: segment i is the pair (seg_frame[i],
+    seg_class[i]); one dict per segment, in list order, with the keys of `extract` and mask_xyz.  A pair named more than
+    once keeps only its last entry; the earlier entries, and every pair whose frame lies outside [0, F) or whose class
+    lies outside [0, 254], are empty segments (no point, mean 0).  A pixel whose class is not listed belongs to
+    nothing."""
+    F = len(frames)
+    owner = {}
+    for i, (f, c) in enumerate(zip(seg_frame, seg_class)):
+        if 0 <= int(f) < F and 0 <= int(c) <= 254:
+            owner[(int(f), int(c))] = i                      # a later entry replaces an earlier one
+    none = np.zeros((0, 3), np.float32)
+    out = []
+    for i, (f, c) in enumerate(zip(seg_frame, seg_class)):
+        f, c = int(f), int(c)
+        if owner.get((f, c)) == i:
+            depth, label, intr = frames[f]
+            seg = frame_segments(depth, label, intr, [c], threshold)[0]
+        else:
+            seg = dict(mask_xyz=none, mean=np.zeros(3, np.float32), xyz=none)
+        idx, nv = radius_outlier(seg['xyz'], nb_points, radius, min_keep)
+        out.append(dict(frame=f, cls=c, mask_xyz=seg['mask_xyz'], xyz=seg['xyz'], mean=seg['mean'],
+                        num_point_after_filter=len(seg['xyz']), inlier_idx=idx, xyz_inlier_full=seg['xyz'][idx],
+                        num_valid_points_in_segment=nv))
+    return out
+
+
 def quat2axangle(q):
     """transforms3d.quaternions.quat2axangle (w, x, y, z) with identity_thresh None (3 float64 eps): (axis, angle)."""
     q = np.asarray(q, dtype=np.float64)

@@ -112,6 +112,59 @@ def test_fps_and_mean_match_plain_loops():
     assert np.array_equal(R.segment_mean(pts), np.array([a / 1000 for a in acc], np.float32))
 
 
+def _same_segment(a, b):
+    for k in ("frame", "cls", "num_point_after_filter", "num_valid_points_in_segment"):
+        assert a[k] == b[k], k
+    for k in ("xyz", "mean", "xyz_inlier_full"):
+        assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
+    assert np.array_equal(a["inlier_idx"], b["inlier_idx"])
+
+
+def test_extract_listed_equals_extract_on_frame_major_lists():
+    rng = np.random.default_rng(4)
+    frames = []
+    for f in range(3):
+        depth = rng.integers(4000, 9000, (9, 11)).astype(np.uint16)
+        depth[rng.random(depth.shape) < 0.3] = 0
+        label = rng.choice(np.array([0, 1, 4, 8, 255], np.uint8), depth.shape)
+        frames.append((depth, label, np.array([50.0 + f, 52.0, 5.0, 4.0 + f, 10000.0], np.float32)))
+    classes = [[0, 3, 7, 254], [3], [0, 5, 254]]                      # class 5 has no pixel
+    params = dict(threshold=np.float32(0.15), nb_points=2, radius=np.float32(0.05), min_keep=3)
+    want = R.extract(frames, classes, **params)
+    seg_frame = [f for f, cl in enumerate(classes) for _ in cl]
+    seg_class = [c for cl in classes for c in cl]
+    got = R.extract_listed(frames, seg_frame, seg_class, **params)
+    assert len(got) == len(want) == 8
+    for a, b in zip(got, want):
+        _same_segment(a, b)
+    assert sum(s["num_point_after_filter"] for s in want) > 20
+    assert any(0 < len(s["inlier_idx"]) < s["num_point_after_filter"] for s in want)
+
+
+def test_extract_listed_duplicate_and_invalid_rules():
+    depth = np.arange(1, 17, dtype=np.uint16).reshape(4, 4) * 500
+    depth[1, 2] = 0
+    label = np.array([[1, 1, 2, 2], [1, 1, 2, 2], [3, 3, 255, 255], [3, 3, 0, 0]], np.uint8)
+    intr = np.array([4.0, 4.0, 1.5, 1.5, 1000.0], np.float32)
+    frames = [(depth, label, intr), (depth[::-1].copy(), label, intr)]
+    params = dict(threshold=np.float32(np.inf), nb_points=0, min_keep=0)
+    #            0  1   2  3  4    5    6    7  8   9
+    seg_frame = [1, 0, -1, 0, 2,   0,   0,   0, 0,  1]
+    seg_class = [0, 1,  1, 0, 0, 255, 300,  -1, 1, 254]
+    got = R.extract_listed(frames, seg_frame, seg_class, **params)
+    assert [s["num_point_after_filter"] for s in got] == [4, 0, 0, 4, 0, 0, 0, 0, 3, 1]   # class 2 (label 3): not listed
+    for i, s in enumerate(got):
+        assert (s["frame"], s["cls"]) == (seg_frame[i], seg_class[i])                        # list order
+    alone = R.extract(frames, [[0, 1], [0, 254]], **params)                                 # 0/0, 0/1, 1/0, 1/254
+    for i, j in ((3, 0), (8, 1), (0, 2), (9, 3)):
+        _same_segment(got[i], alone[j])
+    for i in (1, 2, 4, 5, 6, 7):                      # the earlier of two entries, and every invalid pair: empty
+        s = got[i]
+        assert s["xyz"].shape == (0, 3) and s["mask_xyz"].shape == (0, 3) and not s["mean"].any()
+        assert len(s["inlier_idx"]) == 0 and s["num_valid_points_in_segment"] == 0
+    assert len(got[8]["mask_xyz"]) == 3                # depth 0 at (1, 2) is masked out of class 1
+
+
 def test_quat2axangle_matches_the_rotation():
     from cloudaae_amd.utils import segment as S
     rng = np.random.default_rng(2)
