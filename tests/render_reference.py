@@ -3,12 +3,30 @@ draw rank per pixel.  Written from the definition.  Screen coordinates, areas an
 band keeps them below 2^52), the floating-point part is float64 on the widened float32 inputs in the order the definition
 writes it (NumPy does not fuse a product into a sum), and the depth test is the minimum of an integer key -- so every
 output is an integer and is expected to equal the kernel's bit for bit.  Triangles are drawn one after the other, in
-rank order; the order does not matter."""
+rank order; the order does not matter.
+
+`variant` (project, draw_triangle, render) names deliberate departures from the definition, one boundary each; the
+default, no variant, is the definition.  tests/test_render_edges_host.py uses them to show that its boundary families
+tell the definition from its neighbours."""
 import numpy as np
 
 FRAC = 256                       # 8 fractional bits
 GUARD = float(1 << 24)           # |ix|, |iy| above: unusable
 EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
+VARIANTS = ('exclusive_edges',       # coverage w > 0 for w >= 0
+            'half_even_vertex',      # the vertex snap rounds an exact half to even, not up
+            'half_even_depth',       # the depth quantisation likewise
+            'du_gt_1',               # du > 1 for du >= 1
+            'du_lt_65535',           # du < 65535 for du <= 65535
+            'z_gt_near',             # Z > z_near for Z >= z_near
+            'guard_lt',              # |ix|, |iy| < 2^24 for <= 2^24
+            'owner_lt')              # rank -> instance: the last j with base[j] < rank for <= rank
+
+
+def _variant(variant):
+    v = frozenset([variant] if isinstance(variant, str) else variant or ())
+    assert v <= frozenset(VARIANTS), v
+    return v
 
 
 def pose_matrix(rotvec, trans):
@@ -25,8 +43,9 @@ def pose_matrix(rotvec, trans):
     return T
 
 
-def project(vertices, pose, intr, z_near):
+def project(vertices, pose, intr, z_near, variant=None):
     """The vertex stage: (ix, iy int64, iz float64, usable bool) of one instance's vertices."""
+    variant = _variant(variant)
     v = np.asarray(vertices, np.float32).reshape(-1, 3).astype(np.float64)
     A = np.asarray(pose, np.float64).reshape(-1)
     fx, fy, cx, cy = (float(np.float32(k)) for k in np.asarray(intr).reshape(-1)[:4])
@@ -39,7 +58,13 @@ def project(vertices, pose, intr, z_near):
         sy = (fy * Y) / Z + cy
         fxv = np.floor(sx * 256.0 + 0.5)
         fyv = np.floor(sy * 256.0 + 0.5)
+        if 'half_even_vertex' in variant:
+            fxv, fyv = np.rint(sx * 256.0), np.rint(sy * 256.0)
         ok = np.isfinite(Z) & (Z >= float(z_near)) & (np.abs(fxv) <= GUARD) & (np.abs(fyv) <= GUARD)      # a NaN fails
+        if 'z_gt_near' in variant:
+            ok &= Z > float(z_near)
+        if 'guard_lt' in variant:
+            ok &= (np.abs(fxv) < GUARD) & (np.abs(fyv) < GUARD)
         ix = np.where(ok, fxv, 0.0).astype(np.int64)
         iy = np.where(ok, fyv, 0.0).astype(np.int64)
         iz = np.where(ok, 1.0 / np.where(ok, Z, 1.0), 0.0)
@@ -50,9 +75,10 @@ def _ceil_div(a, b):
     return -((-a) // b)
 
 
-def draw_triangle(zbuf, rank, xs, ys, zs, factor):
+def draw_triangle(zbuf, rank, xs, ys, zs, factor, variant=None):
     """One usable triangle with a non-zero area into zbuf [H,W] uint64.  xs, ys: Python ints; zs: 1 / Z.  Returns the
     number of samples in its clamped box."""
+    variant = _variant(variant)
     H, W = zbuf.shape
     (ax, bx, cx), (ay, by, cy), (iza, izb, izc) = xs, ys, zs
     area2 = (bx - ax) * (cy - ay) - (by - ay) * (cx - ax)
@@ -70,12 +96,20 @@ def draw_triangle(zbuf, rank, xs, ys, zs, factor):
     wc = (bx - ax) * (py - ay) - (by - ay) * (px - ax)
     assert np.all(wa + wb + wc == area2) and max(np.abs(wa).max(), np.abs(wb).max(), np.abs(wc).max()) < (1 << 52)
     covered = (wa >= 0) & (wb >= 0) & (wc >= 0)
+    if 'exclusive_edges' in variant:
+        covered = (wa > 0) & (wb > 0) & (wc > 0)
     if covered.any():
         with np.errstate(all='ignore'):
             q = (wa.astype(np.float64) * iza +wb.astype(np.float64) * izb) + wc.astype(np.float64) * izc
             z = float(area2) / q
             du = np.floor(z * factor + 0.5)
+            if 'half_even_depth' in variant:
+                du = np.rint(z * factor)
             keep = covered & (du >= 1.0) & (du <= 65535.0)
+            if 'du_gt_1' in variant:
+                keep &= du > 1.0
+            if 'du_lt_65535' in variant:
+                keep &= du < 65535.0
         key = (np.where(keep, du, 0.0).astype(np.uint64) << np.uint64(32)) | np.uint64(rank)
         cell = zbuf[v0:v1 + 1, u0:u1 + 1]
         cell[...] = np.where(keep, np.minimum(cell, key), cell)
@@ -94,11 +128,12 @@ def instance_bases(meshes, frames):
     return offs, mesh, lab, poses, vb, tb
 
 
-def render(meshes, frames, intrinsics, height, width, z_near=0.05):
+def render(meshes, frames, intrinsics, height, width, z_near=0.05, variant=None):
     """meshes: [(vertices [V,3] float32, triangles [T,3] int, ...)]; frames: per frame a list of (mesh index, label,
     pose 4x4 float64); intrinsics [F,5] float32 (fx, fy, cx, cy, factor_depth).  -> dict(depth [F,H,W] uint16, label
     uint8, tri int32, dropped, degenerate [J] int32, box [R] int64: the samples in the clamped box of every draw rank,
     -1 for a rank that was not drawn)."""
+    variant = _variant(variant)
     intr = np.asarray(intrinsics, np.float32).reshape(len(frames), 5)
     offs, mesh, lab, poses, vb, tb = instance_bases(meshes, frames)
     F, J = len(frames), len(mesh)
@@ -110,7 +145,7 @@ def render(meshes, frames, intrinsics, height, width, z_near=0.05):
         factor = float(intr[f, 4])
         for j in range(offs[f], offs[f + 1]):
             v, t = meshes[mesh[j]][0], np.asarray(meshes[mesh[j]][1], np.int64).reshape(-1, 3)
-            ix, iy, iz, ok = project(v, poses[j], intr[f], z_near)
+            ix, iy, iz, ok = project(v, poses[j], intr[f], z_near, variant)
             for k, ids in enumerate(t):
                 if np.any(ids < 0) or np.any(ids >= len(ix)) or not np.all(ok[ids]):
                     dropped[j] += 1
@@ -119,12 +154,14 @@ def render(meshes, frames, intrinsics, height, width, z_near=0.05):
                 if (xs[1] - xs[0]) * (ys[2] - ys[0]) - (ys[1] - ys[0]) * (xs[2] - xs[0]) == 0:
                     degenerate[j] += 1
                     continue
-                box[tb[j] + k] = draw_triangle(zbuf[f], int(tb[j]) + k, xs, ys, iz[ids], factor)
+                box[tb[j] + k] = draw_triangle(zbuf[f], int(tb[j]) + k, xs, ys, iz[ids], factor, variant)
     hit = zbuf != EMPTY
     rank = np.where(hit, zbuf & np.uint64(0xFFFFFFFF), 0).astype(np.int64)
     owner = np.searchsorted(tb, rank, side='right') - 1           # the last j with base[j] <= rank
+    if 'owner_lt' in variant:
+        owner = np.searchsorted(tb, rank, side='left') - 1
     depth = np.where(hit, zbuf >> np.uint64(32), 0).astype(np.uint16)
-    label = np.where(hit, lab[np.clip(owner, 0, max(J - 1, 0))] if J else 0, 0).astype(np.uint8)
+    label = np.where(hit & (owner >= 0), lab[np.clip(owner, 0, max(J - 1, 0))] if J else 0, 0).astype(np.uint8)
     tri = np.where(hit, rank, -1).astype(np.int32)
     return dict(depth=depth, label=label, tri=tri, dropped=dropped, degenerate=degenerate, box=box)
 
