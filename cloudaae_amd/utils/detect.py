@@ -1,9 +1,9 @@
 """Detections: which of the components found in an unlabelled depth frame (utils/depth_components.py) is which object,
 under which pose, or nothing -- decided without the ground truth, by verification score across the (component, class)
 pairs of a frame.  Every hypothesis is rendered alone into a window around its component (utils/render.py), counted
-against the observed depth inside that window (cloudaae_depth_fit_counts_window) and the pairs of a frame are assigned
-greedily by their exact fractions (cloudaae_detect_assign; csrc/detect.hip).  The definition is in DESIGN.md
-("Detections").
+against the observed depth inside that window (cloudaae_depth_fit_counts_window; csrc/depth_fit.hip) and the pairs of a
+frame are assigned greedily by their exact fractions (cloudaae_detect_assign; csrc/detect.hip).  The definition is in
+DESIGN.md ("Detections").
 
     d = detect_objects(depth, intrinsics, meshes, ppf_models)          # Detections; d.table['det_class'] [F,K], ...
     r = score_candidates(segments, poses, valid, meshes, mesh_of_class, intrinsics, depth)     # given hypotheses
@@ -16,7 +16,7 @@ import torch
 from .. import _lib
 from .._lib import ptr, require, stream
 from .bop_score import _depth
-from .pose_verify import COUNTERS, MODE_SEGMENT, MODE_SILHOUETTE, tau_units
+from .pose_verify import COUNTERS, MODE_SEGMENT, MODE_SILHOUETTE, _fit_inputs, _int32, tau_units
 
 # choices, not measurements
 MARGIN = 0.5              # of the component's box, added on either side
@@ -61,12 +61,6 @@ def windows(comp_box, n_components, H, W, margin=MARGIN):
     return np.where(live[:, :, None], origin, 0).astype(np.int32), wh, ww
 
 
-def _int32(t, name, shape, dev):
-    require(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and tuple(t.shape) == shape and t.device == dev,
-            "%s must be an int32 %s tensor on the inputs' device" % (name, list(shape)))
-    return t.contiguous()
-
-
 def fit_counts_window(depth_test, label, frame_of, want, origin, depth_hyp, tau):
     """cloudaae_depth_fit_counts_window.  depth_test [F,H,W] and depth_hyp [B,P,wh,ww]: int16 tensors holding the uint16
     bits, or uint16; label [F,H,W] uint8 or None; frame_of [B] int32 (an entry outside [0, F) gives zero counts); want [B]
@@ -76,27 +70,15 @@ def fit_counts_window(depth_test, label, frame_of, want, origin, depth_hyp, tau)
     dt, dh = _depth(depth_test, "depth_test", 3), _depth(depth_hyp, "depth_hyp", 4)
     F, H, W = (int(x) for x in dt.shape)
     B, P, wh, ww = (int(x) for x in dh.shape)
-    dev = dt.device
     require(B >= 1 and P >= 1 and wh >= 1 and ww >= 1, "depth_hyp must be [B, P, wh, ww], none of them 0")
-    require(dh.device == dev, "all inputs must be on one device")
-    if label is not None:
-        require(isinstance(label, torch.Tensor) and label.dtype == torch.uint8 and tuple(label.shape) == (F, H, W) and
-                label.device == dev, "label must be a uint8 [F, H, W] tensor on the inputs' device, or None")
-        label = label.contiguous()
-        want = _int32(want, "want", (B,), dev)
-    else:
-        want = None
-    frame_of, tau = _int32(frame_of, "frame_of", (B,), dev), _int32(tau, "tau", (B,), dev)
-    origin = _int32(origin, "origin", (B, 2), dev)
-    counts = _lib.empty((B, P, len(COUNTERS)), dtype=torch.int32, device=dev)
-    seg_total = _lib.empty((B,), dtype=torch.int32, device=dev)
-    abs_sum = _lib.empty((B, P), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
+    label, frame_of, want, tau, out = _fit_inputs(dt, dh, label, frame_of, want, tau)
+    origin = _int32(origin, "origin", (B, 2), dt.device)
+    with torch.cuda.device(dt.device):
         _lib.check(_lib.lib().cloudaae_depth_fit_counts_window(F, H, W, ptr(dt), ptr(label), B, P, ptr(frame_of), ptr(want),
-                                                               ptr(origin), wh, ww, ptr(dh), ptr(tau), ptr(counts),
-                                                               ptr(seg_total), ptr(abs_sum), stream()),
+                                                               ptr(origin), wh, ww, ptr(dh), ptr(tau), ptr(out["counts"]),
+                                                               ptr(out["seg_total"]), ptr(out["abs_sum"]), stream()),
                    "cloudaae_depth_fit_counts_window")
-    return {"counts": counts, "seg_total": seg_total, "abs_sum": abs_sum}
+    return out
 
 
 def assign(counts, seg_total, valid, pose, n_components, mode=MODE_SEGMENT, min_score=MIN_SCORE, max_per_class=MAX_PER_CLASS):

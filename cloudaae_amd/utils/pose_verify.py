@@ -1,7 +1,7 @@
 """Pose verification: judge candidate poses of an object against the depth the camera saw, without the ground truth,
 and keep the best.  A small set of hypotheses is composed from a base pose (cloudaae_pose_compose), every hypothesis is
 rendered alone with its frame's intrinsics (utils/render.py), each rendering is compared per pixel with the observed
-depth and with the object's segment (cloudaae_depth_fit_counts), and the winner is chosen exactly
+depth and with the object's segment (cloudaae_depth_fit_counts; csrc/depth_fit.hip), and the winner is chosen exactly
 (cloudaae_select_pose; csrc/pose_verify.hip).  The definition is in DESIGN.md ("Pose verification").
 
     table = HypothesisTable.from_models(models)                      # identity + the three principal half turns per class
@@ -142,10 +142,30 @@ def compose(base, class_id, table, p=None):
     return out
 
 
-def _int32(t, name, B, dev):
-    require(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and tuple(t.shape) == (B,) and t.device == dev,
-            "%s must be an int32 [B] tensor on the inputs' device" % name)
+def _int32(t, name, shape, dev):
+    require(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and tuple(t.shape) == shape and t.device == dev,
+            "%s must be an int32 %s tensor on the inputs' device" % (name, list(shape)))
     return t.contiguous()
+
+
+def _fit_inputs(dt, dh, label, frame_of, want, tau):
+    """What fit_counts and detect.fit_counts_window share: the checks of label [F,H,W], want (None without a label),
+    frame_of and tau [B] against the test frames dt [F,H,W] and the hypothesis images dh [B,P,..], and the outputs.
+    -> (label, frame_of, want, tau, out), out the dict of counts [B,P,6] int32, seg_total [B] int32, abs_sum [B,P] int64."""
+    B, P, dev = int(dh.shape[0]), int(dh.shape[1]), dt.device
+    require(dh.device == dev, "all inputs must be on one device")
+    if label is not None:
+        require(isinstance(label, torch.Tensor) and label.dtype == torch.uint8 and label.shape == dt.shape and
+                label.device == dev, "label must be a uint8 [F, H, W] tensor on the inputs' device, or None")
+        label = label.contiguous()
+        want = _int32(want, "want", (B,), dev)
+    else:
+        want = None
+    frame_of, tau = _int32(frame_of, "frame_of", (B,), dev), _int32(tau, "tau", (B,), dev)
+    out = {"counts": _lib.empty((B, P, len(COUNTERS)), dtype=torch.int32, device=dev),
+           "seg_total": _lib.empty((B,), dtype=torch.int32, device=dev),
+           "abs_sum": _lib.empty((B, P), dtype=torch.int64, device=dev)}
+    return label, frame_of, want, tau, out
 
 
 def fit_counts(depth_test, label, frame_of, want, depth_hyp, tau, check_frames=True):
@@ -157,28 +177,16 @@ def fit_counts(depth_test, label, frame_of, want, depth_hyp, tau, check_frames=T
     dt, dh = _depth(depth_test, "depth_test", 3), _depth(depth_hyp, "depth_hyp", 4)
     F, H, W = (int(x) for x in dt.shape)
     B, P = int(dh.shape[0]), int(dh.shape[1])
-    dev = dt.device
     require(tuple(dh.shape) == (B, P, H, W) and B >= 1 and P >= 1, "depth_hyp must be [B, P, H, W] with the test frames' H and W")
-    require(dh.device == dev, "all inputs must be on one device")
-    if label is not None:
-        require(isinstance(label, torch.Tensor) and label.dtype == torch.uint8 and tuple(label.shape) == (F, H, W) and
-                label.device == dev, "label must be a uint8 [F, H, W] tensor on the inputs' device, or None")
-        label = label.contiguous()
-        want = _int32(want, "want", B, dev)
-    else:
-        want = None
-    frame_of, tau = _int32(frame_of, "frame_of", B, dev), _int32(tau, "tau", B, dev)
+    label, frame_of, want, tau, out = _fit_inputs(dt, dh, label, frame_of, want, tau)
     if check_frames:
         fo = frame_of.cpu().numpy()
         require(fo.min() >= 0 and fo.max() < F, "a frame_of entry outside [0, F)")
-    counts = _lib.empty((B, P, len(COUNTERS)), dtype=torch.int32, device=dev)
-    seg_total = _lib.empty((B,), dtype=torch.int32, device=dev)
-    abs_sum = _lib.empty((B, P), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dt.device):
         _lib.check(_lib.lib().cloudaae_depth_fit_counts(F, H, W, ptr(dt), ptr(label), B, P, ptr(frame_of), ptr(want), ptr(dh),
-                                                        ptr(tau), ptr(counts), ptr(seg_total), ptr(abs_sum), stream()),
-                   "cloudaae_depth_fit_counts")
-    return {"counts": counts, "seg_total": seg_total, "abs_sum": abs_sum}
+                                                        ptr(tau), ptr(out["counts"]), ptr(out["seg_total"]),
+                                                        ptr(out["abs_sum"]), stream()), "cloudaae_depth_fit_counts")
+    return out
 
 
 def select(counts, seg_total, valid, pose, mode=MODE_SEGMENT):
@@ -189,7 +197,7 @@ def select(counts, seg_total, valid, pose, mode=MODE_SEGMENT):
             counts.shape[2] == len(COUNTERS) and counts.shape[0] >= 1 and counts.shape[1] >= 1,
             "counts must be an int32 [B, P, 6] tensor")
     B, P, dev = int(counts.shape[0]), int(counts.shape[1]), counts.device
-    seg_total = _int32(seg_total, "seg_total", B, dev)
+    seg_total = _int32(seg_total, "seg_total", (B,), dev)
     if valid is None:
         valid = torch.ones((B, P), dtype=torch.int32, device=dev)
     require(isinstance(valid, torch.Tensor) and valid.dtype == torch.int32 and tuple(valid.shape) == (B, P) and
