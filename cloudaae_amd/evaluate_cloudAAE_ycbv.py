@@ -434,7 +434,8 @@ def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, devic
     (target_cls + 1): what evaluate_batch(verify=...) takes the object's segment from.
     labels="components" (the default "record" uses the records' label images): the label images are found from the depth
     alone by utils.depth_components.segment_depth(depth, intrinsics, **components) -- components: its parameters, seed and
-    first_frame among them -- on every frame of the call, so that frame i of `frames` draws its plane hypotheses from
+    first_frame among them, and creases=True or dict(step, smooth, angle) to cut touching objects apart at their concave
+    creases first -- on every frame of the call, so that frame i of `frames` draws its plane hypotheses from
     first_frame + i whether or not its neighbours hold the class.  The record's label serves for association only: the component with the largest IoU against
     its target_cls + 1 pixels (match_components) takes their place, as value target_cls + 1 of an otherwise empty label
     image, and everything after is unchanged.  Frames without such a component are dropped.  The element gains
@@ -675,6 +676,12 @@ def main(argv=None):
     p.add_argument("--components_jump", type=float, default=dc_util.JUMP, help="depth step that cuts a component, metres")
     p.add_argument("--components_min_pixels", type=int, default=dc_util.MIN_PIXELS)
     p.add_argument("--components_max", type=int, default=dc_util.MAX_COMPONENTS, help="components kept per frame")
+    p.add_argument("--components_creases", action="store_true",
+                   help="cut the foreground along its concave creases before labelling, so that touching objects separate")
+    p.add_argument("--components_crease_step", type=int, default=dc_util.STEP, help="pixels to either end of a chord, 1 .. 8")
+    p.add_argument("--components_crease_smooth", type=int, default=dc_util.SMOOTH, help="half side of the smoothing box, 0 .. 7")
+    p.add_argument("--components_crease_angle", type=float, default=dc_util.ANGLE,
+                   help="degrees a fold must deviate from flat to count as a crease")
     p.add_argument("--choose", default="record", choices=("record", "detect"),
                    help="with --labels components: record associates the class with a component by the record's label; "
                         "detect decides it without the label (utils/detect.py; needs --meshes DIR)")
@@ -803,6 +810,9 @@ def main(argv=None):
                                         max_height=args.components_max_height,
                                         min_plane_percent=args.components_min_plane_percent, jump=args.components_jump,
                                         min_pixels=args.components_min_pixels, max_components=args.components_max))
+            if args.components_creases:
+                comp["components"]["creases"] = dict(step=args.components_crease_step, smooth=args.components_crease_smooth,
+                                                     angle=args.components_crease_angle)
             if detector is not None:
                 comp.update(choose="detect", detector=detector)
         el = element_from_frames(chunk, args.target_cls, args.num_point, models, seed=args.seed + n_launch,

@@ -284,7 +284,8 @@ def detect_objects(depth, intrinsics, meshes, ppf_models, classes=None, segments
                    tau=0.01, mode=MODE_SEGMENT, margin=MARGIN, min_score=MIN_SCORE, max_per_class=MAX_PER_CLASS,
                    samples_per_launch=SAMPLES_PER_LAUNCH):
     """depth [F,H,W] uint16 (numpy, or a tensor holding the bits as int16) and intrinsics [F,5] float32 -> Detections.
-    segment_depth(depth, intrinsics, seed=seed, first_frame=first_frame, **components) unless segments is given; the
+    segment_depth(depth, intrinsics, seed=seed, first_frame=first_frame, **components) unless segments is given
+    (components=dict(creases=True) cuts touching objects apart first, so that each gets a class of its own); the
     clouds of its components (component_clouds: num_point points; a component with fewer inliers is no candidate, valid 0,
     and counted in skipped); their normals (ppf.scene_normals(normal_radius)); ppf.propose_poses of ppf_models (a PPFModels)
     with every cloud repeated for each of classes (default: every class of ppf_models), top proposals each; with icp (the

@@ -56,7 +56,7 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * cloudaae_transform_hausdorff with its workspace query; cloudaae_nearest_equivalent_pose; cloudaae_pose_compose,
  * cloudaae_depth_fit_counts and cloudaae_select_pose; cloudaae_fc_plan (host-only path query); cloudaae_depth_plane,
  * cloudaae_depth_foreground, cloudaae_depth_components and cloudaae_component_labels, the last two with a workspace query;
- * cloudaae_depth_fit_counts_window and cloudaae_detect_assign. */
+ * cloudaae_depth_fit_counts_window and cloudaae_detect_assign; cloudaae_depth_creases with its workspace query. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -1328,6 +1328,30 @@ int cloudaae_depth_foreground(int f, int h, int w, const uint16_t *depth, const 
 long long cloudaae_depth_components_workspace_bytes(int f, int h, int w);
 int cloudaae_depth_components(int f, int h, int w, const uint16_t *depth, const uint8_t *fg, const int *jump_units, int *root,
                               int *status, void *workspace, long long workspace_bytes, cloudaae_stream_t stream);
+
+/* Concave creases of the foreground ("Creases", has the definition): the cut that separates touching objects
+ * before cloudaae_depth_components labels them.  fg [f,h,w] uint8 as cloudaae_depth_foreground writes it (any non-zero
+ * value counts); step s, smooth r, cos2 = cos(angle)^2.
+ * Stage 1, integers.  For a foreground pixel c of a frame with jump_units >= 0 the members of its box are the pixels q of the
+ * frame with |u_q - u_c| <= r, |v_q - v_c| <= r, fg != 0 and |d_q - d_c| <= jump_units (depths widened to int; c itself is
+ * one): S their depths' sum, n their number, smooth_map = (S << 8) | n; elsewhere smooth_map = 0.  The workspace's first
+ * f h w words ARE smooth_map [f,h,w] uint32, written by every call and readable afterwards.
+ * The smoothed point of a pixel, double, un-fused: z = (double)S / ((double)n * (double)factor_depth), x = (((double)u -
+ * (double)cx) * z) / (double)fx, y likewise.
+ * Stage 2.  Direction bit b = 0 .. 3 is (du, dv) = (1,0), (0,1), (1,1), (1,-1); A = (u - s du, v - s dv), B = (u + s du,
+ * v + s dv).  The direction is tested at a foreground pixel C when A and B are pixels of the frame, both foreground, and
+ * |d_A - d_C| <= s jump_units and |d_B - d_C| <= s jump_units on the raw depths (64-bit product).  With e1 = P_A - P_C,
+ * e2 = P_B - P_C on smoothed points: g = (e1x e2x + e1y e2y) + e1z e2z; m = e1 + e2; cc = (mx Cx + my Cy) + mz Cz; q1, q2 the
+ * squared lengths formed like g.  The bit is set when the direction is tested, cc < 0 and (g >= 0 or g g < cos2 (q1 q2)).
+ * Outputs, all written: crease, tested [f,h,w] uint8 (the four bits), fg_cut [f,h,w] uint8 = 1 where fg != 0 and crease = 0,
+ * n_crease [f] int = the pixels with crease != 0.  One memset and two launches, both 32 x 32 tiles staged in LDS with a halo
+ * of r and of s pixels; one integer atomic per workgroup; no workgroup waits for another.  Limits: 1 <= step <= 8;
+ * 0 <= smooth <= 7 (so that S < 2^24 and n < 2^8); cos2 a number in [0, 1]. */
+long long cloudaae_depth_creases_workspace_bytes(int f, int h, int w);
+int cloudaae_depth_creases(int f, int h, int w, const uint16_t *depth, const uint8_t *fg, const float *intrinsics,
+                           const int *jump_units, int step, int smooth, double cos2, uint8_t *crease, uint8_t *tested,
+                           uint8_t *fg_cut, int *n_crease, void *workspace, long long workspace_bytes,
+                           cloudaae_stream_t stream);
 
 /* The component table of root [f,h,w] int as cloudaae_depth_components writes it (an entry outside [0, h w) counts as
  * background).  The candidates of a frame are the components of at least min_pixels pixels, ordered by (size descending,
