@@ -160,6 +160,7 @@ _SIGNATURES = {
     "cloudaae_depth_fit_counts_window": [_I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
     "cloudaae_detect_assign": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                _P, _P, _P, _P, _P],
+    "cloudaae_depth_align_step": [_I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P, _P, _P, _L, _P],
 }
 
 
@@ -386,7 +387,8 @@ def lib():
                        ("cloudaae_cloud_diameter_workspace_bytes", [_I, _I]),
                        ("cloudaae_depth_components_workspace_bytes", [_I, _I, _I]),
                        ("cloudaae_component_labels_workspace_bytes", [_I, _I, _I]),
-                       ("cloudaae_depth_creases_workspace_bytes", [_I, _I, _I])):
+                       ("cloudaae_depth_creases_workspace_bytes", [_I, _I, _I]),
+                       ("cloudaae_depth_align_step_workspace_bytes", [_I, _I, _I])):
             getattr(cdll, q).argtypes = sig
             getattr(cdll, q).restype = ctypes.c_longlong
         cdll.cloudaae_gemm_f32_splits.argtypes = [_I, _I, _I]

@@ -1,0 +1,367 @@
+"""Tracking: known objects followed from frame to frame of a depth sequence by dense depth-image alignment.  The object is
+rendered at its predicted pose into a window around it (utils/render.py), every rendered pixel is paired with the depth the
+camera saw at the same pixel, one point-to-plane step is solved from the pairs (cloudaae_depth_align_step;
+csrc/depth_align.hip), that is repeated, and the result is judged by the windowed counts of "Detections"
+(cloudaae_depth_fit_counts_window, the silhouette rule).  Neither a segmentation nor a pose proposal is needed once a pose
+of the frame before is known.  The definition is in DESIGN.md ("Tracking").
+
+    t = track_objects(depth, intrinsics, meshes, detections_of_frame_0)           # Tracks; t.poses [F,J,4,4], t.lost [F,J]
+    a = align_poses(depth, intrinsics, meshes, mesh_of, frame_of, poses)          # poses refined against their frames
+
+    python -m cloudaae_amd.utils.track --files REC_pcnn.tfrecord --meshes DIR [--mesh_scale S] [--motion velocity]
+"""
+import argparse
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .._lib import ptr, require, stream
+from . import detect
+from .bop_score import _depth
+from .pose_verify import _int32, tau_units
+
+# choices, not measurements
+ITERATIONS = 4
+GATE = 0.03               # |d - t| of a pair, metres
+JUMP = 0.005              # a neighbour farther than this from its pixel takes no part in the slope, metres
+COS_MIN = 0.8             # |n_hyp . n_obs| of a pair
+MARGIN = 0.5              # of the projected bounding box, added on either side
+MIN_SCORE = (1, 2)        # a track below this fraction is lost
+TAU = 0.01                # of the lost-track score, metres
+Z_NEAR = 0.05
+
+SUMS = 28
+
+
+# ---- the binding ------------------------------------------------------------------------------------------------------------
+def align_step(depth_test, frame_of, origin, depth_hyp, intr_win, gate, jump, cos_min, pose_in):
+    """cloudaae_depth_align_step.  depth_test [F,H,W] and depth_hyp [B,wh,ww]: int16 tensors holding the uint16 bits, or
+    uint16; frame_of [B] int32 (an entry outside [0, F) gives status 4 and reads nothing); origin [B,2] int32 = (u0, v0), any
+    values; intr_win [B,5] float32: the windows' rows (fx, fy, cx - u0, cy - v0, factor_depth); gate, jump [B] int32 in depth
+    units; cos_min a number (<= 0: no normal test); pose_in [B,4,4] float64.  All on one device.  -> dict of n_pairs [B]
+    int32, sums [B,28], x [B,6] float64, status [B] int32 and pose_out [B,4,4] float64 on the device.  No read-back."""
+    dt, dh = _depth(depth_test, "depth_test", 3), _depth(depth_hyp, "depth_hyp", 3)
+    F, H, W = (int(v) for v in dt.shape)
+    B, wh, ww = (int(v) for v in dh.shape)
+    dev = dt.device
+    require(B >= 1 and wh >= 1 and ww >= 1, "depth_hyp must be [B, wh, ww], none of them 0")
+    require(dh.device == dev, "all inputs must be on one device")
+    frame_of, gate, jump = (_int32(t, n, (B,), dev) for t, n in ((frame_of, "frame_of"), (gate, "gate"), (jump, "jump")))
+    origin = _int32(origin, "origin", (B, 2), dev)
+    require(isinstance(intr_win, torch.Tensor) and intr_win.dtype == torch.float32 and tuple(intr_win.shape) == (B, 5) and
+            intr_win.device == dev, "intr_win must be a float32 [B, 5] tensor on the inputs' device")
+    require(isinstance(pose_in, torch.Tensor) and pose_in.dtype == torch.float64 and pose_in.numel() == 16 * B and
+            pose_in.device == dev, "pose_in must be a float64 [B, 4, 4] tensor on the inputs' device")
+    cos_min = float(cos_min)
+    require(cos_min == cos_min, "cos_min must be a number")
+    L = _lib.lib()
+    nbytes = int(L.cloudaae_depth_align_step_workspace_bytes(B, wh, ww))
+    require(nbytes > 0, "outside the limits: wh ww <= 2^24, B wh ww <= 2^28")
+    out = dict(n_pairs=_lib.empty((B,), dtype=torch.int32, device=dev), sums=_lib.empty((B, SUMS), dtype=torch.float64, device=dev),
+               x=_lib.empty((B, 6), dtype=torch.float64, device=dev), status=_lib.empty((B,), dtype=torch.int32, device=dev),
+               pose_out=_lib.empty((B, 4, 4), dtype=torch.float64, device=dev))
+    ws = _lib.empty((nbytes,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.cloudaae_depth_align_step(F, H, W, ptr(dt), B, ptr(frame_of), ptr(origin), wh, ww, ptr(dh),
+                                               ptr(intr_win.contiguous()), ptr(gate), ptr(jump), cos_min,
+                                               ptr(pose_in.contiguous()), ptr(out["n_pairs"]), ptr(out["sums"]), ptr(out["x"]),
+                                               ptr(out["status"]), ptr(out["pose_out"]), ptr(ws), nbytes, stream()),
+                   "cloudaae_depth_align_step")
+    return out
+
+
+# ---- windows of posed bounding boxes (host) ---------------------------------------------------------------------------------
+def mesh_aabb(packed):
+    """[S,2,3] float64 (host): the smallest and the largest vertex coordinates of every mesh of a PackedMeshes; read back
+    once per PackedMeshes and kept on it."""
+    if getattr(packed, "aabb", None) is None:
+        v = packed.vertices.cpu().numpy().astype(np.float64)
+        at = np.concatenate([[0], np.cumsum(np.asarray(packed.num_vertices, np.int64))])
+        packed.aabb = np.array([[v[a:b].min(axis=0), v[a:b].max(axis=0)] if b > a else np.zeros((2, 3))
+                                for a, b in zip(at[:-1], at[1:])])
+    return packed.aabb
+
+
+def pose_windows(poses, aabb, intrinsics, H, W, margin=MARGIN, z_near=Z_NEAR):
+    """One window size for the call and an origin per track, on the host.  poses [J,4,4] float64 (model -> camera), aabb
+    [J,2,3]: the low and the high corner of each track's mesh, intrinsics [J,5] (or [5]): each track's frame.  The eight
+    corners (x, y, z), each the low or the high coordinate, go through X = ((A0 x + A1 y) + A2 z) + A3 (Y, Z alike), u = (fx
+    X) / Z + cx, v = (fy Y) / Z + cy in float64; a track with a corner that has Z < z_near, or a value that is not finite,
+    gets no window; its box is (floor min u, floor min v, ceil max u, ceil max v) clipped to the frame, and an empty box is no
+    window either.  Then detect.windows over the tracks that have one.  -> (origin [J,2] int32, zeros without a window; wh;
+    ww; ok [J] bool)."""
+    poses = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+    J = len(poses)
+    aabb = np.asarray(aabb, np.float64)
+    require(aabb.shape == (J, 2, 3), "aabb must be [J, 2, 3], one box per pose")
+    intr = np.broadcast_to(np.asarray(intrinsics, np.float32), (J, 5)).astype(np.float64)
+    pick = np.array([[cx, cy, cz] for cx in (0, 1) for cy in (0, 1) for cz in (0, 1)])
+    c = aabb[:, pick, np.arange(3)[None, :]]                                       # [J,8,3]
+    x, y, z = c[..., 0], c[..., 1], c[..., 2]
+    A = poses[:, None]
+    with np.errstate(all="ignore"):
+        X = ((A[..., 0, 0] * x + A[..., 0, 1] * y) + A[..., 0, 2] * z) + A[..., 0, 3]
+        Y = ((A[..., 1, 0] * x + A[..., 1, 1] * y) + A[..., 1, 2] * z) + A[..., 1, 3]
+        Z = ((A[..., 2, 0] * x + A[..., 2, 1] * y) + A[..., 2, 2] * z) + A[..., 2, 3]
+        u = (intr[:, None, 0] * X) / Z + intr[:, None, 2]
+        v = (intr[:, None, 1] * Y) / Z + intr[:, None, 3]
+        ok = np.all((Z >= float(z_near)) & np.isfinite(Z) & np.isfinite(u) & np.isfinite(v), axis=1)
+        u, v = np.where(ok[:, None], u, 0.0), np.where(ok[:, None], v, 0.0)
+        box = np.stack([np.maximum(np.clip(np.floor(u.min(axis=1)), -1, W), 0), np.maximum(np.clip(np.floor(v.min(axis=1)), -1, H), 0),
+                        np.minimum(np.clip(np.ceil(u.max(axis=1)), -1, W), W - 1),
+                        np.minimum(np.clip(np.ceil(v.max(axis=1)), -1, H), H - 1)], axis=1).astype(np.int64)
+    ok &= (box[:, 0] <= box[:, 2]) & (box[:, 1] <= box[:, 3])
+    live = np.nonzero(ok)[0]
+    packed = np.zeros((1, max(len(live), 1), 4), np.int64)
+    packed[0, :len(live)] = box[live]
+    o, wh, ww = detect.windows(packed, [len(live)], H, W, margin)
+    origin = np.zeros((J, 2), np.int32)
+    origin[live] = o[0, :len(live)]
+    return origin, wh, ww, ok
+
+
+def _host(x, dtype):
+    return np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype)
+
+
+# ---- the loop ---------------------------------------------------------------------------------------------------------------
+def align_poses(depth, intrinsics, meshes, mesh_of, frame_of, poses, iterations=ITERATIONS, gate=GATE, jump=JUMP, cos_min=COS_MIN,
+                margin=MARGIN, window=None, return_trajectory=False):
+    """J poses refined against their frames.  depth [F,H,W] uint16 (numpy, or a device tensor holding the bits as int16),
+    intrinsics [F,5] float32 (host), meshes a PackedMeshes (or what mesh_models.pack_meshes takes), mesh_of and frame_of [J]
+    host integers, poses [J,4,4] float64 (host; a device tensor costs one read-back for the windows unless window is
+    given).  The window (pose_windows of the given poses; window=(origin [J,2], wh, ww) overrides it) is fixed over the
+    iterations; gate and jump in metres become depth units by tau_units of the track's frame.  Per iteration: one
+    render.render_instances call for all tracks (H = wh, W = ww, the windows' rows) and one align_step; nothing is read back
+    inside the loop.  A track without a window is given frame_of -1: status 4, its pose unchanged.  -> dict of poses
+    [J,4,4] float64, n_pairs and status [J] int32 of the last step (device), origin [J,2], wh, ww, ok [J] (host); with
+    return_trajectory also trajectory [iterations + 1,J,4,4]: the pose before every step and after the last, and
+    n_pairs_steps, status_steps [iterations,J] (device)."""
+    from . import depth_components as dc_util
+    from . import mesh_models, render
+    p = mesh_models.pack_meshes(meshes)
+    dev = p.device
+    dt = _depth(dc_util._depth_tensor(depth, dev) if isinstance(depth, np.ndarray) else depth, "depth", 3)
+    F, H, W = (int(v) for v in dt.shape)
+    mesh = np.asarray(mesh_of, np.int64).reshape(-1)
+    J = len(mesh)
+    fo = np.asarray(frame_of, np.int64).reshape(-1)
+    require(J >= 1 and len(fo) == J, "mesh_of and frame_of must be [J], J >= 1")
+    require(mesh.min() >= 0 and mesh.max() < len(p.num_triangles), "mesh_of must lie inside the meshes")
+    require(fo.min() >= 0 and fo.max() < F, "frame_of must lie in [0, F)")
+    intr_host = _host(intrinsics, np.float32)
+    require(intr_host.shape == (F, 5), "intrinsics must be [F, 5], one row per frame")
+    require(int(iterations) >= 0, "iterations must be >= 0")
+    pose_dev = (poses if isinstance(poses, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(poses, np.float64))).to(dev)
+    require(pose_dev.dtype == torch.float64 and pose_dev.numel() == 16 * J, "poses must be float64 [J, 4, 4]")
+    pose_dev = pose_dev.reshape(J, 4, 4).contiguous()
+    if window is None:
+        origin, wh, ww, ok = pose_windows(_host(poses, np.float64), mesh_aabb(p)[mesh], intr_host[fo], H, W, margin)
+    else:
+        origin, wh, ww = np.ascontiguousarray(window[0], np.int32), int(window[1]), int(window[2])
+        require(origin.shape == (J, 2) and wh >= 1 and ww >= 1, "window must be (origin [J, 2], wh, ww)")
+        ok = np.ones(J, bool)
+    rows_host = intr_host[fo].copy()
+    rows_host[:, 2] = intr_host[fo, 2] - origin[:, 0].astype(np.float32)
+    rows_host[:, 3] = intr_host[fo, 3] - origin[:, 1].astype(np.float32)
+    factor = intr_host[fo, 4].astype(np.float64)
+    gu, ju = tau_units(np.broadcast_to(np.asarray(gate, np.float64), (J,)), factor), \
+        tau_units(np.broadcast_to(np.asarray(jump, np.float64), (J,)), factor)
+    ints = torch.from_numpy(np.stack([np.where(ok, fo, -1), gu, ju, origin[:, 0], origin[:, 1]], axis=1).astype(np.int32)).to(dev)
+    frame_dev, gate_dev, jump_dev, org = (ints[:, 0].contiguous(), ints[:, 1].contiguous(), ints[:, 2].contiguous(),
+                                          ints[:, 3:].contiguous())
+    rows = torch.from_numpy(np.ascontiguousarray(rows_host)).to(dev)
+    offs, ones = np.arange(J + 1), np.ones(J, np.int64)
+    traj, n_steps, s_steps = [pose_dev], [], []
+    n_pairs = torch.zeros((J,), dtype=torch.int32, device=dev)
+    status = torch.zeros((J,), dtype=torch.int32, device=dev)
+    for _ in range(int(iterations)):
+        d = render.render_instances(p, rows, offs, mesh, ones, traj[-1].view(J, 16), wh, ww)[0]
+        r = align_step(dt, frame_dev, org, d, rows, gate_dev, jump_dev, cos_min, traj[-1])
+        n_pairs, status = r["n_pairs"], r["status"]
+        if return_trajectory:
+            traj.append(r["pose_out"])
+            n_steps.append(n_pairs)
+            s_steps.append(status)
+        else:
+            traj = [r["pose_out"]]
+    out = dict(poses=traj[-1], n_pairs=n_pairs, status=status, origin=origin, wh=wh, ww=ww, ok=ok,
+               device=dict(depth=dt, frame_of=frame_dev, origin=org, rows=rows, packed=p))
+    if return_trajectory:
+        out["trajectory"] = torch.stack(traj)
+        out["n_pairs_steps"] = torch.stack(n_steps) if n_steps else torch.zeros((0, J), dtype=torch.int32, device=dev)
+        out["status_steps"] = torch.stack(s_steps) if s_steps else torch.zeros((0, J), dtype=torch.int32, device=dev)
+    return out
+
+
+# ---- tracking ---------------------------------------------------------------------------------------------------------------
+class Tracks(object):
+    """The result of track_objects.  mesh_of [J]; poses [F,J,4,4] float64: the pose of every track in every frame (a lost
+    track keeps its last good pose); num, den [F,J]: the silhouette rule's fraction of the frame's attempt; n_pairs, status
+    [F,J]: of the attempt's last step; lost [F,J] bool; first_frame: the global index of frame 0.  All numpy."""
+
+
+def _compose(U, T):
+    """U T with the products of cloudaae_pose_compose (host float64)."""
+    N = np.eye(4)
+    for i in range(3):
+        for c in range(3):
+            N[i, c] = (U[i, 0] * T[0, c] + U[i, 1] * T[1, c]) + U[i, 2] * T[2, c]
+        N[i, 3] = ((U[i, 0] * T[0, 3] + U[i, 1] * T[1, 3]) + U[i, 2] * T[2, 3]) + U[i, 3]
+    return N
+
+
+def _invert(T):
+    """(R^T, -R^T t) of a rigid T."""
+    N = np.eye(4)
+    for i in range(3):
+        N[i, :3] = T[:3, i]
+        N[i, 3] = -((T[0, i] * T[0, 3] + T[1, i] * T[1, 3]) + T[2, i] * T[2, 3])
+    return N
+
+
+def predict(last, before, motion):
+    """The start of a frame: the last pose, or with 'velocity' (T_{f-1} T_{f-2}^-1) T_{f-1} once two poses exist."""
+    if motion == "velocity" and before is not None:
+        return _compose(_compose(last, _invert(before)), last)
+    return last.copy()
+
+
+def _initial_tracks(init):
+    if isinstance(init, detect.Detections):
+        cls, pose = np.asarray(init.table["det_class"])[0], np.asarray(init.table["det_pose"], np.float64)[0]
+        keep = np.nonzero(cls >= 0)[0]
+        return cls[keep].astype(np.int64), pose[keep].copy()
+    require(isinstance(init, (tuple, list)) and len(init) == 2, "init must be a Detections or (mesh_of [J], poses [J, 4, 4])")
+    mesh = np.asarray(init[0], np.int64).reshape(-1)
+    return mesh, _host(init[1], np.float64).reshape(len(mesh), 4, 4).copy()
+
+
+def track_objects(depth, intrinsics, meshes, init, motion="constant", min_score=MIN_SCORE, tau=TAU, on_lost=None, first_frame=0,
+                  **align):
+    """Known objects followed through depth [F,H,W] uint16 (numpy, or a device tensor holding the bits as int16) with
+    intrinsics [F,5] (or [5]) float32.  init: a Detections of frame 0 -- its assigned components become the tracks, mesh =
+    the class id, as detect_objects assumes by default -- or (mesh_of [J], poses [J,4,4]).  Frames are taken in order, frame
+    0 included.  The start of a frame is the track's last pose, or with motion='velocity' (T_{f-1} T_{f-2}^-1) T_{f-1} once
+    two poses exist.  Each frame runs align_poses(**align) from the starts, renders the result into the same window and counts
+    it with detect.fit_counts_window without a label (tau in metres); the score is the silhouette rule's (num, den) =
+    (consistent, consistent + in_front + behind), 0 / 1 for den = 0.  A track is lost in frame f when num min_den < min_num
+    den, in integers, or when it has no window; it keeps its last good pose and is tried again from it, at rest, in the next
+    frame.  on_lost(f, track_indices), called when tracks are lost, may return new poses [len(track_indices),4,4] (or None):
+    they are aligned and scored in the same frame -- the hook to hang detect_objects(depth[f:f+1], ..., first_frame =
+    first_frame + f) on.  One read-back per frame (one more when on_lost gives poses).  -> Tracks."""
+    from . import depth_components as dc_util
+    from . import mesh_models, render
+    require(motion in ("constant", "velocity"), "motion must be 'constant' or 'velocity'")
+    num_min, den_min = int(min_score[0]), int(min_score[1])
+    require(0 <= num_min <= den_min and den_min >= 1, "min_score must be (num, den) with 0 <= num <= den, den >= 1")
+    p = mesh_models.pack_meshes(meshes)
+    dev = p.device
+    dt = _depth(dc_util._depth_tensor(depth, dev) if isinstance(depth, np.ndarray) else depth, "depth", 3)
+    F = int(dt.shape[0])
+    intr = np.ascontiguousarray(np.broadcast_to(_host(intrinsics, np.float32).reshape(-1, 5), (F, 5)))
+    mesh_of, last = _initial_tracks(init)
+    J = len(mesh_of)
+    require(J >= 1, "no track to follow")
+    tau_frame = tau_units(np.broadcast_to(np.asarray(tau, np.float64), (F,)), intr[:, 4].astype(np.float64))
+    before = [None] * J
+    t = Tracks()
+    t.mesh_of, t.first_frame = mesh_of, int(first_frame)
+    t.poses = np.zeros((F, J, 4, 4))
+    t.num, t.den = np.zeros((F, J), np.int64), np.ones((F, J), np.int64)
+    t.n_pairs, t.status, t.lost = np.zeros((F, J), np.int32), np.zeros((F, J), np.int32), np.zeros((F, J), bool)
+
+    def attempt(f, idx, start):
+        """align, render, count and read back -> (pose [n,4,4], num, den, n_pairs, status, lost [n])."""
+        n = len(idx)
+        a = align_poses(dt, intr, p, mesh_of[idx], np.full(n, f), start, **align)
+        dv = a["device"]
+        d = render.render_instances(p, dv["rows"], np.arange(n + 1), mesh_of[idx], np.ones(n, np.int64), a["poses"].view(n, 16),
+                                    a["wh"], a["ww"])[0]
+        tau_dev = torch.full((n,), int(tau_frame[f]), dtype=torch.int32, device=dev)
+        c = detect.fit_counts_window(dt, None, dv["frame_of"], None, dv["origin"], d.view(n, 1, a["wh"], a["ww"]), tau_dev)
+        # the one read-back: the poses as their bits, the counters, the last step's pairs and status
+        host = torch.cat([a["poses"].contiguous().view(torch.int32).reshape(-1), c["counts"].reshape(-1), a["n_pairs"],
+                          a["status"]]).cpu().numpy()
+        pose = host[:32 * n].copy().view(np.float64).reshape(n, 4, 4)
+        counts = host[32 * n:38 * n].reshape(n, 6).astype(np.int64)
+        num, den = counts[:, 1].copy(), counts[:, 1] + counts[:, 2] + counts[:, 3]
+        num, den = np.where(den > 0, num, 0), np.where(den > 0, den, 1)
+        lost = ~a["ok"] | (num * den_min < num_min * den)
+        return pose, num, den, host[38 * n:39 * n], host[39 * n:40 * n], lost
+
+    for f in range(F):
+        idx = np.arange(J)
+        start = np.array([predict(last[j], before[j], motion) for j in idx])
+        pose, num, den, n_pairs, status, lost = attempt(f, idx, start)
+        if lost.any() and on_lost is not None:
+            again = np.nonzero(lost)[0]
+            given = on_lost(f, again.copy())
+            if given is not None:
+                given = _host(given, np.float64).reshape(len(again), 4, 4)
+                pose[again], num[again], den[again], n_pairs[again], status[again], lost[again] = attempt(f, again, given)
+        for j in idx:
+            if lost[j]:
+                before[j] = None
+            else:
+                before[j], last[j] = last[j].copy(), pose[j]
+        t.poses[f], t.num[f], t.den[f], t.n_pairs[f], t.status[f], t.lost[f] = last, num, den, n_pairs, status, lost
+    return t
+
+
+# ---- command line -----------------------------------------------------------------------------------------------------------
+def quat2mat(q):
+    """The rotation matrix of a quaternion (w, x, y, z), normalised first, float64."""
+    w, x, y, z = np.asarray(q, np.float64) / np.sqrt((np.asarray(q, np.float64) ** 2).sum())
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def pose_errors(T, truth):
+    """(rotation error in degrees, translation error in metres) of T against truth."""
+    c = (np.trace(T[:3, :3] @ truth[:3, :3].T) - 1.0) / 2.0
+    return float(np.degrees(np.arccos(min(max(c, -1.0), 1.0)))), float(np.sqrt(((T[:3, 3] - truth[:3, 3]) ** 2).sum()))
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description="track the objects of a <seq>_pcnn.tfrecord from its first frame's poses")
+    parser.add_argument("--files", required=True, help="one <seq>_pcnn.tfrecord; its frames are taken in file order")
+    parser.add_argument("--meshes", required=True, help="directory of *.ply files; class i is the i-th in sorted order")
+    parser.add_argument("--mesh_scale", type=float, default=1.0, help="factor on the coordinates (0.001: millimetres to metres)")
+    parser.add_argument("--motion", choices=["constant", "velocity"], default="constant")
+    parser.add_argument("--iterations", type=int, default=ITERATIONS)
+    parser.add_argument("--gpu", type=int, default=0)
+    args = parser.parse_args(argv)
+    from .. import tfrecord_io
+    from . import mesh_models
+    torch.cuda.set_device(args.gpu)
+    frames = list(tfrecord_io.read_frames(args.files))
+    require(len(frames) >= 1, "no frame in %s" % args.files)
+    packed = mesh_models.pack_meshes(mesh_models.mesh_files(args.meshes), args.mesh_scale)
+    classes = [int(c) for c in np.nonzero(frames[0]["class_one_hot"])[0] if c < len(packed.num_triangles)]
+    require(len(classes) >= 1, "the first frame names no class that has a mesh")
+
+    def truth(fr):
+        out = np.tile(np.eye(4), (len(classes), 1, 1))
+        for i, c in enumerate(classes):
+            out[i, :3, :3], out[i, :3, 3] = quat2mat(fr["quaternions"][c]), fr["translations"][c]
+        return out
+
+    depth = np.stack([fr["depth"] for fr in frames])
+    intr = np.array([[fr[k] for k in ("fx", "fy", "cx", "cy", "factor_depth")] for fr in frames], np.float32)
+    t = track_objects(depth, intr, packed, (classes, truth(frames[0])), motion=args.motion, iterations=args.iterations)
+    for f, fr in enumerate(frames):
+        gt = truth(fr)
+        for i, c in enumerate(classes):
+            here = bool(fr["class_one_hot"][c])
+            rot, trans = pose_errors(t.poses[f, i], gt[i]) if here else (float("nan"), float("nan"))
+            print("frame %d class %d score %d/%d lost %d rot_err_deg %.4f trans_err_m %.6f"
+                  % (int(fr["frame_id"]), c, t.num[f, i], t.den[f, i], int(t.lost[f, i]), rot, trans))
+    print("%d frames, %d tracks, %d lost track-frames" % (len(frames), len(classes), int(t.lost.sum())))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -56,7 +56,8 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * cloudaae_transform_hausdorff with its workspace query; cloudaae_nearest_equivalent_pose; cloudaae_pose_compose,
  * cloudaae_depth_fit_counts and cloudaae_select_pose; cloudaae_fc_plan (host-only path query); cloudaae_depth_plane,
  * cloudaae_depth_foreground, cloudaae_depth_components and cloudaae_component_labels, the last two with a workspace query;
- * cloudaae_depth_fit_counts_window and cloudaae_detect_assign; cloudaae_depth_creases with its workspace query. */
+ * cloudaae_depth_fit_counts_window and cloudaae_detect_assign; cloudaae_depth_creases with its workspace query;
+ * cloudaae_depth_align_step with its workspace query. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -1409,6 +1410,44 @@ int cloudaae_detect_assign(int f, int k, int c, int p, const int *counts, const 
                            int *pair_hyp, int *pair_num, int *pair_den, double *pair_score, int *det_class, int *det_hyp,
                            int *det_num, int *det_den, double *det_score, int *det_rank, double *det_pose, int *alt_class,
                            int *alt_num, int *alt_den, int *n_det, cloudaae_stream_t stream);
+
+/* ---- tracking: depth-image alignment of known objects across frames ("Tracking", has the definition) ---- */
+
+/* One Gauss-Newton step of dense point-to-plane alignment for b tracks.  depth_test [f,h,w] uint16; frame_of [b] int; origin
+ * [b,2] int = (u0, v0) and one wh, ww per call: window pixel (x, y) is frame pixel (u0 + x, v0 + y), as for
+ * cloudaae_depth_fit_counts_window; depth_hyp [b,wh,ww] uint16: the object alone, rendered at pose_in into its window;
+ * intr_win [b,5] float: the window's row (fx, fy, cx - u0, cy - v0, factor_depth); gate, jump [b] int in depth units; cos_min;
+ * pose_in [b,16] double.  All device memory.  Arithmetic: double on exactly widened integers and floats, un-fused, in the
+ * written order.
+ * P(x, y, z) = (((x - cxw) dm) / fx, ((y - cyw) dm) / fy, dm), dm = z / factor_depth, (x, y) WINDOW coordinates in either
+ * image.  The normal of an image at a pixel s of depth z_s: a neighbour is valid when it lies inside the image (the window
+ * for depth_hyp, the frame for depth_test), has depth != 0 and |z_nb - z_s| <= jump; along x: gx = P(x+1) - P(x-1) when both
+ * are valid, P(x+1) - P(s) or P(s) - P(x-1) with the one valid neighbour, else the axis has no slope; gy likewise; n = gx x gy,
+ * each component (p q) - (r s); nn = (nx nx + ny ny) + nz nz; the pixel is flat when an axis has no slope or nn is 0 or not
+ * finite; the unit normal is each component divided by sqrt(nn), its sign as it comes.
+ * A window pixel with d = depth_hyp and t = the frame pixel's depth (0 outside the frame) is a pair when d != 0, t != 0,
+ * |d - t| <= gate, the hypothesis normal n at (x, y) is not flat and, when cos_min > 0, the observed normal m at the frame
+ * pixel is not flat and |(nx mx + ny my) + nz mz| >= cos_min; cos_min <= 0 reads no observed neighbour.
+ * Per pair p = P(x, y, d), q = P(x, y, t), e = p - q, r = (ex nx + ey ny) + ez nz, a = p x n = (py nz - pz ny, pz nx - px nz,
+ * px ny - py nx), J = (a, n); A = sum J J^T, b = sum J r; A x = -b by LDL^T without pivoting and U from x exactly as in
+ * cloudaae_icp_point_to_plane.
+ * Outputs, all written: n_pairs [b] int; sums [b,28] double = sum r r, A's upper triangle by rows, b; x [b,6] double (zeros
+ * unless status is 0); status [b] int: 0 updated, 1 fewer than six pairs, 2 a pivot that is not a finite number > 0, 3 a
+ * solution that is not finite, 4 frame_of outside [0, f) (nothing of that sample is read; n_pairs and sums are 0);
+ * pose_out [b,16] double = U pose_in with the products formed as cloudaae_pose_compose forms them and the last row 0 0 0 1;
+ * for every status but 0 pose_in bit for bit.
+ * Two launches: a workgroup of 256 lanes adds a run of 2048 window pixels, eight consecutive per lane in pixel order, the wave
+ * by a butterfly, the four waves in order, and stores 28 partial sums and a count to the workspace; one wave per sample adds
+ * the runs in run order and solves.  No floating-point atomics and no workgroup waits for another: the same bits run to run
+ * and whatever else is in the batch.  workspace: cloudaae_depth_align_step_workspace_bytes(b, wh, ww) bytes, 8-byte aligned
+ * (0: outside the limits).  Limits: f, h, w, b, wh, ww >= 1; h * w <= 2^24; wh * ww <= 2^24; b * wh * ww <= 2^28; outside
+ * them, with a null pointer, a workspace too small or cos_min not a number the call returns an error and launches nothing. */
+long long cloudaae_depth_align_step_workspace_bytes(int b, int wh, int ww);
+int cloudaae_depth_align_step(int f, int h, int w, const uint16_t *depth_test, int b, const int *frame_of, const int *origin,
+                              int wh, int ww, const uint16_t *depth_hyp, const float *intr_win, const int *gate,
+                              const int *jump, double cos_min, const double *pose_in, int *n_pairs, double *sums, double *x,
+                              int *status, double *pose_out, void *workspace, long long workspace_bytes,
+                              cloudaae_stream_t stream);
 
 #ifdef __cplusplus
 }
