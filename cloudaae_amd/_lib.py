@@ -161,6 +161,9 @@ _SIGNATURES = {
     "cloudaae_detect_assign": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                _P, _P, _P, _P, _P],
     "cloudaae_depth_align_step": [_I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P, _P, _P, _L, _P],
+    "cloudaae_depth_edge_nearest": [_I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _I, _P, _P],
+    "cloudaae_depth_contour_sums": [_I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P],
+    "cloudaae_depth_align_solve": [_I, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P],
 }
 
 
@@ -388,7 +391,8 @@ def lib():
                        ("cloudaae_depth_components_workspace_bytes", [_I, _I, _I]),
                        ("cloudaae_component_labels_workspace_bytes", [_I, _I, _I]),
                        ("cloudaae_depth_creases_workspace_bytes", [_I, _I, _I]),
-                       ("cloudaae_depth_align_step_workspace_bytes", [_I, _I, _I])):
+                       ("cloudaae_depth_align_step_workspace_bytes", [_I, _I, _I]),
+                       ("cloudaae_depth_contour_sums_workspace_bytes", [_I, _I, _I])):
             getattr(cdll, q).argtypes = sig
             getattr(cdll, q).restype = ctypes.c_longlong
         cdll.cloudaae_gemm_f32_splits.argtypes = [_I, _I, _I]

@@ -8,7 +8,11 @@ of the frame before is known.  The definition is in DESIGN.md ("Tracking").
     t = track_objects(depth, intrinsics, meshes, detections_of_frame_0)           # Tracks; t.poses [F,J,4,4], t.lost [F,J]
     a = align_poses(depth, intrinsics, meshes, mesh_of, frame_of, poses)          # poses refined against their frames
 
-    python -m cloudaae_amd.utils.track --files REC_pcnn.tfrecord --meshes DIR [--mesh_scale S] [--motion velocity]
+    python -m cloudaae_amd.utils.track --files REC_pcnn.tfrecord --meshes DIR [--mesh_scale S] [--motion velocity] [--contour]
+
+contour=True on either call adds the occluding-contour term of DESIGN.md, "Contours" (csrc/depth_contour.hip): the rendered
+object's occluding edges are pulled onto the nearest occluding edges of the frame, which holds flat and thin objects that
+point-to-plane alone lets slide.  It is off by default.
 """
 import argparse
 
@@ -30,6 +34,11 @@ MARGIN = 0.5              # of the projected bounding box, added on either side
 MIN_SCORE = (1, 2)        # a track below this fraction is lost
 TAU = 0.01                # of the lost-track score, metres
 Z_NEAR = 0.05
+# the contour term: choices too, backed by the CPU prototype's table ("Contours")
+CONTOUR_RADIUS = 16       # pixels within which an observed occluding edge is looked for
+CONTOUR_STEP = 0.02       # a neighbour farther behind than this (or empty) makes a pixel an occluding edge, metres
+CONTOUR_WEIGHT = 1.0 / 16.0   # of the contour sums against the plane sums
+MAX_RADIUS = 32
 
 SUMS = 28
 
@@ -68,6 +77,98 @@ def align_step(depth_test, frame_of, origin, depth_hyp, intr_win, gate, jump, co
                                                ptr(pose_in.contiguous()), ptr(out["n_pairs"]), ptr(out["sums"]), ptr(out["x"]),
                                                ptr(out["status"]), ptr(out["pose_out"]), ptr(ws), nbytes, stream()),
                    "cloudaae_depth_align_step")
+    return out
+
+
+# ---- the contour term ("Contours"; csrc/depth_contour.hip) -------------------------------------------------------
+def _contour_settings(contour):
+    """contour=None | True | dict(radius, step, weight) -> None or the full dict."""
+    if contour is None or contour is False:
+        return None
+    c = dict(radius=CONTOUR_RADIUS, step=CONTOUR_STEP, weight=CONTOUR_WEIGHT)
+    if contour is not True:
+        require(isinstance(contour, dict) and set(contour) <= set(c), "contour must be None, True or a dict of radius, step, weight")
+        c.update(contour)
+    c["radius"], c["weight"] = int(c["radius"]), float(c["weight"])
+    require(1 <= c["radius"] <= MAX_RADIUS, "contour radius must lie in [1, %d]" % MAX_RADIUS)
+    require(c["weight"] == c["weight"], "contour weight must be a number")
+    return c
+
+
+def edge_nearest(depth_test, frame_of, origin, wh, ww, step, radius):
+    """cloudaae_depth_edge_nearest.  depth_test [F,H,W], frame_of [B], origin [B,2] as for align_step; one wh, ww per call;
+    step [B] int32 in depth units (device); 1 <= radius <= 32.  -> nearest [B,wh,ww] int32 on the device: -1, or (mask_obs <<
+    16) | ((j + radius) << 8) | (i + radius) of the nearest observed occluding edge (u0 + x + i, v0 + y + j) of window pixel
+    (x, y).  A sample whose frame_of lies outside [0, F) is all -1.  No read-back."""
+    dt = _depth(depth_test, "depth_test", 3)
+    F, H, W = (int(v) for v in dt.shape)
+    dev = dt.device
+    require(isinstance(frame_of, torch.Tensor) and frame_of.dim() == 1 and frame_of.numel() >= 1, "frame_of must be [B], B >= 1")
+    B, wh, ww, radius = int(frame_of.numel()), int(wh), int(ww), int(radius)
+    require(wh >= 1 and ww >= 1, "wh and ww must be >= 1")
+    require(1 <= radius <= MAX_RADIUS, "radius must lie in [1, %d]" % MAX_RADIUS)
+    frame_of, step = _int32(frame_of, "frame_of", (B,), dev), _int32(step, "step", (B,), dev)
+    origin = _int32(origin, "origin", (B, 2), dev)
+    nearest = _lib.empty((B, wh, ww), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().cloudaae_depth_edge_nearest(F, H, W, ptr(dt), B, ptr(frame_of), ptr(origin), wh, ww, ptr(step), radius,
+                                                          ptr(nearest), stream()), "cloudaae_depth_edge_nearest")
+    return nearest
+
+
+def contour_sums(depth_test, frame_of, origin, depth_hyp, intr_win, gate, step, radius, nearest):
+    """cloudaae_depth_contour_sums.  The arguments of align_step without jump and cos_min, plus step [B] int32 in depth units,
+    the radius and the nearest [B,wh,ww] int32 of edge_nearest for the same frames, origins, step and radius.  -> dict of
+    n_rows [B] int32 (two per contour pair) and sums [B,28] float64 in align_step's layout, on the device.  No read-back."""
+    dt, dh = _depth(depth_test, "depth_test", 3), _depth(depth_hyp, "depth_hyp", 3)
+    F, H, W = (int(v) for v in dt.shape)
+    B, wh, ww = (int(v) for v in dh.shape)
+    dev, radius = dt.device, int(radius)
+    require(B >= 1 and wh >= 1 and ww >= 1, "depth_hyp must be [B, wh, ww], none of them 0")
+    require(dh.device == dev, "all inputs must be on one device")
+    require(1 <= radius <= MAX_RADIUS, "radius must lie in [1, %d]" % MAX_RADIUS)
+    frame_of, gate, step = (_int32(t, n, (B,), dev) for t, n in ((frame_of, "frame_of"), (gate, "gate"), (step, "step")))
+    origin, nearest = _int32(origin, "origin", (B, 2), dev), _int32(nearest, "nearest", (B, wh, ww), dev)
+    require(isinstance(intr_win, torch.Tensor) and intr_win.dtype == torch.float32 and tuple(intr_win.shape) == (B, 5) and
+            intr_win.device == dev, "intr_win must be a float32 [B, 5] tensor on the inputs' device")
+    L = _lib.lib()
+    nbytes = int(L.cloudaae_depth_contour_sums_workspace_bytes(B, wh, ww))
+    require(nbytes > 0, "outside the limits: wh ww <= 2^24, B wh ww <= 2^28")
+    out = dict(n_rows=_lib.empty((B,), dtype=torch.int32, device=dev), sums=_lib.empty((B, SUMS), dtype=torch.float64, device=dev))
+    ws = _lib.empty((nbytes,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.cloudaae_depth_contour_sums(F, H, W, ptr(dt), B, ptr(frame_of), ptr(origin), wh, ww, ptr(dh),
+                                                 ptr(intr_win.contiguous()), ptr(gate), ptr(step), radius, ptr(nearest),
+                                                 ptr(out["n_rows"]), ptr(out["sums"]), ptr(ws), nbytes, stream()),
+                   "cloudaae_depth_contour_sums")
+    return out
+
+
+def solve_sums(plane, contour, weight, pose_in):
+    """cloudaae_depth_align_solve.  plane: what align_step returned (its sums, n_pairs and status are read); contour: what
+    contour_sums returned; weight a number; pose_in [B,4,4] float64, the pose both were formed at.  total = plane sums + weight
+    x contour sums; status 4 where the plane step's is 4, else 1 where n_pairs + n_rows < 6, else align_step's solve on the
+    totals.  -> dict of x [B,6], status [B] int32, pose_out [B,4,4] float64 on the device (pose_in bit for bit unless status
+    is 0).  No read-back."""
+    ps, dev = plane["sums"], plane["sums"].device
+    B = int(ps.shape[0])
+    require(ps.dtype == torch.float64 and tuple(ps.shape) == (B, SUMS) and B >= 1, "plane sums must be float64 [B, 28]")
+    cs = contour["sums"]
+    require(isinstance(cs, torch.Tensor) and cs.dtype == torch.float64 and tuple(cs.shape) == (B, SUMS) and cs.device == dev,
+            "contour sums must be float64 [B, 28] on the plane sums' device")
+    n_pairs, st, n_rows = (_int32(t, n, (B,), dev) for t, n in ((plane["n_pairs"], "n_pairs"), (plane["status"], "status"),
+                                                               (contour["n_rows"], "n_rows")))
+    require(isinstance(pose_in, torch.Tensor) and pose_in.dtype == torch.float64 and pose_in.numel() == 16 * B and
+            pose_in.device == dev, "pose_in must be a float64 [B, 4, 4] tensor on the inputs' device")
+    weight = float(weight)
+    require(weight == weight, "weight must be a number")
+    out = dict(x=_lib.empty((B, 6), dtype=torch.float64, device=dev), status=_lib.empty((B,), dtype=torch.int32, device=dev),
+               pose_out=_lib.empty((B, 4, 4), dtype=torch.float64, device=dev))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().cloudaae_depth_align_solve(B, ptr(ps.contiguous()), ptr(n_pairs), ptr(st), ptr(cs.contiguous()),
+                                                         ptr(n_rows), weight, ptr(pose_in.contiguous()), ptr(out["x"]),
+                                                         ptr(out["status"]), ptr(out["pose_out"]), stream()),
+                   "cloudaae_depth_align_solve")
     return out
 
 
@@ -127,14 +228,18 @@ def _host(x, dtype):
 
 # ---- the loop ---------------------------------------------------------------------------------------------------------------
 def align_poses(depth, intrinsics, meshes, mesh_of, frame_of, poses, iterations=ITERATIONS, gate=GATE, jump=JUMP, cos_min=COS_MIN,
-                margin=MARGIN, window=None, return_trajectory=False):
+                margin=MARGIN, window=None, return_trajectory=False, contour=None):
     """J poses refined against their frames.  depth [F,H,W] uint16 (numpy, or a device tensor holding the bits as int16),
     intrinsics [F,5] float32 (host), meshes a PackedMeshes (or what mesh_models.pack_meshes takes), mesh_of and frame_of [J]
     host integers, poses [J,4,4] float64 (host; a device tensor costs one read-back for the windows unless window is
     given).  The window (pose_windows of the given poses; window=(origin [J,2], wh, ww) overrides it) is fixed over the
     iterations; gate and jump in metres become depth units by tau_units of the track's frame.  Per iteration: one
     render.render_instances call for all tracks (H = wh, W = ww, the windows' rows) and one align_step; nothing is read back
-    inside the loop.  A track without a window is given frame_of -1: status 4, its pose unchanged.  -> dict of poses
+    inside the loop.  contour=True or dict(radius=16, step=0.02, weight=1/16) adds the occluding-contour term (DESIGN.md,
+    "Contours"): one edge_nearest call before the loop (step in metres becomes units like the gates) and per iteration, after
+    the align_step, one contour_sums and one solve_sums, whose pose and status replace the step's; n_pairs stays the plane
+    pairs'.  With contour=None nothing of that is called.  A track without a window is given frame_of -1: status 4, its
+    pose unchanged.  -> dict of poses
     [J,4,4] float64, n_pairs and status [J] int32 of the last step (device), origin [J,2], wh, ww, ok [J] (host); with
     return_trajectory also trajectory [iterations + 1,J,4,4]: the pose before every step and after the last, and
     n_pairs_steps, status_steps [iterations,J] (device)."""
@@ -168,10 +273,17 @@ def align_poses(depth, intrinsics, meshes, mesh_of, frame_of, poses, iterations=
     factor = intr_host[fo, 4].astype(np.float64)
     gu, ju = tau_units(np.broadcast_to(np.asarray(gate, np.float64), (J,)), factor), \
         tau_units(np.broadcast_to(np.asarray(jump, np.float64), (J,)), factor)
-    ints = torch.from_numpy(np.stack([np.where(ok, fo, -1), gu, ju, origin[:, 0], origin[:, 1]], axis=1).astype(np.int32)).to(dev)
+    con = _contour_settings(contour)
+    cols = [np.where(ok, fo, -1), gu, ju, origin[:, 0], origin[:, 1]]
+    if con:                                                # the edge step rides along in the one upload of the integers
+        cols.append(tau_units(np.broadcast_to(np.asarray(con["step"], np.float64), (J,)), factor))
+    ints = torch.from_numpy(np.stack(cols, axis=1).astype(np.int32)).to(dev)
     frame_dev, gate_dev, jump_dev, org = (ints[:, 0].contiguous(), ints[:, 1].contiguous(), ints[:, 2].contiguous(),
-                                          ints[:, 3:].contiguous())
+                                          ints[:, 3:5].contiguous())
     rows = torch.from_numpy(np.ascontiguousarray(rows_host)).to(dev)
+    if con and int(iterations) > 0:
+        step_dev = ints[:, 5].contiguous()
+        near = edge_nearest(dt, frame_dev, org, wh, ww, step_dev, con["radius"])
     offs, ones = np.arange(J + 1), np.ones(J, np.int64)
     traj, n_steps, s_steps = [pose_dev], [], []
     n_pairs = torch.zeros((J,), dtype=torch.int32, device=dev)
@@ -179,7 +291,11 @@ def align_poses(depth, intrinsics, meshes, mesh_of, frame_of, poses, iterations=
     for _ in range(int(iterations)):
         d = render.render_instances(p, rows, offs, mesh, ones, traj[-1].view(J, 16), wh, ww)[0]
         r = align_step(dt, frame_dev, org, d, rows, gate_dev, jump_dev, cos_min, traj[-1])
-        n_pairs, status = r["n_pairs"], r["status"]
+        n_pairs = r["n_pairs"]
+        if con:
+            c = contour_sums(dt, frame_dev, org, d, rows, gate_dev, step_dev, con["radius"], near)
+            r = solve_sums(r, c, con["weight"], traj[-1])
+        status = r["status"]
         if return_trajectory:
             traj.append(r["pose_out"])
             n_steps.append(n_pairs)
@@ -239,7 +355,7 @@ def _initial_tracks(init):
 
 
 def track_objects(depth, intrinsics, meshes, init, motion="constant", min_score=MIN_SCORE, tau=TAU, on_lost=None, first_frame=0,
-                  **align):
+                  contour=None, **align):
     """Known objects followed through depth [F,H,W] uint16 (numpy, or a device tensor holding the bits as int16) with
     intrinsics [F,5] (or [5]) float32.  init: a Detections of frame 0 -- its assigned components become the tracks, mesh =
     the class id, as detect_objects assumes by default -- or (mesh_of [J], poses [J,4,4]).  Frames are taken in order, frame
@@ -250,7 +366,8 @@ def track_objects(depth, intrinsics, meshes, init, motion="constant", min_score=
     den, in integers, or when it has no window; it keeps its last good pose and is tried again from it, at rest, in the next
     frame.  on_lost(f, track_indices), called when tracks are lost, may return new poses [len(track_indices),4,4] (or None):
     they are aligned and scored in the same frame -- the hook to hang detect_objects(depth[f:f+1], ..., first_frame =
-    first_frame + f) on.  One read-back per frame (one more when on_lost gives poses).  -> Tracks."""
+    first_frame + f) on.  contour (None, True or dict(radius, step, weight)) is align_poses': the occluding-contour term that
+    holds flat and thin objects, off by default.  One read-back per frame (one more when on_lost gives poses).  -> Tracks."""
     from . import depth_components as dc_util
     from . import mesh_models, render
     require(motion in ("constant", "velocity"), "motion must be 'constant' or 'velocity'")
@@ -275,7 +392,7 @@ def track_objects(depth, intrinsics, meshes, init, motion="constant", min_score=
     def attempt(f, idx, start):
         """align, render, count and read back -> (pose [n,4,4], num, den, n_pairs, status, lost [n])."""
         n = len(idx)
-        a = align_poses(dt, intr, p, mesh_of[idx], np.full(n, f), start, **align)
+        a = align_poses(dt, intr, p, mesh_of[idx], np.full(n, f), start, contour=contour, **align)
         dv = a["device"]
         d = render.render_instances(p, dv["rows"], np.arange(n + 1), mesh_of[idx], np.ones(n, np.int64), a["poses"].view(n, 16),
                                     a["wh"], a["ww"])[0]
@@ -332,6 +449,7 @@ def main(argv=None):
     parser.add_argument("--mesh_scale", type=float, default=1.0, help="factor on the coordinates (0.001: millimetres to metres)")
     parser.add_argument("--motion", choices=["constant", "velocity"], default="constant")
     parser.add_argument("--iterations", type=int, default=ITERATIONS)
+    parser.add_argument("--contour", action="store_true", help="add the occluding-contour term at its defaults (flat and thin objects)")
     parser.add_argument("--gpu", type=int, default=0)
     args = parser.parse_args(argv)
     from .. import tfrecord_io
@@ -351,7 +469,8 @@ def main(argv=None):
 
     depth = np.stack([fr["depth"] for fr in frames])
     intr = np.array([[fr[k] for k in ("fx", "fy", "cx", "cy", "factor_depth")] for fr in frames], np.float32)
-    t = track_objects(depth, intr, packed, (classes, truth(frames[0])), motion=args.motion, iterations=args.iterations)
+    t = track_objects(depth, intr, packed, (classes, truth(frames[0])), motion=args.motion, iterations=args.iterations,
+                      contour=True if args.contour else None)
     for f, fr in enumerate(frames):
         gt = truth(fr)
         for i, c in enumerate(classes):

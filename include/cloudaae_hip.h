@@ -57,7 +57,8 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * cloudaae_depth_fit_counts and cloudaae_select_pose; cloudaae_fc_plan (host-only path query); cloudaae_depth_plane,
  * cloudaae_depth_foreground, cloudaae_depth_components and cloudaae_component_labels, the last two with a workspace query;
  * cloudaae_depth_fit_counts_window and cloudaae_detect_assign; cloudaae_depth_creases with its workspace query;
- * cloudaae_depth_align_step with its workspace query. */
+ * cloudaae_depth_align_step with its workspace query; cloudaae_depth_edge_nearest, cloudaae_depth_contour_sums with its
+ * workspace query and cloudaae_depth_align_solve. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -1448,6 +1449,45 @@ int cloudaae_depth_align_step(int f, int h, int w, const uint16_t *depth_test, i
                               const int *jump, double cos_min, const double *pose_in, int *n_pairs, double *sums, double *x,
                               int *status, double *pose_out, void *workspace, long long workspace_bytes,
                               cloudaae_stream_t stream);
+
+/* ---- tracking: the occluding-contour term ("Contours", has the definition) ---- */
+
+/* Shared by the three entries below: the arguments named as in cloudaae_depth_align_step mean the same; its limits and error
+ * rules apply (an error launches nothing), and in addition 1 <= radius <= 32.  The edge mask of a pixel with depth z != 0 of
+ * an image: bits 0..3 stand for the neighbours (x-1, y), (x+1, y), (x, y-1), (x, y+1); a bit is set when that neighbour lies
+ * inside the image (the frame for depth_test, the window for depth_hyp) and has z_nb = 0 or z_nb - z > step, in integers; a
+ * pixel with z = 0 has mask 0; an edge pixel is one with mask != 0. */
+
+/* The nearest observed edge of every window pixel.  step [b] int, device memory, in depth units.  nearest [b,wh,ww] int: -1,
+ * or (mask_obs << 16) | ((j + radius) << 8) | (i + radius) for the offset (i, j) smallest in (i i + j j, j, i) among those
+ * with i i + j j <= radius^2 whose frame pixel (u0 + x + i, v0 + y + j) lies inside the frame and is an edge pixel of
+ * depth_test.  A sample whose frame_of lies outside [0, f) reads nothing and is all -1.  One launch, one workgroup per tile of
+ * 32 x 32 window pixels. */
+int cloudaae_depth_edge_nearest(int f, int h, int w, const uint16_t *depth_test, int b, const int *frame_of, const int *origin,
+                                int wh, int ww, const int *step, int radius, int *nearest, cloudaae_stream_t stream);
+
+/* The sums of the contour rows.  A window pixel (x, y) with d = depth_hyp(x, y) is a pair when its mask in depth_hyp is not
+ * 0, nearest(x, y) >= 0 with offset (i, j) and mask_obs, |d - t_c| <= gate for the frame's depth t_c at (u0 + x + i, v0 + y +
+ * j), and the two masks are equal.  With p = P(x, y, d) and dm = p_z a pair gives the row r = ((-i) dm) / fx, g = (1, 0,
+ * -(p_x / p_z)) and then the row r = ((-j) dm) / fy, g = (0, 1, -(p_y / p_z)); J = (p x g, g), the cross product formed as in
+ * cloudaae_depth_align_step.  n_rows [b] int = 2 x pairs; sums [b,28] double in the layout of cloudaae_depth_align_step, the
+ * rows taken in pixel order.  Two launches, runs of 2048 window pixels, as cloudaae_depth_align_step; the same bits run to run
+ * and whatever else is in the batch.  workspace: cloudaae_depth_contour_sums_workspace_bytes(b, wh, ww) bytes, 8-byte aligned
+ * (0: outside the limits). */
+long long cloudaae_depth_contour_sums_workspace_bytes(int b, int wh, int ww);
+int cloudaae_depth_contour_sums(int f, int h, int w, const uint16_t *depth_test, int b, const int *frame_of, const int *origin,
+                                int wh, int ww, const uint16_t *depth_hyp, const float *intr_win, const int *gate,
+                                const int *step, int radius, const int *nearest, int *n_rows, double *sums, void *workspace,
+                                long long workspace_bytes, cloudaae_stream_t stream);
+
+/* The combined step: total[k] = plane_sums[k] + weight * contour_sums[k] (one multiply, one add), k < 28.  status [b]: 4
+ * where plane_status is 4; else 1 where n_pairs + n_rows < 6; else the LDL^T solve, x -> U and pose_out = U pose_in of
+ * cloudaae_depth_align_step on the totals, with its statuses 0, 2 and 3.  x [b,6] is zeros and pose_out [b,16] is pose_in bit
+ * for bit for every status but 0.  plane_sums, n_pairs and plane_status are the sums, n_pairs and status that
+ * cloudaae_depth_align_step wrote.  1 <= b <= 2^28; weight must be a number.  One launch, one wave per sample. */
+int cloudaae_depth_align_solve(int b, const double *plane_sums, const int *n_pairs, const int *plane_status,
+                               const double *contour_sums, const int *n_rows, double weight, const double *pose_in, double *x,
+                               int *status, double *pose_out, cloudaae_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -9,8 +9,12 @@ frame 0.  Warm-up calls first, then timed calls each; prints min / median / max 
       which a tracker cannot do (frame f starts from the result of frame f - 1), and one frame per call, as frames arrive;
   (e) the pieces of an iteration alone: render_instances of the three windows, and the windowed count of the score.
 The numbers of profiles/notes_track.md come from this script (its output: profiles/track_bench_8x480x640.json).
+With --contour, (b) and (c) run with the occluding-contour term at its defaults ("Contours"), and
+  (f) the term's three entries alone: edge_nearest (once per frame), contour_sums and solve_sums (once per iteration)
+is added; (a), (d) and (e) are what they are without it.  The numbers of profiles/notes_track_contour.md come from one run
+with and one without the flag in the same session.
 
-    python tools/bench_track.py [OUT.json]
+    python tools/bench_track.py [--contour] [OUT.json]
 """
 import json
 import os
@@ -30,6 +34,8 @@ torch.cuda.set_device(0)
 dev = torch.device("cuda:0")
 F, H, W = 8, 480, 640
 CALLS = int(os.environ.get("BENCH_TRACK_CALLS", "10"))
+CONTOUR = True if "--contour" in sys.argv[1:] else None
+ARGS = [a for a in sys.argv[1:] if a != "--contour"]
 s = DR.scene()
 meshes = [(m[0], m[1]) for m in s['meshes']]
 intr = np.tile(np.array([[750.0, 750.0, 319.5, 239.5, 10000.0]], np.float32), (F, 1))
@@ -76,9 +82,10 @@ print(json.dumps(res["shape"]), flush=True)
 res["a_align_step"] = timed(lambda: track.align_step(depth, dv["frame_of"], dv["origin"], hyp, dv["rows"], gate, jump, track.COS_MIN,
                                                      a["trajectory"][0]), calls=3 * CALLS)
 print("a_align_step", res["a_align_step"], flush=True)
-res["b_align_poses"] = timed(lambda: track.align_poses(depth, intr, packed, mesh_of, [1, 1, 1], truth[0]))
+res["contour"] = bool(CONTOUR)
+res["b_align_poses"] = timed(lambda: track.align_poses(depth, intr, packed, mesh_of, [1, 1, 1], truth[0], contour=CONTOUR))
 print("b_align_poses", res["b_align_poses"], flush=True)
-res["c_track_objects_8_frames"] = timed(lambda: track.track_objects(depth, intr, packed, (mesh_of, truth[0])))
+res["c_track_objects_8_frames"] = timed(lambda: track.track_objects(depth, intr, packed, (mesh_of, truth[0]), contour=CONTOUR))
 res["c_track_objects_per_frame_median_us"] = res["c_track_objects_8_frames"]["median_us"] / F
 print("c_track_objects_8_frames", res["c_track_objects_8_frames"], res["c_track_objects_per_frame_median_us"], flush=True)
 res["d_detect_objects_8_frames"] = timed(lambda: detect.detect_objects(depth, intr, packed, models))
@@ -93,11 +100,25 @@ tau = torch.from_numpy(track.tau_units(np.full(3, track.TAU), factor)).to(dev)
 res["e_count_windows"] = timed(lambda: detect.fit_counts_window(depth, None, dv["frame_of"], None, dv["origin"],
                                                                 hyp.view(3, 1, a["wh"], a["ww"]), tau), calls=3 * CALLS)
 print("e_count_windows", res["e_count_windows"], flush=True)
+if CONTOUR:
+    step = torch.from_numpy(track.tau_units(np.full(3, track.CONTOUR_STEP), factor)).to(dev)
+    R = track.CONTOUR_RADIUS
+    res["f_edge_nearest"] = timed(lambda: track.edge_nearest(depth, dv["frame_of"], dv["origin"], a["wh"], a["ww"], step, R), calls=3 * CALLS)
+    print("f_edge_nearest", res["f_edge_nearest"], flush=True)
+    near = track.edge_nearest(depth, dv["frame_of"], dv["origin"], a["wh"], a["ww"], step, R)
+    plane = track.align_step(depth, dv["frame_of"], dv["origin"], hyp, dv["rows"], gate, jump, track.COS_MIN, a["trajectory"][0])
+    res["f_contour_sums"] = timed(lambda: track.contour_sums(depth, dv["frame_of"], dv["origin"], hyp, dv["rows"], gate, step, R, near),
+                                  calls=3 * CALLS)
+    print("f_contour_sums", res["f_contour_sums"], flush=True)
+    con = track.contour_sums(depth, dv["frame_of"], dv["origin"], hyp, dv["rows"], gate, step, R, near)
+    res["f_solve_sums"] = timed(lambda: track.solve_sums(plane, con, track.CONTOUR_WEIGHT, a["trajectory"][0]), calls=3 * CALLS)
+    print("f_solve_sums", res["f_solve_sums"], flush=True)
+    res["f_n_rows"] = con["n_rows"].cpu().numpy().tolist()
 
-t = track.track_objects(depth, intr, packed, (mesh_of, truth[0]))
+t = track.track_objects(depth, intr, packed, (mesh_of, truth[0]), contour=CONTOUR)
 res["check"] = dict(error=[[float(np.abs(t.poses[f, j] - truth[f, j]).max()) for j in range(3)] for f in range(F)],
                     lost=t.lost.astype(int).tolist(), num=t.num.tolist(), den=t.den.tolist(), n_pairs=t.n_pairs.tolist())
 print(json.dumps(res["check"]))
-if len(sys.argv) > 1:
-    with open(sys.argv[1], "w") as fh:
+if ARGS:
+    with open(ARGS[0], "w") as fh:
         json.dump(res, fh, indent=1)

@@ -4,8 +4,12 @@ the 384 x 512 table scene, one object at a time -- the 7 cm cube, the L prism ly
 a constant and a constant-velocity start, on clean frames and on frames that went through the 'kinect1' sensor model
 (tests/depth_noise_reference.py).  Prints max |T - T_true| over the 4 x 4 entries per frame, and whether the track was lost.
 
-    python tools/track_accuracy.py
+    python tools/track_accuracy.py [--contour]
+
+--contour adds the occluding-contour term of DESIGN.md "Contours" at its defaults (tests/contour_reference.py): the table of
+profiles/notes_track_contour.md.
 """
+import argparse
 import os
 import sys
 
@@ -13,6 +17,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import contour_reference as CR
 import depth_noise_reference as DN
 import detect_reference as DR
 import render_reference as R
@@ -34,6 +39,9 @@ def pose(obj, f, motion):
 
 
 def main():
+    parser = argparse.ArgumentParser(description="the restatement's tracking accuracy on the table scene")
+    parser.add_argument("--contour", action="store_true", help="with the occluding-contour term at its defaults")
+    run = CR.track if parser.parse_args().contour else TR.track
     meshes = DR.scene_meshes()
     intr = np.tile(TR.SCENE_INTR, (TR.FRAMES, 1))
     print("| object | motion | start | sensor | max abs T - T_true per frame | lost |")
@@ -47,7 +55,7 @@ def main():
                              seed=7, first_frame=0)
             for sname, depth in (("clean", clean['depth']), ("kinect1", noisy['depth'])):
                 for start in ("constant", "velocity"):
-                    r = TR.track(depth, TR.SCENE_INTR, meshes, [obj], truth[:1], motion=start)
+                    r = run(depth, TR.SCENE_INTR, meshes, [obj], truth[:1], motion=start)
                     err = ["%.1e" % TR.pose_error(r['poses'][f, 0], truth[f]) for f in range(TR.FRAMES)]
                     print("| %s | %s | %s | %s | %s | %s |" % (PLACE[obj][0], mname, start, sname, " ".join(err),
                                                              "".join("x" if v else "." for v in r['lost'][:, 0])), flush=True)
