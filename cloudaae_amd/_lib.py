@@ -164,6 +164,9 @@ _SIGNATURES = {
     "cloudaae_depth_edge_nearest": [_I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _I, _P, _P],
     "cloudaae_depth_contour_sums": [_I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P],
     "cloudaae_depth_align_solve": [_I, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P],
+    "cloudaae_tsdf_integrate": [_I, _I, _I, _D, _D, _D, _D, _P, _I, _I, _I, _P, _P, _P, _P, _P, _D, _D, _D, _P],
+    "cloudaae_tsdf_count": [_I, _I, _I, _P, _I, _P, _P],
+    "cloudaae_tsdf_emit": [_I, _I, _I, _D, _D, _D, _D, _P, _I, _P, _L, _P, _P, _P],
 }
 
 

@@ -7,6 +7,7 @@ DESIGN.md ("Mesh sampling"); a model is a function of (seed, mesh id) alone.
     v, t, c = read_ply("obj_000001.ply", scale=0.001)                       # BOP meshes are in millimetres
     models, normals = models_from_meshes(paths, return_normals=True)       # [S,2048,6] f32, [S,2048,3] f64 (device)
     write_obj_models("obj_models.tfrecords", models)                       # what --data_dir / load_object_models read
+    write_ply("model.ply", vertices, triangles)                            # e.g. a mesh fused by utils/fuse.py
 
     python -m cloudaae_amd.utils.mesh_models --meshes DIR --out FILE [--scale 0.001] [--seed N]
 """
@@ -82,7 +83,7 @@ def _ply_binary_element(data, pos, count, props):
             first.append(None)
         else:
             cdt = np.dtype("<" + prop[1])
-            if p + cdt.itemsize > len(data):
+            if count and p + cdt.itemsize > len(data):          # (an element without rows, as write_ply's faces of an empty mesh)
                 raise ValueError("PLY file is cut short")
             k = int(np.frombuffer(data, cdt, 1, p)[0]) if count else 0
             first.append(k)
@@ -201,6 +202,25 @@ def read_ply(path, scale=1.0):
         raise ValueError("PLY vertex index outside int32")
     triangles = triangles.astype(np.int32)
     return vertices, triangles, colors
+
+
+def write_ply(path, vertices, triangles):
+    """(vertices [V,3], triangles [T,3]; arrays or tensors) -> a binary_little_endian PLY file with float x y z and faces as
+    `list uchar int vertex_indices`: what read_ply reads back, the float32 coordinates bit for bit."""
+    v = np.asarray(vertices.detach().cpu() if isinstance(vertices, torch.Tensor) else vertices)
+    t = np.asarray(triangles.detach().cpu() if isinstance(triangles, torch.Tensor) else triangles)
+    require(v.ndim == 2 and v.shape[1] == 3, "vertices must be [V, 3]")
+    require(t.ndim == 2 and t.shape[1] == 3 and t.dtype.kind in "iu", "triangles must be an integer [T, 3]")
+    require(t.size == 0 or (t.min() >= 0 and t.max() < len(v)), "a triangle names a vertex outside the mesh")
+    faces = np.zeros(len(t), np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    faces["n"], faces["i"] = 3, t
+    header = "\n".join(["ply", "format binary_little_endian 1.0", "element vertex %d" % len(v), "property float x",
+                        "property float y", "property float z", "element face %d" % len(t),
+                        "property list uchar int vertex_indices", "end_header"]) + "\n"
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(np.ascontiguousarray(v, "<f4").tobytes())
+        f.write(faces.tobytes())
 
 
 # ---- meshes on the device ------------------------------------------------------------------------------------------------

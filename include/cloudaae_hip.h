@@ -58,7 +58,7 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * cloudaae_depth_foreground, cloudaae_depth_components and cloudaae_component_labels, the last two with a workspace query;
  * cloudaae_depth_fit_counts_window and cloudaae_detect_assign; cloudaae_depth_creases with its workspace query;
  * cloudaae_depth_align_step with its workspace query; cloudaae_depth_edge_nearest, cloudaae_depth_contour_sums with its
- * workspace query and cloudaae_depth_align_solve. */
+ * workspace query and cloudaae_depth_align_solve; cloudaae_tsdf_integrate, cloudaae_tsdf_count and cloudaae_tsdf_emit. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -1488,6 +1488,46 @@ int cloudaae_depth_contour_sums(int f, int h, int w, const uint16_t *depth_test,
 int cloudaae_depth_align_solve(int b, const double *plane_sums, const int *n_pairs, const int *plane_status,
                                const double *contour_sums, const int *n_rows, double weight, const double *pose_in, double *x,
                                int *status, double *pose_out, cloudaae_stream_t stream);
+
+/* ---- fused models: a signed distance volume from posed depth frames, and its mesh ("Fused models") ---- */
+
+/* Shared by the three entries below.  The volume has nx x ny x nz voxels of side `voxel` (metres, in the object's frame); the
+ * centre of voxel (i, j, k) is (ox + (i + 0.5) voxel, oy + (j + 0.5) voxel, oz + (k + 0.5) voxel) and its linear index (k ny +
+ * j) nx + i.  state [nz,ny,nx,4] int, device memory, 16-byte aligned: (acc, cnt, acc_deep, cnt_deep) per voxel; the caller
+ * zeroes it before the first frame.  Limits: 2 <= nx, ny, nz <= 512, nx ny nz <= 2^27; the origin finite, the voxel finite and
+ * positive.  Outside them, or with a null required pointer, a call returns an error and launches nothing. */
+
+/* Adds f frames to the state.  depth [f,h,w] uint16; label [f,h,w] uint8 and want [f] int, both or neither (either null: every
+ * pixel with depth != 0 is used; else a pixel of frame g is used when want[g] == 0 or label == want[g]); intr [f,5] float:
+ * fx, fy, cx, cy, factor_depth; poses [f,16] double, row-major 4 x 4, model -> camera.  Per voxel centre (x, y, z) and frame,
+ * in float64 on exactly widened values, un-fused: X = ((A0 x + A1 y) + A2 z) + A3, Y and Z alike; nothing unless Z > z_near;
+ * u' = ((fx X) / Z + cx) + 0.5, v' alike; nothing unless 0 <= u' < w and 0 <= v' < h (a NaN fails); d = depth at (floor u',
+ * floor v'); nothing when d = 0 or the pixel is not used; sdf = d / factor_depth - Z; q = (int) rint(((sdf < front ? sdf :
+ * front) / front) * 4096); sdf >= -behind: acc += q, cnt += 1; else sdf >= -front: acc_deep += q, cnt_deep += 1.  The sums are
+ * integers: any split of the frames over calls and any order of the frames gives the same state bit for bit; they wrap
+ * silently beyond 2^19 votes per voxel over all calls.  Limits: 1 <= f <= 2^19, h, w >= 1, h w <= 2^24; front, behind and
+ * z_near finite, front > behind > 0, z_near > 0.  One launch, a lane per voxel, no atomics. */
+int cloudaae_tsdf_integrate(int nx, int ny, int nz, double ox, double oy, double oz, double voxel, int *state, int f, int h,
+                            int w, const uint16_t *depth, const uint8_t *label, const int *want, const float *intr,
+                            const double *poses, double front, double behind, double z_near, cloudaae_stream_t stream);
+
+/* Marching tetrahedra on the voxel centres.  A voxel's value is acc / cnt when cnt >= min_count, else acc_deep / cnt_deep when
+ * cnt_deep >= 1, else unknown; it is inside when the value is < 0.  Cell (i, j, k), 0 <= i < nx - 1 (j, k alike), linear index
+ * (k (ny - 1) + j)(nx - 1) + i, has corner c at voxel (i + (c & 1), j + ((c >> 1) & 1), k + (c >> 2)); a cell with an unknown
+ * corner has no triangle.  tri_count [cells] uint8: the triangles of every cell (0..12), six tetrahedra around the diagonal
+ * from corner 0 to corner 7 with one or two triangles each.  min_count >= 1.  One launch, a lane per cell. */
+int cloudaae_tsdf_count(int nx, int ny, int nz, const int *state, int min_count, uint8_t *tri_count, cloudaae_stream_t stream);
+
+/* The triangles themselves.  tri_offset [cells] long long: the exclusive prefix sum of cloudaae_tsdf_count's tri_count for the
+ * same state and min_count; total: their sum (0: nothing is launched); a cell whose offset and count do not fit into [0,
+ * total] writes nothing.  tri_pos [total,3,3] double: the vertices in metres; tri_key [total,3] long long: the vertex's edge,
+ * lo * 8 + code, lo the smaller linear voxel index of the edge's two voxels and code = dx + 2 dy + 4 dz of the other minus lo
+ * (1..7).  A vertex lies at c_lo + (c_hi - c_lo) t per coordinate, t = v_lo / (v_lo - v_hi): the same bits from every cell
+ * that touches the edge.  Order: cell, tetrahedron, triangle; normals (p1 - p0) x (p2 - p0) point from inside to outside.
+ * One launch, a lane per cell. */
+int cloudaae_tsdf_emit(int nx, int ny, int nz, double ox, double oy, double oz, double voxel, const int *state, int min_count,
+                       const long long *tri_offset, long long total, double *tri_pos, long long *tri_key,
+                       cloudaae_stream_t stream);
 
 #ifdef __cplusplus
 }
