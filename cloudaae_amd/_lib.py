@@ -167,6 +167,7 @@ _SIGNATURES = {
     "cloudaae_tsdf_integrate": [_I, _I, _I, _D, _D, _D, _D, _P, _I, _I, _I, _P, _P, _P, _P, _P, _D, _D, _D, _P],
     "cloudaae_tsdf_count": [_I, _I, _I, _P, _I, _P, _P],
     "cloudaae_tsdf_emit": [_I, _I, _I, _D, _D, _D, _D, _P, _I, _P, _L, _P, _P, _P],
+    "cloudaae_tsdf_raycast": [_I, _I, _I, _D, _D, _D, _D, _P, _I, _I, _I, _I, _P, _P, _D, _D, _P, _P],
 }
 
 

@@ -1,0 +1,221 @@
+"""Scanning: an object that has no CAD model and no known poses is followed through a depth sequence and fused as it goes.
+Each new frame is aligned against the volume fused so far -- the volume is raycast into a depth window at the current pose
+(cloudaae_tsdf_raycast; csrc/tsdf.hip), track.align_step solves a point-to-plane step between that window and the frame, that
+is repeated -- the result is judged by the windowed counts of "Detections" under the silhouette rule, and a frame that is not
+lost is summed into the volume at its pose (fuse.integrate).  Frame 0 defines the object's frame.  The definition is in
+DESIGN.md ("Scanning").
+
+    s = scan_object(depth, intrinsics, 0.002)                       # Scan; s.poses [F,4,4], s.lost [F], s.volume
+    vertices, triangles = s.mesh()                                  # what mesh_models.pack_meshes takes as a mesh
+    d = raycast(volume, poses, intr_win, wh, ww)                    # [B,wh,ww]: the volume seen from B poses
+
+    python -m cloudaae_amd.utils.scan --files REC_pcnn.tfrecord --target_cls C --voxel 0.002 --out model.ply [--every N]
+        [--motion velocity]
+"""
+import argparse
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .._lib import ptr, require, stream
+from . import detect, fuse, render, track
+from .bop_score import _depth
+from .pose_verify import tau_units
+
+# a choice, not a measurement
+STEP_VOXELS = 0.5         # the march's step along the camera depth, in voxels
+GROW = 0.5                # of the first frame's largest side, added to its box on every side
+
+
+# ---- the binding ------------------------------------------------------------------------------------------------------------
+def raycast(volume, poses, intr_win, wh, ww, step=None, min_count=1, z_near=render.Z_NEAR):
+    """cloudaae_tsdf_raycast.  volume a fuse.Volume; poses [B,4,4] float64, model -> camera; intr_win [B,5] float32: the
+    windows' rows (fx, fy, cx - u0, cy - v0, factor_depth), both device tensors (or numpy, uploaded); step in metres of camera
+    depth (default 0.5 voxel).  -> depth [B,wh,ww]: a device int16 tensor holding the uint16 bits, as the renderer returns;
+    0 where the ray meets no surface from known outside.  No read-back."""
+    require(isinstance(volume, fuse.Volume), "volume must be a Volume")
+    dev = volume.device
+
+    def tensor(x, dtype):
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        return t.to(device=dev, dtype=dtype).contiguous()
+    pose, rows = tensor(poses, torch.float64), tensor(intr_win, torch.float32)
+    require(pose.dim() == 3 and tuple(pose.shape[1:]) == (4, 4) and int(pose.shape[0]) >= 1, "poses must be [B, 4, 4], B >= 1")
+    B, wh, ww = int(pose.shape[0]), int(wh), int(ww)
+    require(tuple(rows.shape) == (B, 5), "intr_win must be [B, 5]")
+    require(wh >= 1 and ww >= 1 and wh * ww <= (1 << 24) and B * wh * ww <= (1 << 28), "outside the limits: wh ww <= 2^24, B wh ww <= 2^28")
+    step = STEP_VOXELS * volume.voxel if step is None else float(step)
+    nx, ny, nz = volume.dims
+    ox, oy, oz = volume.origin
+    out = _lib.empty((B, wh, ww), dtype=torch.int16, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().cloudaae_tsdf_raycast(nx, ny, nz, ox, oy, oz, volume.voxel, ptr(volume.state), int(min_count), B, wh, ww,
+                                                    ptr(rows), ptr(pose), step, float(z_near), ptr(out), stream()),
+                   "cloudaae_tsdf_raycast")
+    return out
+
+
+# ---- the loop ---------------------------------------------------------------------------------------------------------------
+class Scan(object):
+    """The result of scan_object.  poses [F,4,4] float64: the object's pose in every frame, model -> camera (a lost frame
+    keeps the last good pose); num, den [F]: the silhouette rule's fraction of the frame's attempt (0 / 1 for frame 0);
+    n_pairs, status [F]: of the attempt's last step; lost [F] bool, all numpy; volume: the fuse.Volume, on the device."""
+
+    def mesh(self):
+        """fuse.extract_mesh(volume, min_count) -> (vertices [V,3] float32, triangles [T,3] int32) on the device."""
+        return fuse.extract_mesh(self.volume, self.min_count)
+
+
+def _first_pose(dt, lab, intr, want):
+    """No rotation; the translation is the centre of the used pixels' box in the camera's frame (one read-back)."""
+    eye = torch.eye(4, dtype=torch.float64, device=dt.device).unsqueeze(0)
+    box = fuse.used_points_aabb(dt[:1], None if lab is None else lab[:1], intr[:1], eye, None if lab is None else want[:1])
+    T = np.eye(4)
+    T[:3, 3] = (box[0] + box[1]) / 2.0
+    return T
+
+
+def scan_object(depth, intrinsics, voxel, label=None, want=None, first_pose=None, aabb=None, grow=GROW, motion="constant",
+                iterations=track.ITERATIONS, gate=track.GATE, jump=track.JUMP, cos_min=track.COS_MIN, margin=track.MARGIN,
+                min_score=track.MIN_SCORE, tau=track.TAU, min_count=1, front=None, behind=None, step=None, on_frame=None, on_step=None):
+    """An unknown object followed through depth [F,H,W] uint16 (numpy, or a device tensor holding the bits as int16) with
+    intrinsics [F,5] (or [5]) float32, and fused into a volume of `voxel` metres.  label [F,H,W] uint8 with want [F] (or one
+    number) restricts the integration as in fuse.integrate and is handed to the counts.  Frame 0 defines the object's frame:
+    first_pose (model -> camera; default no rotation and the centre of the used pixels' box) and aabb [2,3], the object's
+    extent in that frame (default fuse.used_points_aabb of frame 0 grown on every side by `grow` times its largest side: one
+    view sees only the front); the volume is fuse.volume_for(aabb, voxel) and is not resized later.  Frame 0 is integrated at
+    first_pose.  Every later frame starts from the last pose (motion='velocity': track.predict), takes track.pose_windows of
+    that pose and the box, runs `iterations` times raycast + track.align_step, raycasts once more at the final pose and
+    counts it with detect.fit_counts_window (tau in metres); the score is the silhouette rule's, and the frame is lost when
+    num min_den < min_num den or it has no window, as in track_objects.  A frame that is not lost is integrated at its pose;
+    a lost one is not, the pose stays at the last good one and the next frame starts from it at rest.  Nothing is read back
+    inside the iterations; one read-back per frame.  step: the raycast's, metres (default 0.5 voxel).  Two hooks for tests and
+    tools: on_step(f, dict(pose_in, depth_hyp, pose_out, n_pairs, status: device tensors; origin, wh, ww, rows, frame_of:
+    host)) after every step and on_frame(f, pose, volume) after every frame.  -> Scan."""
+    from . import depth_components as dc_util
+    require(motion in ("constant", "velocity"), "motion must be 'constant' or 'velocity'")
+    num_min, den_min = int(min_score[0]), int(min_score[1])
+    require(0 <= num_min <= den_min and den_min >= 1, "min_score must be (num, den) with 0 <= num <= den, den >= 1")
+    require(int(iterations) >= 0 and int(min_count) >= 1, "iterations must be >= 0 and min_count >= 1")
+    dev = depth.device if isinstance(depth, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+    dt = _depth(dc_util._depth_tensor(depth, dev) if isinstance(depth, np.ndarray) else depth, "depth", 3)
+    F, H, W = (int(v) for v in dt.shape)
+    intr = np.ascontiguousarray(np.broadcast_to(track._host(intrinsics, np.float32).reshape(-1, 5), (F, 5)))
+    require((label is None) or (want is not None), "label and want come together")
+    if label is not None:
+        want = np.ascontiguousarray(np.broadcast_to(track._host(want, np.int64).astype(np.int32).reshape(-1), (F,)))
+    dt, intr_dev, _, lab, wnt = fuse._frames(dev, dt, intr, np.tile(np.eye(4), (F, 1, 1)), label, want if label is not None else None)
+    first = _first_pose(dt, lab, intr_dev, wnt) if first_pose is None else track._host(first_pose, np.float64).reshape(4, 4).copy()
+
+    def pose_tensor(T):
+        return torch.from_numpy(np.ascontiguousarray(T, np.float64).reshape(1, 4, 4)).to(dev)
+
+    def integrate(f, pose_dev):
+        fuse.integrate(volume, dt[f:f + 1], intr_dev[f:f + 1], pose_dev, None if lab is None else lab[f:f + 1],
+                       None if lab is None else wnt[f:f + 1], front=front, behind=behind)
+
+    if aabb is None:
+        box = fuse.used_points_aabb(dt[:1], None if lab is None else lab[:1], intr_dev[:1], pose_tensor(first),
+                                    None if lab is None else wnt[:1])
+        side = float((box[1] - box[0]).max())
+        aabb = np.stack([box[0] - float(grow) * side, box[1] + float(grow) * side])
+    aabb = track._host(aabb, np.float64).reshape(2, 3)
+    volume = fuse.volume_for(aabb, voxel, device=dev)
+    step = STEP_VOXELS * volume.voxel if step is None else float(step)
+
+    s = Scan()
+    s.volume, s.min_count, s.aabb = volume, int(min_count), aabb
+    s.poses = np.zeros((F, 4, 4))
+    s.num, s.den = np.zeros(F, np.int64), np.ones(F, np.int64)
+    s.n_pairs, s.status, s.lost = np.zeros(F, np.int32), np.zeros(F, np.int32), np.zeros(F, bool)
+    integrate(0, pose_tensor(first))
+    s.poses[0] = first
+    if on_frame is not None:
+        on_frame(0, first, volume)
+    last, before = first.copy(), None
+    for f in range(1, F):
+        start = track.predict(last, before, motion)
+        origin, wh, ww, ok = track.pose_windows(start[None], aabb[None], intr[f][None], H, W, margin)
+        rows_host = intr[f][None].copy()
+        rows_host[:, 2] = intr[f, 2] - origin[:, 0].astype(np.float32)
+        rows_host[:, 3] = intr[f, 3] - origin[:, 1].astype(np.float32)
+        factor = np.array([intr[f, 4]], np.float64)
+        units = [int(tau_units(np.array([q], np.float64), factor)[0]) for q in (gate, jump, tau)]
+        # one upload of the integers: the frame (or -1 without a window), gate, jump, tau, the origin, want
+        ints = torch.from_numpy(np.array([[f if ok[0] else -1] + units + [int(origin[0, 0]), int(origin[0, 1]),
+                                                                          int(want[f]) if lab is not None else 0]], np.int32)).to(dev)
+        frame_dev, gate_dev, jump_dev, tau_dev = (ints[:, c].contiguous() for c in range(4))
+        org, want_dev = ints[:, 4:6].contiguous(), ints[:, 6].contiguous()
+        rows = torch.from_numpy(np.ascontiguousarray(rows_host)).to(dev)
+        pose = pose_tensor(start)
+        n_pairs = torch.zeros((1,), dtype=torch.int32, device=dev)
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+        for _ in range(int(iterations)):
+            d = raycast(volume, pose, rows, wh, ww, step, min_count)
+            r = track.align_step(dt, frame_dev, org, d, rows, gate_dev, jump_dev, cos_min, pose)
+            if on_step is not None:
+                on_step(f, dict(pose_in=pose, depth_hyp=d, pose_out=r["pose_out"], n_pairs=r["n_pairs"], status=r["status"],
+                                origin=origin, wh=wh, ww=ww, rows=rows_host, frame_of=f if ok[0] else -1))
+            pose, n_pairs, status = r["pose_out"], r["n_pairs"], r["status"]
+        d = raycast(volume, pose, rows, wh, ww, step, min_count)
+        c = detect.fit_counts_window(dt, lab, frame_dev, want_dev if lab is not None else None, org, d.view(1, 1, wh, ww), tau_dev)
+        # the one read-back: the pose as its bits, the counters, the last step's pairs and status
+        host = torch.cat([pose.contiguous().view(torch.int32).reshape(-1), c["counts"].reshape(-1), n_pairs, status]).cpu().numpy()
+        final = host[:32].copy().view(np.float64).reshape(4, 4)
+        counts = host[32:38].astype(np.int64)
+        num, den = int(counts[1]), int(counts[1] + counts[2] + counts[3])
+        num, den = (num, den) if den > 0 else (0, 1)
+        lost = (not ok[0]) or (num * den_min < num_min * den)
+        if lost:
+            before = None
+        else:
+            before, last = last.copy(), final
+            integrate(f, pose)
+        s.poses[f], s.num[f], s.den[f], s.n_pairs[f], s.status[f], s.lost[f] = last, num, den, host[38], host[39], lost
+        if on_frame is not None:
+            on_frame(f, last, volume)
+    return s
+
+
+# ---- command line -----------------------------------------------------------------------------------------------------------
+def main(argv=None):
+    parser = argparse.ArgumentParser(description="scan one class of a <seq>_pcnn.tfrecord into a mesh from the pose of its first frame")
+    parser.add_argument("--files", required=True, help="one <seq>_pcnn.tfrecord; its frames are taken in file order")
+    parser.add_argument("--target_cls", type=int, required=True, help="the class to scan (its label in the frames is class + 1)")
+    parser.add_argument("--voxel", type=float, default=0.002, help="voxel side in metres")
+    parser.add_argument("--out", required=True, help="the PLY file to write")
+    parser.add_argument("--every", type=int, default=1, help="take every N-th frame")
+    parser.add_argument("--motion", choices=["constant", "velocity"], default="constant")
+    parser.add_argument("--gpu", type=int, default=0)
+    args = parser.parse_args(argv)
+    from .. import tfrecord_io
+    from . import mesh_models
+    torch.cuda.set_device(args.gpu)
+    require(args.every >= 1, "--every must be >= 1")
+    c = args.target_cls
+    frames = [fr for fr in list(tfrecord_io.read_frames(args.files))[::args.every] if bool(fr["class_one_hot"][c])]
+    require(len(frames) >= 1, "no frame of %s shows class %d" % (args.files, c))
+    depth = np.stack([fr["depth"] for fr in frames])
+    label = np.stack([fr["label"] for fr in frames]).astype(np.uint8)
+    intr = np.array([[fr[k] for k in ("fx", "fy", "cx", "cy", "factor_depth")] for fr in frames], np.float32)
+    truth = np.tile(np.eye(4), (len(frames), 1, 1))
+    for f, fr in enumerate(frames):
+        truth[f, :3, :3], truth[f, :3, 3] = track.quat2mat(fr["quaternions"][c]), fr["translations"][c]
+    # only the first pose is used; the others are what the printed errors are measured against
+    s = scan_object(depth, intr, args.voxel, label=label, want=np.full(len(frames), c + 1, np.int32), first_pose=truth[0],
+                    motion=args.motion)
+    vertices, triangles = s.mesh()
+    mesh_models.write_ply(args.out, vertices, triangles)
+    for f, fr in enumerate(frames):
+        rot, trans = track.pose_errors(s.poses[f], truth[f])
+        print("frame %d score %d/%d lost %d rot_err_deg %.4f trans_err_m %.6f"
+              % (int(fr["frame_id"]), s.num[f], s.den[f], int(s.lost[f]), rot, trans))
+    print("%d frames into %d x %d x %d voxels of %g m, %d lost" % ((len(frames),) + s.volume.dims + (s.volume.voxel, int(s.lost.sum()))))
+    print("%d vertices, %d triangles, %d boundary edges, %d components written to %s"
+          % (fuse.mesh_counts(vertices, triangles) + (args.out,)))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

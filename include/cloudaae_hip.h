@@ -58,7 +58,8 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * cloudaae_depth_foreground, cloudaae_depth_components and cloudaae_component_labels, the last two with a workspace query;
  * cloudaae_depth_fit_counts_window and cloudaae_detect_assign; cloudaae_depth_creases with its workspace query;
  * cloudaae_depth_align_step with its workspace query; cloudaae_depth_edge_nearest, cloudaae_depth_contour_sums with its
- * workspace query and cloudaae_depth_align_solve; cloudaae_tsdf_integrate, cloudaae_tsdf_count and cloudaae_tsdf_emit. */
+ * workspace query and cloudaae_depth_align_solve; cloudaae_tsdf_integrate, cloudaae_tsdf_count and cloudaae_tsdf_emit;
+ * cloudaae_tsdf_raycast. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -1528,6 +1529,25 @@ int cloudaae_tsdf_count(int nx, int ny, int nz, const int *state, int min_count,
 int cloudaae_tsdf_emit(int nx, int ny, int nz, double ox, double oy, double oz, double voxel, const int *state, int min_count,
                        const long long *tri_offset, long long total, double *tri_pos, long long *tri_key,
                        cloudaae_stream_t stream);
+
+/* The volume seen from a pose, as a uint16 depth window ("Scanning").  B samples; sample b has the window's row
+ * intr_win[b] = (fx, fy, cxw, cyw, factor_depth) and poses[b] (4x4 row-major, model -> camera, R and t).  float64 on exactly
+ * widened values, un-fused, in the order written; comparisons in float64 before any conversion.  Window pixel (x, y): dx = (x -
+ * cxw) / fx, dy = (y - cyw) / fy; the ray is parametrised by the camera depth z.  Per axis a: o_a = -((R0a t0 + R1a t1) + R2a
+ * t2), d_a = (R0a dx + R1a dy) + R2a, g0_a = (o_a - origin_a) / voxel - 0.5, gd_a = d_a / voxel: g(z) = g0 + z gd in
+ * voxel-centre coordinates.  Interval: z0 = z_near, z1 = 65535 / factor_depth; per axis with n voxels: gd_a == 0 misses unless
+ * 0 <= g0_a <= n - 1; else ta = (0 - g0_a) / gd_a, tb = ((n - 1) - g0_a) / gd_a, z0 = max(z0, min(ta, tb)), z1 = min(z1,
+ * max(ta, tb)); a NaN misses; the ray misses unless z0 <= z1.  Samples z_k = z0 + (double) k step, k = 0, 1, ... while z_k <=
+ * z1 and k < 4096.  At a sample g = g0 + z_k gd; the cell is i_a = clamp(floor g_a, 0, n_a - 2), f_a = g_a - i_a; the eight
+ * corner values are cloudaae_tsdf_count's with min_count, the sample is unknown when any is; else trilinear: along x v0 + (v1 -
+ * v0) f_x on the corner pairs (0,1), (2,3), (4,5), (6,7), then along y, then along z.  prev starts unknown; an unknown sample
+ * sets prev unknown; v >= 0 sets prev = (v, z_k); v < 0 ends the ray, and with a known prev = (v_p, z_p) it is a hit: z* = z_p +
+ * (z_k - z_p) (v_p / (v_p - v)), du = floor(z* factor_depth + 0.5), the pixel is du when 1 <= du <= 65535.  Every other pixel
+ * is 0; every pixel of depth_out [B,wh,ww] is written.  Limits: the volume's; B, wh, ww >= 1, wh ww <= 2^24, B wh ww <= 2^28;
+ * min_count >= 1; step and z_near finite and > 0.  One launch, a lane per pixel, no atomics. */
+int cloudaae_tsdf_raycast(int nx, int ny, int nz, double ox, double oy, double oz, double voxel, const int *state, int min_count,
+                          int B, int wh, int ww, const float *intr_win, const double *poses, double step, double z_near,
+                          uint16_t *depth_out, cloudaae_stream_t stream);
 
 #ifdef __cplusplus
 }
