@@ -19,23 +19,23 @@
 // disc so do all others of the row; candidates of different rows differ in j, which comes before i.
 //
 // No floating-point atomic, no ticket, no workgroup waits for another: a sample's result is the same bits run to run and
-// whatever else is in the batch.  The LDL^T solve and x -> U restate da_solve of depth_align.hip (icp_plane_update of icp.hip).
+// whatever else is in the batch.
+//
+// Here are the nearest map, the pairing of the rendered edges with it, the two contour rows and the total of the two terms.
+// What the sums and the solve share with the plane step of depth_align.hip is in depth_gn.h: the limits and the launch shape
+// (gn_within_limits, gn_runs), the window's camera and the bounds-checked depth load (GnCam, gn_backproject, gn_depth, here
+// with -1 outside the image, which dc_open reads), the 28 sums of a row (gn_add_row), the workgroup's reduction
+// (gn_store_run), the sum over a sample's runs (gn_add_runs), the LDL^T solve with x -> U (gn_solve) and the write of
+// U pose_in (gn_write_update): weight 0 gives the plane step's own pose because both run that one text.
 #include "common.h"
+#include "depth_gn.h"
 #include "../../include/cloudaae_hip.h"
 
 #include <math.h>
 
 namespace cloudaae {
 
-constexpr long long DC_MAX_PIXELS = 1ll << 24;     // h w, wh ww
-constexpr long long DC_MAX_TOTAL = 1ll << 28;      // b wh ww
 constexpr int DC_MAX_RADIUS = 32;
-
-constexpr int DC_BLOCK = 256;
-constexpr int DC_WAVES = DC_BLOCK / 64;
-constexpr int DC_PIX = 8;                          // consecutive window pixels of a lane
-constexpr int DC_RUN = DC_BLOCK * DC_PIX;          // window pixels of a workgroup of the sums kernel
-constexpr int DC_SUMS = 28;                        // sum r^2, A's upper triangle by rows (21), b (6)
 
 constexpr int EN_TILE = 32;                        // the nearest map's tile side
 constexpr int EN_MASK_SIDE = EN_TILE + 2 * DC_MAX_RADIUS;      // tile + halo R, at the largest R
@@ -50,7 +50,7 @@ struct EdgeNearestArgs {
     int *nearest;                                  // [b, wh, ww]
 };
 
-__global__ __launch_bounds__(DC_BLOCK) void depth_edge_nearest_kernel(EdgeNearestArgs a)
+__global__ __launch_bounds__(GN_BLOCK) void depth_edge_nearest_kernel(EdgeNearestArgs a)
 {
     __shared__ unsigned short zs[EN_DEPTH_SIDE * EN_DEPTH_SIDE];       // 19 208 B
     __shared__ unsigned char mask[EN_MASK_SIDE * EN_MASK_SIDE];        //  9 216 B
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(DC_BLOCK) void depth_edge_nearest_kernel(EdgeNeares
     int *out = a.nearest + (size_t)s * a.wh * a.ww;
     const int fr = a.frame_of[s];
     if (fr < 0 || fr >= a.f) {                     // (the whole workgroup: no barrier has been reached)
-        for (int e = tid; e < EN_TILE * EN_TILE; e += DC_BLOCK) {
+        for (int e = tid; e < EN_TILE * EN_TILE; e += GN_BLOCK) {
             const int x = x0 + (e & (EN_TILE - 1)), y = y0 + e / EN_TILE;
             if (x < a.ww && y < a.wh)
                 out[(size_t)y * a.ww + x] = -1;
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(DC_BLOCK) void depth_edge_nearest_kernel(EdgeNeares
     // frame pixel of entry (0, 0) of the staged depth; entry (c, r) of the masks is entry (c + 1, r + 1) of the depth
     const long long ud = (long long)a.origin[2 * s] + x0 - (R + 1), vd = (long long)a.origin[2 * s + 1] + y0 - (R + 1);
 
-    for (int e = tid; e < side_d * side_d; e += DC_BLOCK) {
+    for (int e = tid; e < side_d * side_d; e += GN_BLOCK) {
         const int r = e / side_d, c = e - r * side_d;
         const long long u = ud + c, v = vd + r;
         unsigned short z = 0;
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(DC_BLOCK) void depth_edge_nearest_kernel(EdgeNeares
         zs[e] = z;
     }
     __syncthreads();
-    for (int e = tid; e < side_m * side_m; e += DC_BLOCK) {
+    for (int e = tid; e < side_m * side_m; e += GN_BLOCK) {
         const int r = e / side_m, c = e - r * side_m;
         const long long u = ud + c + 1, v = vd + r + 1;
         const int at = (r + 1) * side_d + (c + 1);
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(DC_BLOCK) void depth_edge_nearest_kernel(EdgeNeares
         mask[e] = (unsigned char)m;
     }
     __syncthreads();
-    for (int e = tid; e < side_m * EN_TILE; e += DC_BLOCK) {
+    for (int e = tid; e < side_m * EN_TILE; e += GN_BLOCK) {
         const int r = e / EN_TILE, c = e & (EN_TILE - 1);
         const unsigned char *row = mask + r * side_m + c + R;          // the pixel of column c itself
         int best = row[0] != 0 ? 0 : EN_NONE;
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(DC_BLOCK) void depth_edge_nearest_kernel(EdgeNeares
     }
     __syncthreads();
     const int rr = R * R;
-    for (int e = tid; e < EN_TILE * EN_TILE; e += DC_BLOCK) {
+    for (int e = tid; e < EN_TILE * EN_TILE; e += GN_BLOCK) {
         const int y = e / EN_TILE, x = e & (EN_TILE - 1);
         if (x0 + x >= a.ww || y0 + y >= a.wh)
             continue;
@@ -129,15 +129,8 @@ __global__ __launch_bounds__(DC_BLOCK) void depth_edge_nearest_kernel(EdgeNeares
 }
 
 // ---- the contour sums -------------------------------------------------------------------------------------------------------
-// the depth of image [h, w] at pixel (u, v); -1 where that is no pixel of the image (nothing is read there)
-__device__ __forceinline__ int dc_depth(const unsigned short *pix, int h, int w, long long u, long long v)
-{
-    if (u < 0 || u >= w || v < 0 || v >= h)
-        return -1;
-    return (int)pix[(size_t)v * w + (size_t)u];
-}
-
-// one bit of an edge mask: the neighbour lies inside the image and is empty or more than `step` farther than z
+// one bit of an edge mask: the neighbour lies inside the image (gn_depth gave no -1) and is empty or more than `step`
+// farther than z
 __device__ __forceinline__ bool dc_open(int z_nb, int z, int step)
 {
     return z_nb >= 0 && (z_nb == 0 || z_nb - z > step);
@@ -152,72 +145,60 @@ struct ContourSumsArgs {
     int *part_rows;                                // [b, runs]
 };
 
-__global__ __launch_bounds__(DC_BLOCK) void depth_contour_sums_kernel(ContourSumsArgs a)
+__global__ __launch_bounds__(GN_BLOCK) void depth_contour_sums_kernel(ContourSumsArgs a)
 {
-    __shared__ double red[DC_WAVES][DC_SUMS];
-    __shared__ int red_rows[DC_WAVES];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const int s = blockIdx.x / a.runs, run = blockIdx.x % a.runs;
     const int fr = a.frame_of[s];
     if (fr < 0 || fr >= a.f)                       // (the whole workgroup: no barrier has been reached)
         return;
     const int n = a.wh * a.ww;                     // window pixels of a sample
-    const int q0 = run * DC_RUN + tid * DC_PIX;    // the lane's first window pixel (may lie past n)
+    const int q0 = run * GN_RUN + tid * GN_PIX;    // the lane's first window pixel (may lie past n)
     const int gate = a.gate[s], step = a.step[s], R = a.radius;
-    const float *k = a.intr_win + 5 * (size_t)s;
-    const double fx = (double)k[0], fy = (double)k[1], cx = (double)k[2], cy = (double)k[3], factor = (double)k[4];
+    const GnCam cam = gn_cam(a.intr_win + 5 * (size_t)s);
     const unsigned short *hyp = a.depth_hyp + (size_t)s * n;
     const unsigned short *test = a.depth_test + (size_t)fr * a.h * a.w;
     const int *near = a.nearest + (size_t)s * n;
     const long long u0 = a.origin[2 * s], v0 = a.origin[2 * s + 1];
 
-    double acc[DC_SUMS];
+    double acc[GN_SUMS];
 #pragma unroll
-    for (int e = 0; e < DC_SUMS; ++e)
+    for (int e = 0; e < GN_SUMS; ++e)
         acc[e] = 0.0;
     int rows = 0;
     int y = q0 / a.ww, x = q0 - y * a.ww;
 #pragma unroll 1
-    for (int px = 0; px < DC_PIX; ++px) {
+    for (int px = 0; px < GN_PIX; ++px) {
         if (q0 + px < n) {
             const int d = (int)hyp[q0 + px];
             int m = 0;
             if (d != 0) {
-                m |= dc_open(dc_depth(hyp, a.wh, a.ww, x - 1, y), d, step) ? 1 : 0;
-                m |= dc_open(dc_depth(hyp, a.wh, a.ww, x + 1, y), d, step) ? 2 : 0;
-                m |= dc_open(dc_depth(hyp, a.wh, a.ww, x, y - 1), d, step) ? 4 : 0;
-                m |= dc_open(dc_depth(hyp, a.wh, a.ww, x, y + 1), d, step) ? 8 : 0;
+                m |= dc_open(gn_depth(hyp, a.wh, a.ww, x - 1, y, -1), d, step) ? 1 : 0;
+                m |= dc_open(gn_depth(hyp, a.wh, a.ww, x + 1, y, -1), d, step) ? 2 : 0;
+                m |= dc_open(gn_depth(hyp, a.wh, a.ww, x, y - 1, -1), d, step) ? 4 : 0;
+                m |= dc_open(gn_depth(hyp, a.wh, a.ww, x, y + 1, -1), d, step) ? 8 : 0;
             }
             const int code = m != 0 ? near[q0 + px] : -1;
             if (code >= 0 && (code >> 16) == m) {
                 const int i = (code & 255) - R, j = ((code >> 8) & 255) - R;
-                const int t = dc_depth(test, a.h, a.w, u0 + x + i, v0 + y + j);      // (-1: a code that points outside the frame)
+                const int t = gn_depth(test, a.h, a.w, u0 + x + i, v0 + y + j, -1);  // (-1: a code that points outside the frame)
                 const int diff = d - t, mag = diff < 0 ? -diff : diff;
                 if (t >= 0 && mag <= gate) {
-                    const double dm = (double)d / factor;
-                    const double p0 = (((double)x - cx) * dm) / fx, p1 = (((double)y - cy) * dm) / fy, p2 = dm;
+                    double p[3];
+                    gn_backproject(cam, x, y, d, p);
                     rows += 2;
 #pragma unroll 1
                     for (int axis = 0; axis < 2; ++axis) {             // the u row, then the v row
                         const double off = axis == 0 ? -(double)i : -(double)j;
-                        const double r = (off * dm) / (axis == 0 ? fx : fy);
+                        const double r = (off * p[2]) / (axis == 0 ? cam.fx : cam.fy);
                         const double g0 = axis == 0 ? 1.0 : 0.0, g1 = axis == 0 ? 0.0 : 1.0;
-                        const double g2 = -((axis == 0 ? p0 : p1) / p2);
+                        const double g2 = -((axis == 0 ? p[0] : p[1]) / p[2]);
                         double J[6];
-                        J[0] = p1 * g2 - p2 * g1;
-                        J[1] = p2 * g0 - p0 * g2;
-                        J[2] = p0 * g1 - p1 * g0;
+                        J[0] = p[1] * g2 - p[2] * g1;
+                        J[1] = p[2] * g0 - p[0] * g2;
+                        J[2] = p[0] * g1 - p[1] * g0;
                         J[3] = g0, J[4] = g1, J[5] = g2;
-                        acc[0] += r * r;
-                        int e = 1;
-#pragma unroll
-                        for (int g = 0; g < 6; ++g)
-#pragma unroll
-                            for (int c = g; c < 6; ++c)
-                                acc[e++] += J[g] * J[c];
-#pragma unroll
-                        for (int g = 0; g < 6; ++g)
-                            acc[22 + g] += J[g] * r;
+                        gn_add_row(acc, J, r);
                     }
                 }
             }
@@ -225,33 +206,7 @@ __global__ __launch_bounds__(DC_BLOCK) void depth_contour_sums_kernel(ContourSum
         if (++x == a.ww)
             x = 0, ++y;
     }
-#pragma unroll
-    for (int e = 0; e < DC_SUMS; ++e)
-        acc[e] = wave_sum(acc[e]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        rows += __shfl_xor(rows, off, 64);
-    if (lane == 0) {
-#pragma unroll
-        for (int e = 0; e < DC_SUMS; ++e)
-            red[wv][e] = acc[e];
-        red_rows[wv] = rows;
-    }
-    __syncthreads();
-    const size_t at = (size_t)s * a.runs + run;
-    if (tid < DC_SUMS) {
-        double v = red[0][tid];
-#pragma unroll
-        for (int e = 1; e < DC_WAVES; ++e)
-            v += red[e][tid];
-        a.part_sums[at * DC_SUMS + tid] = v;
-    } else if (tid == DC_SUMS) {
-        int v = red_rows[0];
-#pragma unroll
-        for (int e = 1; e < DC_WAVES; ++e)
-            v += red_rows[e];
-        a.part_rows[at] = v;
-    }
+    gn_store_run(acc, rows, (size_t)s * a.runs + run, a.part_sums, a.part_rows);
 }
 
 // one wave per sample: lane k < 28 adds sum k of the sample's runs in run order, lane 28 the rows
@@ -263,100 +218,13 @@ __global__ __launch_bounds__(64) void depth_contour_finish_kernel(int f, int run
     const int s = blockIdx.x, lane = threadIdx.x;
     const int fr = frame_of[s];
     const bool live = fr >= 0 && fr < f;               // (the whole wave)
-    if (lane < DC_SUMS) {
-        double v = 0.0;
-        if (live)
-            for (int r = 0; r < runs; ++r)
-                v += part_sums[((size_t)s * runs + r) * DC_SUMS + lane];
-        sums[(size_t)s * DC_SUMS + lane] = v;
-    } else if (lane == DC_SUMS) {
-        int v = 0;
-        if (live)
-            for (int r = 0; r < runs; ++r)
-                v += part_rows[(size_t)s * runs + r];
-        n_rows[s] = v;
-    }
+    if (lane < GN_SUMS)
+        sums[(size_t)s * GN_SUMS + lane] = gn_add_runs(live, s, runs, part_sums, GN_SUMS, lane);
+    else if (lane == GN_SUMS)
+        n_rows[s] = gn_add_runs(live, s, runs, part_rows, 1, 0);
 }
 
 // ---- the combined solve -----------------------------------------------------------------------------------------------------
-// A x = -b by LDL^T without pivoting on the sums s = (sum r^2, A's upper triangle by rows, b); x = (alpha, beta, gamma, t);
-// U = [Rz(gamma) Ry(beta) Rx(alpha) | t] (3 x 4).  -> 0, or 2 for a pivot that is not a finite number > 0, 3 for a
-// solution with a component that is not finite.  Every loop is unrolled: the arrays stay in registers.
-__device__ __forceinline__ int dc_solve(const double (&s)[DC_SUMS], double (&x)[6], double (&U)[12])
-{
-    double A[6][6], L[6][6], d[6];
-    {
-        int e = 1;
-#pragma unroll
-        for (int g = 0; g < 6; ++g)
-#pragma unroll
-            for (int c = g; c < 6; ++c) {
-                A[g][c] = s[e];
-                A[c][g] = s[e];
-                ++e;
-            }
-    }
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double dj = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k)
-            dj -= (L[j][k] * L[j][k]) * d[k];
-        bad = bad || !(dj > 0.0) || !isfinite(dj);     // (the first bad pivot decides; what follows it is not used)
-        d[j] = dj;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double v = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k)
-                v -= (L[i][k] * L[j][k]) * d[k];
-            L[i][j] = v / dj;
-        }
-    }
-    if (bad)
-        return 2;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {                      // L y = -b
-        double v = -s[22 + i];
-#pragma unroll
-        for (int k = 0; k < i; ++k)
-            v -= L[i][k] * x[k];
-        x[i] = v;
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i)                        // D z = y
-        x[i] = x[i] / d[i];
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {                     // L^T x = z
-        double v = x[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k)
-            v -= L[k][i] * x[k];
-        x[i] = v;
-    }
-    bool finite = true;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-        finite = finite && isfinite(x[i]);
-    if (!finite)
-        return 3;
-    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
-    U[0] = cg * cb;
-    U[1] = (cg * sb) * sa - sg * ca;
-    U[2] = (cg * sb) * ca + sg * sa;
-    U[3] = x[3];
-    U[4] = sg * cb;
-    U[5] = (sg * sb) * sa + cg * ca;
-    U[6] = (sg * sb) * ca - cg * sa;
-    U[7] = x[4];
-    U[8] = -sb;
-    U[9] = cb * sa;
-    U[10] = cb * ca;
-    U[11] = x[5];
-    return 0;
-}
-
 // one wave per sample: lane k < 28 forms plane[k] + w contour[k]; lane 0 decides the status, solves and writes the pose
 __global__ __launch_bounds__(64) void depth_align_combined_solve_kernel(const double *__restrict__ plane_sums,
                                                                        const int *__restrict__ n_pairs,
@@ -367,55 +235,24 @@ __global__ __launch_bounds__(64) void depth_align_combined_solve_kernel(const do
                                                                        double *__restrict__ x_out, int *__restrict__ status,
                                                                        double *__restrict__ pose_out)
 {
-    __shared__ double total[DC_SUMS];
+    __shared__ double total[GN_SUMS];
     const int s = blockIdx.x, lane = threadIdx.x;
-    if (lane < DC_SUMS)
-        total[lane] = plane_sums[(size_t)s * DC_SUMS + lane] + weight * contour_sums[(size_t)s * DC_SUMS + lane];
+    if (lane < GN_SUMS)
+        total[lane] = plane_sums[(size_t)s * GN_SUMS + lane] + weight * contour_sums[(size_t)s * GN_SUMS + lane];
     __syncthreads();
     if (lane != 0)
         return;
-    double sm[DC_SUMS], x[6], U[12];
+    double sm[GN_SUMS], x[6], U[12];
 #pragma unroll
-    for (int k = 0; k < DC_SUMS; ++k)
+    for (int k = 0; k < GN_SUMS; ++k)
         sm[k] = total[k];
     int st = plane_status[s] == 4 ? 4 : (long long)n_pairs[s] + (long long)n_rows[s] < 6 ? 1 : 0;
     if (st == 0)
-        st = dc_solve(sm, x, U);
-    const double *T = pose_in + 16 * (size_t)s;
-    double *out = pose_out + 16 * (size_t)s;
-    status[s] = st;
-    if (st != 0) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            x_out[6 * (size_t)s + k] = 0.0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k)
-            out[k] = T[k];
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-        x_out[6 * (size_t)s + k] = x[k];
-#pragma unroll
-    for (int row = 0; row < 3; ++row) {
-        const double u0 = U[4 * row + 0], u1 = U[4 * row + 1], u2 = U[4 * row + 2], u3 = U[4 * row + 3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            out[4 * row + c] = (u0 * T[c] + u1 * T[4 + c]) + u2 * T[8 + c];
-        out[4 * row + 3] = ((u0 * T[3] + u1 * T[7]) + u2 * T[11]) + u3;
-    }
-    out[12] = out[13] = out[14] = 0.0;
-    out[15] = 1.0;
+        st = gn_solve(sm, x, U);
+    gn_write_update(s, st, x, U, pose_in, x_out, status, pose_out);
 }
 
-static bool dc_within_limits(long long f, long long h, long long w, long long b, long long wh, long long ww)
-{
-    return f >= 1 && h >= 1 && w >= 1 && b >= 1 && wh >= 1 && ww >= 1 && h * w <= DC_MAX_PIXELS && wh * ww <= DC_MAX_PIXELS &&
-           b * (wh * ww) <= DC_MAX_TOTAL;
-}
-
-static const char *const DC_LIMITS =
-    "outside the limits: f, h, w, b, wh, ww >= 1; h * w <= 2^24; wh * ww <= 2^24; b * wh * ww <= 2^28; 1 <= radius <= 32";
+static const char *const DC_LIMITS = CLOUDAAE_GN_LIMITS "; 1 <= radius <= 32";
 
 } // namespace cloudaae
 
@@ -426,7 +263,7 @@ CLOUDAAE_API int cloudaae_depth_edge_nearest(int f, int h, int w, const uint16_t
                                              cloudaae_stream_t stream)
 {
     const char *name = "cloudaae_depth_edge_nearest";
-    CLOUDAAE_REQUIRE(dc_within_limits(f, h, w, b, wh, ww) && radius >= 1 && radius <= DC_MAX_RADIUS, name, DC_LIMITS);
+    CLOUDAAE_REQUIRE(gn_within_limits(f, h, w, b, wh, ww) && radius >= 1 && radius <= DC_MAX_RADIUS, name, DC_LIMITS);
     CLOUDAAE_REQUIRE(depth_test && frame_of && origin && step && nearest, name, "null pointer");
     EdgeNearestArgs a;
     a.f = f, a.h = h, a.w = w, a.wh = wh, a.ww = ww, a.radius = radius;
@@ -436,17 +273,14 @@ CLOUDAAE_API int cloudaae_depth_edge_nearest(int f, int h, int w, const uint16_t
     a.nearest = nearest;
     // b * tiles <= b * (wh + 31) * (ww + 31) / 1024 < 2^28 + b: below the grid limit
     const long long blocks = (long long)b * a.tiles_x * a.tiles_y;
-    hipLaunchKernelGGL(depth_edge_nearest_kernel, dim3((unsigned)blocks), dim3(DC_BLOCK), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(depth_edge_nearest_kernel, dim3((unsigned)blocks), dim3(GN_BLOCK), 0, (hipStream_t)stream, a);
     CLOUDAAE_CHECK_LAUNCH(name);
     return 0;
 }
 
 CLOUDAAE_API long long cloudaae_depth_contour_sums_workspace_bytes(int b, int wh, int ww)
 {
-    if (!dc_within_limits(1, 1, 1, b, wh, ww))
-        return 0;
-    const long long runs = (long long)b * ceil_div((long long)wh * ww, DC_RUN);
-    return runs * (long long)(DC_SUMS * sizeof(double)) + (runs * (long long)sizeof(int) + 7) / 8 * 8;
+    return gn_within_limits(1, 1, 1, b, wh, ww) ? gn_runs(b, wh, ww, nullptr).bytes : 0;
 }
 
 CLOUDAAE_API int cloudaae_depth_contour_sums(int f, int h, int w, const uint16_t *depth_test, int b, const int *frame_of,
@@ -455,24 +289,23 @@ CLOUDAAE_API int cloudaae_depth_contour_sums(int f, int h, int w, const uint16_t
                                              double *sums, void *workspace, long long workspace_bytes, cloudaae_stream_t stream)
 {
     const char *name = "cloudaae_depth_contour_sums";
-    CLOUDAAE_REQUIRE(dc_within_limits(f, h, w, b, wh, ww) && radius >= 1 && radius <= DC_MAX_RADIUS, name, DC_LIMITS);
+    CLOUDAAE_REQUIRE(gn_within_limits(f, h, w, b, wh, ww) && radius >= 1 && radius <= DC_MAX_RADIUS, name, DC_LIMITS);
     CLOUDAAE_REQUIRE(depth_test && frame_of && origin && depth_hyp && intr_win && gate && step && nearest && n_rows && sums &&
                          workspace,
                      name, "null pointer");
-    CLOUDAAE_REQUIRE(((uintptr_t)workspace & 7u) == 0 && workspace_bytes >= cloudaae_depth_contour_sums_workspace_bytes(b, wh, ww),
-                     name, "the workspace is smaller than cloudaae_depth_contour_sums_workspace_bytes or not 8-byte aligned");
+    const GnRuns g = gn_runs(b, wh, ww, workspace);
+    CLOUDAAE_REQUIRE(((uintptr_t)workspace & 7u) == 0 && workspace_bytes >= g.bytes, name,
+                     "the workspace is smaller than cloudaae_depth_contour_sums_workspace_bytes or not 8-byte aligned");
     ContourSumsArgs a;
     a.f = f, a.h = h, a.w = w, a.wh = wh, a.ww = ww, a.radius = radius;
-    a.runs = ceil_div((long long)wh * ww, DC_RUN);
+    a.runs = g.runs;
     a.depth_test = depth_test, a.depth_hyp = depth_hyp;
     a.frame_of = frame_of, a.origin = origin, a.gate = gate, a.step = step, a.nearest = nearest;
     a.intr_win = intr_win;
-    const long long runs = (long long)b * a.runs;
-    a.part_sums = (double *)workspace;
-    a.part_rows = (int *)(a.part_sums + runs * DC_SUMS);
+    a.part_sums = g.part_sums;
+    a.part_rows = g.part_count;
     hipStream_t sm = (hipStream_t)stream;
-    // b * runs <= 2^28 / 2048 + b: below the grid limit
-    hipLaunchKernelGGL(depth_contour_sums_kernel, dim3((unsigned)runs), dim3(DC_BLOCK), 0, sm, a);
+    hipLaunchKernelGGL(depth_contour_sums_kernel, dim3((unsigned)g.all), dim3(GN_BLOCK), 0, sm, a);
     CLOUDAAE_CHECK_LAUNCH(name);
     hipLaunchKernelGGL(depth_contour_finish_kernel, dim3((unsigned)b), dim3(64), 0, sm, f, a.runs, frame_of,
                        (const double *)a.part_sums, (const int *)a.part_rows, n_rows, sums);
@@ -485,7 +318,7 @@ CLOUDAAE_API int cloudaae_depth_align_solve(int b, const double *plane_sums, con
                                             double *x, int *status, double *pose_out, cloudaae_stream_t stream)
 {
     const char *name = "cloudaae_depth_align_solve";
-    CLOUDAAE_REQUIRE(b >= 1 && b <= DC_MAX_TOTAL, name, "outside the limits: 1 <= b <= 2^28");
+    CLOUDAAE_REQUIRE(b >= 1 && b <= GN_MAX_TOTAL, name, "outside the limits: 1 <= b <= 2^28");
     CLOUDAAE_REQUIRE(!isnan(weight), name, "weight must be a number");
     CLOUDAAE_REQUIRE(plane_sums && n_pairs && plane_status && contour_sums && n_rows && pose_in && x && status && pose_out, name,
                      "null pointer");

@@ -44,24 +44,45 @@ SUMS = 28
 
 
 # ---- the binding ------------------------------------------------------------------------------------------------------------
+def _window_inputs(depth_test, frame_of, origin, columns, depth_hyp=None, size=None, intr_win=None):
+    """The window bindings' common inputs, checked: depth_test [F,H,W]; depth_hyp [B,wh,ww], or size = (wh, ww) with B from
+    frame_of; frame_of and the columns ((name, tensor), ...) int32 [B]; origin int32 [B,2]; intr_win, when given, float32 [B,5];
+    one device.  -> (dt, dh or None, (F, H, W, B, wh, ww), device, frame_of, origin, [columns])."""
+    dt = _depth(depth_test, "depth_test", 3)
+    dev = dt.device
+    if depth_hyp is not None:
+        dh = _depth(depth_hyp, "depth_hyp", 3)
+        B, wh, ww = (int(v) for v in dh.shape)
+        require(B >= 1 and wh >= 1 and ww >= 1, "depth_hyp must be [B, wh, ww], none of them 0")
+        require(dh.device == dev, "all inputs must be on one device")
+    else:
+        require(isinstance(frame_of, torch.Tensor) and frame_of.dim() == 1 and frame_of.numel() >= 1, "frame_of must be [B], B >= 1")
+        dh, B, wh, ww = None, int(frame_of.numel()), int(size[0]), int(size[1])
+        require(wh >= 1 and ww >= 1, "wh and ww must be >= 1")
+    frame_of = _int32(frame_of, "frame_of", (B,), dev)
+    columns = [_int32(t, n, (B,), dev) for n, t in columns]
+    origin = _int32(origin, "origin", (B, 2), dev)
+    if intr_win is not None:
+        require(isinstance(intr_win, torch.Tensor) and intr_win.dtype == torch.float32 and tuple(intr_win.shape) == (B, 5) and
+                intr_win.device == dev, "intr_win must be a float32 [B, 5] tensor on the inputs' device")
+    return dt, dh, tuple(int(v) for v in dt.shape) + (B, wh, ww), dev, frame_of, origin, columns
+
+
+def _pose_in(pose_in, B, dev):
+    require(isinstance(pose_in, torch.Tensor) and pose_in.dtype == torch.float64 and pose_in.numel() == 16 * B and
+            pose_in.device == dev, "pose_in must be a float64 [B, 4, 4] tensor on the inputs' device")
+    return pose_in.contiguous()
+
+
 def align_step(depth_test, frame_of, origin, depth_hyp, intr_win, gate, jump, cos_min, pose_in):
     """cloudaae_depth_align_step.  depth_test [F,H,W] and depth_hyp [B,wh,ww]: int16 tensors holding the uint16 bits, or
     uint16; frame_of [B] int32 (an entry outside [0, F) gives status 4 and reads nothing); origin [B,2] int32 = (u0, v0), any
     values; intr_win [B,5] float32: the windows' rows (fx, fy, cx - u0, cy - v0, factor_depth); gate, jump [B] int32 in depth
     units; cos_min a number (<= 0: no normal test); pose_in [B,4,4] float64.  All on one device.  -> dict of n_pairs [B]
     int32, sums [B,28], x [B,6] float64, status [B] int32 and pose_out [B,4,4] float64 on the device.  No read-back."""
-    dt, dh = _depth(depth_test, "depth_test", 3), _depth(depth_hyp, "depth_hyp", 3)
-    F, H, W = (int(v) for v in dt.shape)
-    B, wh, ww = (int(v) for v in dh.shape)
-    dev = dt.device
-    require(B >= 1 and wh >= 1 and ww >= 1, "depth_hyp must be [B, wh, ww], none of them 0")
-    require(dh.device == dev, "all inputs must be on one device")
-    frame_of, gate, jump = (_int32(t, n, (B,), dev) for t, n in ((frame_of, "frame_of"), (gate, "gate"), (jump, "jump")))
-    origin = _int32(origin, "origin", (B, 2), dev)
-    require(isinstance(intr_win, torch.Tensor) and intr_win.dtype == torch.float32 and tuple(intr_win.shape) == (B, 5) and
-            intr_win.device == dev, "intr_win must be a float32 [B, 5] tensor on the inputs' device")
-    require(isinstance(pose_in, torch.Tensor) and pose_in.dtype == torch.float64 and pose_in.numel() == 16 * B and
-            pose_in.device == dev, "pose_in must be a float64 [B, 4, 4] tensor on the inputs' device")
+    dt, dh, (F, H, W, B, wh, ww), dev, frame_of, origin, (gate, jump) = _window_inputs(
+        depth_test, frame_of, origin, (("gate", gate), ("jump", jump)), depth_hyp=depth_hyp, intr_win=intr_win)
+    pose_in = _pose_in(pose_in, B, dev)
     cos_min = float(cos_min)
     require(cos_min == cos_min, "cos_min must be a number")
     L = _lib.lib()
@@ -73,9 +94,9 @@ def align_step(depth_test, frame_of, origin, depth_hyp, intr_win, gate, jump, co
     ws = _lib.empty((nbytes,), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         _lib.check(L.cloudaae_depth_align_step(F, H, W, ptr(dt), B, ptr(frame_of), ptr(origin), wh, ww, ptr(dh),
-                                               ptr(intr_win.contiguous()), ptr(gate), ptr(jump), cos_min,
-                                               ptr(pose_in.contiguous()), ptr(out["n_pairs"]), ptr(out["sums"]), ptr(out["x"]),
-                                               ptr(out["status"]), ptr(out["pose_out"]), ptr(ws), nbytes, stream()),
+                                               ptr(intr_win.contiguous()), ptr(gate), ptr(jump), cos_min, ptr(pose_in),
+                                               ptr(out["n_pairs"]), ptr(out["sums"]), ptr(out["x"]), ptr(out["status"]),
+                                               ptr(out["pose_out"]), ptr(ws), nbytes, stream()),
                    "cloudaae_depth_align_step")
     return out
 
@@ -100,15 +121,10 @@ def edge_nearest(depth_test, frame_of, origin, wh, ww, step, radius):
     step [B] int32 in depth units (device); 1 <= radius <= 32.  -> nearest [B,wh,ww] int32 on the device: -1, or (mask_obs <<
     16) | ((j + radius) << 8) | (i + radius) of the nearest observed occluding edge (u0 + x + i, v0 + y + j) of window pixel
     (x, y).  A sample whose frame_of lies outside [0, F) is all -1.  No read-back."""
-    dt = _depth(depth_test, "depth_test", 3)
-    F, H, W = (int(v) for v in dt.shape)
-    dev = dt.device
-    require(isinstance(frame_of, torch.Tensor) and frame_of.dim() == 1 and frame_of.numel() >= 1, "frame_of must be [B], B >= 1")
-    B, wh, ww, radius = int(frame_of.numel()), int(wh), int(ww), int(radius)
-    require(wh >= 1 and ww >= 1, "wh and ww must be >= 1")
+    dt, _, (F, H, W, B, wh, ww), dev, frame_of, origin, (step,) = _window_inputs(depth_test, frame_of, origin, (("step", step),),
+                                                                               size=(wh, ww))
+    radius = int(radius)
     require(1 <= radius <= MAX_RADIUS, "radius must lie in [1, %d]" % MAX_RADIUS)
-    frame_of, step = _int32(frame_of, "frame_of", (B,), dev), _int32(step, "step", (B,), dev)
-    origin = _int32(origin, "origin", (B, 2), dev)
     nearest = _lib.empty((B, wh, ww), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().cloudaae_depth_edge_nearest(F, H, W, ptr(dt), B, ptr(frame_of), ptr(origin), wh, ww, ptr(step), radius,
@@ -120,17 +136,11 @@ def contour_sums(depth_test, frame_of, origin, depth_hyp, intr_win, gate, step, 
     """cloudaae_depth_contour_sums.  The arguments of align_step without jump and cos_min, plus step [B] int32 in depth units,
     the radius and the nearest [B,wh,ww] int32 of edge_nearest for the same frames, origins, step and radius.  -> dict of
     n_rows [B] int32 (two per contour pair) and sums [B,28] float64 in align_step's layout, on the device.  No read-back."""
-    dt, dh = _depth(depth_test, "depth_test", 3), _depth(depth_hyp, "depth_hyp", 3)
-    F, H, W = (int(v) for v in dt.shape)
-    B, wh, ww = (int(v) for v in dh.shape)
-    dev, radius = dt.device, int(radius)
-    require(B >= 1 and wh >= 1 and ww >= 1, "depth_hyp must be [B, wh, ww], none of them 0")
-    require(dh.device == dev, "all inputs must be on one device")
+    dt, dh, (F, H, W, B, wh, ww), dev, frame_of, origin, (gate, step) = _window_inputs(
+        depth_test, frame_of, origin, (("gate", gate), ("step", step)), depth_hyp=depth_hyp, intr_win=intr_win)
+    radius = int(radius)
     require(1 <= radius <= MAX_RADIUS, "radius must lie in [1, %d]" % MAX_RADIUS)
-    frame_of, gate, step = (_int32(t, n, (B,), dev) for t, n in ((frame_of, "frame_of"), (gate, "gate"), (step, "step")))
-    origin, nearest = _int32(origin, "origin", (B, 2), dev), _int32(nearest, "nearest", (B, wh, ww), dev)
-    require(isinstance(intr_win, torch.Tensor) and intr_win.dtype == torch.float32 and tuple(intr_win.shape) == (B, 5) and
-            intr_win.device == dev, "intr_win must be a float32 [B, 5] tensor on the inputs' device")
+    nearest = _int32(nearest, "nearest", (B, wh, ww), dev)
     L = _lib.lib()
     nbytes = int(L.cloudaae_depth_contour_sums_workspace_bytes(B, wh, ww))
     require(nbytes > 0, "outside the limits: wh ww <= 2^24, B wh ww <= 2^28")
@@ -158,16 +168,15 @@ def solve_sums(plane, contour, weight, pose_in):
             "contour sums must be float64 [B, 28] on the plane sums' device")
     n_pairs, st, n_rows = (_int32(t, n, (B,), dev) for t, n in ((plane["n_pairs"], "n_pairs"), (plane["status"], "status"),
                                                                (contour["n_rows"], "n_rows")))
-    require(isinstance(pose_in, torch.Tensor) and pose_in.dtype == torch.float64 and pose_in.numel() == 16 * B and
-            pose_in.device == dev, "pose_in must be a float64 [B, 4, 4] tensor on the inputs' device")
+    pose_in = _pose_in(pose_in, B, dev)
     weight = float(weight)
     require(weight == weight, "weight must be a number")
     out = dict(x=_lib.empty((B, 6), dtype=torch.float64, device=dev), status=_lib.empty((B,), dtype=torch.int32, device=dev),
                pose_out=_lib.empty((B, 4, 4), dtype=torch.float64, device=dev))
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().cloudaae_depth_align_solve(B, ptr(ps.contiguous()), ptr(n_pairs), ptr(st), ptr(cs.contiguous()),
-                                                         ptr(n_rows), weight, ptr(pose_in.contiguous()), ptr(out["x"]),
-                                                         ptr(out["status"]), ptr(out["pose_out"]), stream()),
+                                                         ptr(n_rows), weight, ptr(pose_in), ptr(out["x"]), ptr(out["status"]),
+                                                         ptr(out["pose_out"]), stream()),
                    "cloudaae_depth_align_solve")
     return out
 

@@ -222,6 +222,48 @@ def test_two_runs_and_the_batch_give_the_same_bits(track, dev, cases):
             assert alone[k][0].tobytes() == a[k][i].tobytes(), (k, i)
 
 
+def test_solve_statuses_on_hand_made_sums(track, dev):
+    """Every status of the shared solve from hand-made sums (1, A's upper triangle by rows, b), status 3 -- a solution that is
+    not finite -- among them, which no image of the other tests reaches.  Eight rows with n_pairs = 6, n_rows = 0 and plane
+    status 0, then three rows on the good sums that the counts and the plane status decide; the eight alone must give the
+    same bits as inside the eleven."""
+    good, b0 = np.diag(np.arange(1.0, 7.0)) + 0.1, np.arange(1.0, 7.0) * 1e-3
+    edit = lambda a, at, v: np.where(np.isin(np.arange(a.size).reshape(a.shape), at), v, a)
+    table = [(good, b0, 0), (np.zeros((6, 6)), b0, 2), (np.diag([1.0, 1.0, -1.0, 1.0, 1.0, 1.0]), b0, 2),
+             (edit(good, [0], np.inf), b0, 2), (edit(good, [1, 6], np.nan), b0, 2), (np.ones((6, 6)), b0, 2),
+             (good, edit(b0, [2], np.nan), 3), (good, edit(b0, [5], np.inf), 3)]
+    table += [(good, b0, 1), (good, b0, 0), (good, b0, 4)]
+    sums = np.array([np.concatenate([[1.0], A[np.triu_indices(6)], b]) for A, b, _ in table])
+    n_pairs = np.array([6] * 8 + [5, 3, 6], np.int32)
+    n_rows = np.array([0] * 8 + [0, 3, 0], np.int32)
+    plane_status = np.array([0] * 8 + [0, 0, 4], np.int32)
+    expected = np.array([st for _, _, st in table], np.int32)
+    pose_in = np.tile(TR.update_matrix([0.3, -0.2, 0.5, 0.1, -0.05, 0.9]), (len(table), 1, 1))
+
+    def gpu(contour, weight, B):
+        plane = dict(sums=torch.from_numpy(sums[:B]).to(dev), n_pairs=_i32(n_pairs[:B], dev), status=_i32(plane_status[:B], dev))
+        con = dict(sums=torch.from_numpy(np.ascontiguousarray(contour[:B])).to(dev), n_rows=_i32(n_rows[:B], dev))
+        out = track.solve_sums(plane, con, weight, torch.from_numpy(pose_in[:B].copy()).to(dev))
+        torch.cuda.synchronize()
+        return {k: v.cpu().numpy() for k, v in out.items()}
+    for contour, weight in ((np.zeros_like(sums), 0.0), (sums, 0.5)):
+        with np.errstate(all='ignore'):
+            want = CR.solve_sums(sums, n_pairs, plane_status, contour, n_rows, weight, pose_in)
+        got, eight = gpu(contour, weight, len(table)), gpu(contour, weight, 8)
+        print("weight %g: status %s (restatement %s)" % (weight, got['status'], want['status']))
+        assert np.array_equal(want['status'], expected) and np.array_equal(got['status'], want['status'])
+        for b in range(len(table)):
+            if expected[b] == 0:
+                print("row %d: x within %.3g, pose within %.3g" % (b, np.abs(got['x'][b] - want['x'][b]).max(),
+                                                                   np.abs(got['pose_out'][b] - want['pose_out'][b]).max()))
+                assert np.abs(got['x'][b] - want['x'][b]).max() <= POSE_TOL
+                assert np.abs(got['pose_out'][b] - want['pose_out'][b]).max() <= POSE_TOL
+            else:
+                assert got['pose_out'][b].tobytes() == pose_in[b].tobytes() and np.all(got['x'][b] == 0.0), b
+        for k in got:
+            assert eight[k].tobytes() == got[k][:8].tobytes(), k
+
+
 def test_errors_launch_nothing(hip, dev):
     L = hip.lib()
     d = torch.zeros(64, dtype=torch.int64, device=dev)
