@@ -168,6 +168,10 @@ _SIGNATURES = {
     "cloudaae_tsdf_count": [_I, _I, _I, _P, _I, _P, _P],
     "cloudaae_tsdf_emit": [_I, _I, _I, _D, _D, _D, _D, _P, _I, _P, _L, _P, _P, _P],
     "cloudaae_tsdf_raycast": [_I, _I, _I, _D, _D, _D, _D, _P, _I, _I, _I, _I, _P, _P, _D, _D, _P, _P],
+    "cloudaae_mesh_cluster_keys": [_I, _P, _D, _D, _D, _D, _I, _I, _I, _P, _P],
+    "cloudaae_mesh_cluster_sums": [_I, _I, _P, _P, _I, _P, _P, _D, _D, _D, _D, _P, _L, _P, _P, _L, _P, _P, _P, _P],
+    "cloudaae_mesh_cluster_place": [_I, _P, _P, _P, _D, _D, _D, _D, _D, _P, _P, _P, _P],
+    "cloudaae_mesh_cluster_triangles": [_I, _I, _P, _P, _I, _P, _P],
 }
 
 

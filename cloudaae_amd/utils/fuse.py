@@ -12,6 +12,7 @@ DESIGN.md ("Fused models").
     mesh_models.write_ply("model.ply", vertices, triangles)
 
     python -m cloudaae_amd.utils.fuse --files REC_pcnn.tfrecord --target_cls C --voxel 0.002 --out model.ply [--every N]
+        [--simplify METRES]
 """
 import argparse
 
@@ -147,12 +148,17 @@ def weld(tri_pos, tri_key):
     return tri_pos.reshape(-1, 3)[first].to(torch.float32), inverse.reshape(T, 3).to(torch.int32)
 
 
-def extract_mesh(volume, min_count=1):
+def extract_mesh(volume, min_count=1, simplify=None):
     """-> (vertices [V,3] float32, triangles [T,3] int32) on the device: what mesh_models.pack_meshes takes as a mesh.  An
     empty surface gives two empty tensors.  Surfaces no view saw stay open; zero-area triangles (a vertex exactly on a voxel
-    centre) are kept."""
+    centre) are kept.  simplify: a cell side in metres -- the mesh goes through simplify.simplify_mesh with its defaults
+    ("Simplified meshes"); None: the mesh as cut."""
     pos, key, _ = extract_triangles(volume, min_count)
-    return weld(pos, key)
+    vertices, triangles = weld(pos, key)
+    if simplify is not None:
+        from .simplify import simplify_mesh
+        vertices, triangles = simplify_mesh(vertices, triangles, simplify)
+    return vertices, triangles
 
 
 def used_points_aabb(depth, label, intrinsics, poses, want):
@@ -180,17 +186,18 @@ def used_points_aabb(depth, label, intrinsics, poses, want):
     return box
 
 
-def fuse_frames(depth, label, intrinsics, poses, want, voxel, aabb=None, min_count=1, front=None, behind=None, z_near=render.Z_NEAR):
+def fuse_frames(depth, label, intrinsics, poses, want, voxel, aabb=None, min_count=1, front=None, behind=None, z_near=render.Z_NEAR,
+                simplify=None):
     """One object from F posed frames: the volume around `aabb` (default: the box of the used pixels back-projected into the
-    object's frame, one read-back), all frames integrated, the mesh extracted.  label and want may both be None.  -> (vertices
-    [V,3] float32, triangles [T,3] int32, volume)."""
+    object's frame, one read-back), all frames integrated, the mesh extracted (simplify: as in extract_mesh).  label and want
+    may both be None.  -> (vertices [V,3] float32, triangles [T,3] int32, volume)."""
     dev = torch.device("cuda", torch.cuda.current_device()) if not isinstance(depth, torch.Tensor) else depth.device
     dt, intr, pose, lab, wnt = _frames(dev, depth, intrinsics, poses, label, want)
     if aabb is None:
         aabb = used_points_aabb(dt, lab, intr, pose, wnt)
     volume = volume_for(aabb, voxel, device=dev)
     integrate(volume, dt, intr, pose, lab, wnt, front=front, behind=behind, z_near=z_near)
-    vertices, triangles = extract_mesh(volume, min_count)
+    vertices, triangles = extract_mesh(volume, min_count, simplify)
     return vertices, triangles, volume
 
 
@@ -222,6 +229,7 @@ def main(argv=None):
     parser.add_argument("--voxel", type=float, default=0.002, help="voxel side in metres")
     parser.add_argument("--out", required=True, help="the PLY file to write")
     parser.add_argument("--every", type=int, default=1, help="take every N-th frame")
+    parser.add_argument("--simplify", type=float, default=None, metavar="METRES", help="simplify the mesh on cells of this side")
     parser.add_argument("--gpu", type=int, default=0)
     args = parser.parse_args(argv)
     from .. import tfrecord_io
@@ -238,7 +246,8 @@ def main(argv=None):
     poses = np.tile(np.eye(4), (len(frames), 1, 1))
     for f, fr in enumerate(frames):
         poses[f, :3, :3], poses[f, :3, 3] = quat2mat(fr["quaternions"][c]), fr["translations"][c]
-    vertices, triangles, volume = fuse_frames(depth, label, intr, poses, np.full(len(frames), c + 1, np.int32), args.voxel)
+    vertices, triangles, volume = fuse_frames(depth, label, intr, poses, np.full(len(frames), c + 1, np.int32), args.voxel,
+                                              simplify=args.simplify)
     mesh_models.write_ply(args.out, vertices, triangles)
     print("%d frames into %d x %d x %d voxels of %g m" % ((len(frames),) + volume.dims + (volume.voxel,)))
     print("%d vertices, %d triangles, %d boundary edges, %d components written to %s" % (mesh_counts(vertices, triangles) + (args.out,)))

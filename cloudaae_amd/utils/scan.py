@@ -10,7 +10,7 @@ DESIGN.md ("Scanning").
     d = raycast(volume, poses, intr_win, wh, ww)                    # [B,wh,ww]: the volume seen from B poses
 
     python -m cloudaae_amd.utils.scan --files REC_pcnn.tfrecord --target_cls C --voxel 0.002 --out model.ply [--every N]
-        [--motion velocity]
+        [--motion velocity] [--simplify METRES]
 """
 import argparse
 
@@ -62,9 +62,10 @@ class Scan(object):
     keeps the last good pose); num, den [F]: the silhouette rule's fraction of the frame's attempt (0 / 1 for frame 0);
     n_pairs, status [F]: of the attempt's last step; lost [F] bool, all numpy; volume: the fuse.Volume, on the device."""
 
-    def mesh(self):
-        """fuse.extract_mesh(volume, min_count) -> (vertices [V,3] float32, triangles [T,3] int32) on the device."""
-        return fuse.extract_mesh(self.volume, self.min_count)
+    def mesh(self, simplify=None):
+        """fuse.extract_mesh(volume, min_count, simplify) -> (vertices [V,3] float32, triangles [T,3] int32) on the device;
+        simplify: a cell side in metres, or None for the mesh as cut."""
+        return fuse.extract_mesh(self.volume, self.min_count, simplify)
 
 
 def _first_pose(dt, lab, intr, want):
@@ -187,6 +188,7 @@ def main(argv=None):
     parser.add_argument("--out", required=True, help="the PLY file to write")
     parser.add_argument("--every", type=int, default=1, help="take every N-th frame")
     parser.add_argument("--motion", choices=["constant", "velocity"], default="constant")
+    parser.add_argument("--simplify", type=float, default=None, metavar="METRES", help="simplify the mesh on cells of this side")
     parser.add_argument("--gpu", type=int, default=0)
     args = parser.parse_args(argv)
     from .. import tfrecord_io
@@ -205,7 +207,7 @@ def main(argv=None):
     # only the first pose is used; the others are what the printed errors are measured against
     s = scan_object(depth, intr, args.voxel, label=label, want=np.full(len(frames), c + 1, np.int32), first_pose=truth[0],
                     motion=args.motion)
-    vertices, triangles = s.mesh()
+    vertices, triangles = s.mesh(args.simplify)
     mesh_models.write_ply(args.out, vertices, triangles)
     for f, fr in enumerate(frames):
         rot, trans = track.pose_errors(s.poses[f], truth[f])

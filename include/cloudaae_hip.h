@@ -1549,6 +1549,59 @@ int cloudaae_tsdf_raycast(int nx, int ny, int nz, double ox, double oy, double o
                           int B, int wh, int ww, const float *intr_win, const double *poses, double step, double z_near,
                           uint16_t *depth_out, cloudaae_stream_t stream);
 
+/* ---- simplified meshes: uniform vertex clustering with quadric-error placement ("Simplified meshes") ---- */
+
+/* Shared by the four entries below.  The grid has nx x ny x nz cells of side `cell` with its low corner at (ox, oy, oz); the
+ * centre of cell (gx, gy, gz) is z = o + (g + 0.5) cell per axis and its key (gz ny + gy) nx + gx.  vertices [V,3] float,
+ * triangles [T,3] int.  The cells of a mesh are the distinct keys >= 0 of its vertices in ascending order, a cell's position in
+ * that order is its rank; rank [V] int holds every vertex's, -1 for an unused vertex; cell_grid [C,3] int holds (gx, gy, gz)
+ * per cell.  A triangle is dropped when an index lies outside [0, V) or a corner's rank is < 0.  All arithmetic is float64 on
+ * exactly widened values, un-fused, in the order written; comparisons in float64 before any conversion.  Limits: 0 <= V, T <
+ * 2^31 / 3; 0 <= C <= 2^21; the origin finite, cell (and eps) finite and > 0; 1 <= nx, ny, nz <= 2^20.  Outside them, or with
+ * a null required pointer, a call returns an error, launches nothing and leaves its outputs untouched; V = 0 (keys), C = 0
+ * (sums, place) and T = 0 (triangles) launch nothing and succeed. */
+
+/* key [V] long long: per axis g = floor((p - o) / cell); the vertex's key when 0 <= g < n on every axis (a NaN or an infinity
+ * fails: a vertex exactly on a cell's upper plane belongs to the next cell, one on the grid's far plane is outside), else -1.
+ * One launch, a lane per vertex. */
+int cloudaae_mesh_cluster_keys(int V, const float *vertices, double ox, double oy, double oz, double cell, int nx, int ny, int nz,
+                               long long *key, cloudaae_stream_t stream);
+
+/* The sums of every cell.  sums [C,16] double: m [0:3] = sum of q = p - z over the cell's vertices; then over every corner (t,
+ * k) of a triangle that is not dropped whose vertex lies in the cell, with q_i = p_i - z of the triangle's three vertices, u =
+ * q_1 - q_0, w = q_2 - q_0, n = u x w (n_0 = u_1 w_2 - u_2 w_1, ...), d = -((n_0 q_00 + n_1 q_01) + n_2 q_02): A [3:9] += (n_0
+ * n_0, n_0 n_1, n_0 n_2, n_1 n_1, n_1 n_2, n_2 n_2), b [9:12] += n d, e [12] += d d; [13:16] are written as zeros.  counts
+ * [C,2] int: the vertices and the corners added.  vert_order [n_vert_order] int: vertices grouped by rank, ascending index
+ * inside a group, the group of cell r at [vert_start[r], vert_start[r + 1]); corner_order [n_corner_order] int, corner_start
+ * alike for the corners 3 t + k; vert_start, corner_start [C + 1] long long.  A range is cut to its list; an entry that is out
+ * of range, or whose vertex (corner) does not belong to the cell, or whose triangle is dropped, is skipped: bad lists read
+ * nothing outside the arrays.  n_vert_order <= V, n_corner_order <= 3 T.  A cell's additions: lane l of the cell's wave takes
+ * the entries l, l + 64, ... of each range in order, then the 64 lanes meet in a fixed butterfly -- the order follows from the
+ * cell's two lists alone.  One launch, a wave per cell, no atomics. */
+int cloudaae_mesh_cluster_sums(int V, int T, const float *vertices, const int *triangles, int C, const int *rank,
+                               const int *cell_grid, double ox, double oy, double oz, double cell, const int *vert_order,
+                               long long n_vert_order, const long long *vert_start, const int *corner_order,
+                               long long n_corner_order, const long long *corner_start, double *sums, int *counts,
+                               cloudaae_stream_t stream);
+
+/* The vertex of every cell.  mean = m / n_v.  A is eigen-decomposed by 8 sweeps of cyclic Jacobi over the pairs (0,1), (0,2),
+ * (1,2); a rotation of (p, q) does nothing when a_pq == 0, else theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| +
+ * sqrt(theta theta + 1)), c = 1 / sqrt(t t + 1), s = t c; a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0, (a_rp, a_rq) = (c a_rp - s
+ * a_rq, s a_rp + c a_rq) and the same for every row of V.  lam_max is the largest diagonal entry; unless all three are finite
+ * and lam_max > 0: x = mean, how = 4.  Else r = -b - A mean, x = mean, and for i = 0, 1, 2 with lam_i > eps lam_max: x += v_i
+ * ((v_i . r) / lam_i); how = the number of those; if some |x_a| > cell / 2 or x is not finite: x = mean, how += 4.  pos [C,3]
+ * double = z + x; how [C] uint8; err [C] double = ((A x) . x + 2 (b . x)) + e, every dot product (t0 + t1) + t2.  One launch, a
+ * lane per cell. */
+int cloudaae_mesh_cluster_place(int C, const double *sums, const int *counts, const int *cell_grid, double ox, double oy,
+                                double oz, double cell, double eps, double *pos, uint8_t *how, double *err,
+                                cloudaae_stream_t stream);
+
+/* tri_key [T] long long: -1 when the triangle is dropped, a corner's rank lies outside [0, C), or two of its three ranks are
+ * equal; else the ranks rotated so that the smallest comes first (the orientation stays), packed as (r_a 2^21 + r_b) 2^21 +
+ * r_c.  One launch, a lane per triangle. */
+int cloudaae_mesh_cluster_triangles(int V, int T, const int *triangles, const int *rank, int C, long long *tri_key,
+                                    cloudaae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
