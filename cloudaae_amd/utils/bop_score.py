@@ -16,6 +16,7 @@ import torch
 
 from .. import _lib
 from .._lib import ptr, require, stream
+from .frame_inputs import check_depth, check_poses
 from .icp import _points
 
 VSD_DELTA = 0.015                                        # metres
@@ -25,22 +26,12 @@ MSPD_PIXELS = tuple(5.0 * j for j in range(1, 11))       # times width / 640
 MAX_TAUS = 16
 
 
-_DEPTH_TYPES = (torch.int16,) + ((torch.uint16,) if hasattr(torch, "uint16") else ())
-
-
-def _depth(t, name, dims):
-    require(isinstance(t, torch.Tensor) and t.dim() == dims and t.dtype in _DEPTH_TYPES,
-            "%s must be an int16 (the uint16 bits, as render_frames returns them) or uint16 tensor of %d dimensions"
-            % (name, dims))
-    return t.contiguous()
-
-
 def vsd_counts(depth_test, intrinsics, frame_of, depth_gt, depth_est, delta, taus, check_frames=True):
     """cloudaae_vsd_counts.  depth_test [F,H,W], depth_gt [B,H,W], depth_est [B,P,H,W]: int16 tensors holding the uint16
     bits (what render_frames returns) or uint16; intrinsics [F,5] float32; frame_of [B] int32 in [0, F) (checked here
     with one read-back unless check_frames is False: the kernel gives an entry outside zero counts); taus [B,K] float64
     in metres, K <= 16.  -> dict of inter, union [B,P], over [B,P,K], visib_gt [B] int32 on the device."""
-    dt, dg, de = _depth(depth_test, "depth_test", 3), _depth(depth_gt, "depth_gt", 3), _depth(depth_est, "depth_est", 4)
+    dt, dg, de = check_depth(depth_test, "depth_test", 3), check_depth(depth_gt, "depth_gt", 3), check_depth(depth_est, "depth_est", 4)
     F, H, W = (int(x) for x in dt.shape)
     B, P = int(de.shape[0]), int(de.shape[1])
     dev = dt.device
@@ -81,13 +72,6 @@ def vsd_errors(inter, union, over):
     return np.where(u == 0, 1.0, num / np.where(u == 0, 1.0, u))
 
 
-def _pose_tensor(t, name, dims, B, dev):
-    require(isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.dim() in dims and tuple(t.shape[-2:]) == (4, 4) and
-            int(t.shape[0]) == B and t.device == dev, "%s must be a float64 [B, %s4, 4] tensor on the inputs' device"
-            % (name, "P, " if 4 in dims else ""))
-    return t.contiguous()
-
-
 def vsd(meshes, mesh_index, est, gt, depth_test, intrinsics, frame_of, diameters, delta=VSD_DELTA, taus=VSD_TAUS,
         samples_per_launch=8):
     """VSD of the estimates est [B,P,4,4] (or [B,4,4]: P = 1) against the ground truth gt [B,4,4] (float64, model ->
@@ -103,12 +87,12 @@ def vsd(meshes, mesh_index, est, gt, depth_test, intrinsics, frame_of, diameters
     from . import mesh_models, render
     p = mesh_models.pack_meshes(meshes)
     dev = p.device
-    dt = _depth(depth_test, "depth_test", 3)
+    dt = check_depth(depth_test, "depth_test", 3)
     F, H, W = (int(x) for x in dt.shape)
     require(isinstance(gt, torch.Tensor) and gt.dim() == 3, "gt must be a float64 [B, 4, 4] tensor")
     B = int(gt.shape[0])
-    gt = _pose_tensor(gt, "gt", (3,), B, dev)
-    est = _pose_tensor(est, "est", (3, 4), B, dev)
+    gt = check_poses(gt, "gt", (3,), B, dev)
+    est = check_poses(est, "est", (3, 4), B, dev)
     P = int(est.shape[1]) if est.dim() == 4 else 1
     est = est.view(B, P, 16)
     mesh = np.asarray(mesh_index.cpu() if isinstance(mesh_index, torch.Tensor) else mesh_index, np.int64).reshape(-1)
@@ -189,8 +173,8 @@ def mssd_mspd(model_xyz, est, gt, intrinsics=None, symmetries=None):
     point lies at Z <= 0 under a pose), float64 on the device."""
     mp, mps, mcs, M = _points(model_xyz, "model_xyz")
     B, dev = int(model_xyz.shape[0]), model_xyz.device
-    gt = _pose_tensor(gt, "gt", (3,), B, dev)
-    est = _pose_tensor(est, "est", (3, 4), B, dev)
+    gt = check_poses(gt, "gt", (3,), B, dev)
+    est = check_poses(est, "est", (3, 4), B, dev)
     P = int(est.shape[1]) if est.dim() == 4 else 1
     if intrinsics is not None:
         require(isinstance(intrinsics, torch.Tensor) and intrinsics.dtype == torch.float32 and

@@ -16,6 +16,7 @@ import torch
 
 from .. import _lib
 from .._lib import ptr, require, stream
+from .frame_inputs import upload_depth, upload_intrinsics
 
 # choices, not measurements
 N_HYP = 256
@@ -39,21 +40,6 @@ class DepthSegments(object):
     uncut image, the components are those of fg_cut) and n_crease [F] (host, the same read-back)."""
 
 
-def _depth_tensor(depth, device):
-    if isinstance(depth, np.ndarray):
-        require(depth.dtype == np.uint16, "depth must be uint16")
-        return torch.from_numpy(np.ascontiguousarray(depth).view(np.int16)).to(device)   # the same bits
-    require(depth.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)), "depth must be uint16")
-    return depth.to(device).contiguous()
-
-
-def _intrinsics(intrinsics, device):
-    if isinstance(intrinsics, torch.Tensor):
-        require(intrinsics.dtype == torch.float32, "intrinsics must be float32")
-        return intrinsics.to(device).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(intrinsics, np.float32))).to(device)
-
-
 def jump_units(jump, factor_depth):
     """floor(jump * factor_depth + 0.5) in float64 per frame, as pose_verify's tau_units."""
     return np.array([int(math.floor(float(jump) * float(fd) + 0.5)) for fd in np.asarray(factor_depth).reshape(-1)], np.int32)
@@ -65,8 +51,8 @@ def find_creases(depth, fg, intrinsics, jump_units, step=STEP, smooth=SMOOTH, an
     n_crease [F] int32 (written into the given tensor when there is one) and smooth_map [F,H,W] int32 holding the bits of
     the kernel's uint32 (S << 8) | n.  angle is in degrees; cos(angle)^2 is formed here, once."""
     device = fg.device if isinstance(fg, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
-    d = _depth_tensor(depth, device)
-    intr = _intrinsics(intrinsics, device)
+    d = upload_depth(depth, device)
+    intr = upload_intrinsics(intrinsics, device)
     g = (fg if isinstance(fg, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(fg))).to(device).contiguous()
     ju = (jump_units if isinstance(jump_units, torch.Tensor)
           else torch.from_numpy(np.ascontiguousarray(jump_units, np.int32))).to(device).contiguous()
@@ -100,8 +86,8 @@ def segment_depth(depth, intrinsics, seed=0, first_frame=0, n_hyp=N_HYP, stride=
     creases: None (nothing changes), True (the defaults) or a dict with any of step, smooth, angle: find_creases runs after
     the foreground and the components are those of its fg_cut."""
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    d = _depth_tensor(depth, device)
-    intr = _intrinsics(intrinsics, device)
+    d = upload_depth(depth, device)
+    intr = upload_intrinsics(intrinsics, device)
     require(d.dim() == 3, "depth must be [F, H, W]")
     F, H, W = (int(v) for v in d.shape)
     require(tuple(intr.shape) == (F, 5), "intrinsics must be [F, 5]")
@@ -168,7 +154,7 @@ def match_components(found_label, other_label, depth, value):
     torch.bincount; the comparison is exact in integers (n_k union_j > n_j union_k, ties to the lowest k).  Returns
     (k [F] int64 numpy, 0 when nothing overlaps; iou [F] float64 numpy)."""
     device = found_label.device
-    d = _depth_tensor(depth, device)
+    d = upload_depth(depth, device)
     other = other_label if isinstance(other_label, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(other_label))
     other = other.to(device)
     F = int(found_label.shape[0])

@@ -15,8 +15,8 @@ import torch
 
 from .. import _lib
 from .._lib import ptr, require, stream
-from .bop_score import _depth
-from .pose_verify import COUNTERS, MODE_SEGMENT, MODE_SILHOUETTE, _fit_inputs, _int32, tau_units
+from .frame_inputs import check_depth, check_int32, upload_depth
+from .pose_verify import COUNTERS, MODE_SEGMENT, MODE_SILHOUETTE, _fit_inputs, tau_units
 
 # choices, not measurements
 MARGIN = 0.5              # of the component's box, added on either side
@@ -67,12 +67,12 @@ def fit_counts_window(depth_test, label, frame_of, want, origin, depth_hyp, tau)
     int32 (ignored without a label); origin [B,2] int32 = (u0, v0), any values; tau [B] int32 in depth units.  Window
     pixel (x, y) of sample b is frame pixel (u0 + x, v0 + y); outside the frame there is no depth and no segment.
     -> dict of counts [B,P,6] int32 (pose_verify.COUNTERS), seg_total [B] int32 and abs_sum [B,P] int64 on the device."""
-    dt, dh = _depth(depth_test, "depth_test", 3), _depth(depth_hyp, "depth_hyp", 4)
+    dt, dh = check_depth(depth_test, "depth_test", 3), check_depth(depth_hyp, "depth_hyp", 4)
     F, H, W = (int(x) for x in dt.shape)
     B, P, wh, ww = (int(x) for x in dh.shape)
     require(B >= 1 and P >= 1 and wh >= 1 and ww >= 1, "depth_hyp must be [B, P, wh, ww], none of them 0")
     label, frame_of, want, tau, out = _fit_inputs(dt, dh, label, frame_of, want, tau)
-    origin = _int32(origin, "origin", (B, 2), dt.device)
+    origin = check_int32(origin, "origin", (B, 2), dt.device)
     with torch.cuda.device(dt.device):
         _lib.check(_lib.lib().cloudaae_depth_fit_counts_window(F, H, W, ptr(dt), ptr(label), B, P, ptr(frame_of), ptr(want),
                                                                ptr(origin), wh, ww, ptr(dh), ptr(tau), ptr(out["counts"]),
@@ -91,11 +91,11 @@ def assign(counts, seg_total, valid, pose, n_components, mode=MODE_SEGMENT, min_
     F, K, C, P = (int(x) for x in counts.shape[:4])
     dev = counts.device
     require(K <= MAX_K and C <= MAX_C and P <= MAX_P, "at most %d components, %d classes and %d hypotheses" % (MAX_K, MAX_C, MAX_P))
-    seg_total = _int32(seg_total, "seg_total", (F, K, C), dev)
+    seg_total = check_int32(seg_total, "seg_total", (F, K, C), dev)
     if valid is None:
         valid = torch.ones((F, K, C, P), dtype=torch.int32, device=dev)
-    valid = _int32(valid, "valid", (F, K, C, P), dev)
-    n_components = _int32(n_components, "n_components", (F,), dev)
+    valid = check_int32(valid, "valid", (F, K, C, P), dev)
+    n_components = check_int32(n_components, "n_components", (F,), dev)
     require(isinstance(pose, torch.Tensor) and pose.dtype == torch.float64 and tuple(pose.shape) == (F, K, C, P, 4, 4) and
             pose.device == dev, "pose must be a float64 [F, K, C, P, 4, 4] tensor on the counts' device")
     num, den = int(min_score[0]), int(min_score[1])
@@ -128,7 +128,7 @@ def window_counts(segments, poses, meshes, mesh_of_class, intrinsics, depth, tau
     from . import mesh_models, render
     p = mesh_models.pack_meshes(meshes)
     dev = p.device
-    dt = _depth(depth, "depth", 3)
+    dt = check_depth(depth, "depth", 3)
     F, H, W = (int(x) for x in dt.shape)
     require(isinstance(poses, torch.Tensor) and poses.dim() == 6 and poses.dtype == torch.float64 and
             tuple(poses.shape[4:]) == (4, 4) and int(poses.shape[0]) == F and min(poses.shape) >= 1 and poses.device == dev,
@@ -307,7 +307,7 @@ def detect_objects(depth, intrinsics, meshes, ppf_models, classes=None, segments
     mesh_of_class = classes if mesh_of_class is None else [int(m) for m in mesh_of_class]
     if segments is None:
         segments = dc_util.segment_depth(depth, intrinsics, seed=seed, first_frame=first_frame, device=dev, **(components or {}))
-    d = dc_util._depth_tensor(depth, dev)
+    d = upload_depth(depth, dev)
     F = int(d.shape[0])
     n_comp = np.asarray(segments.n_components, np.int64).reshape(-1)
     K = max(int(n_comp.max()), 1)

@@ -22,6 +22,7 @@ import torch
 from .. import _lib
 from .._lib import ptr, require, stream
 from . import render
+from .frame_inputs import depth_frames, host, on_device
 
 # choices, not measurements on data
 FRONT_VOXELS = 4.0        # the truncation in front of a surface, and the deep band's far end behind it
@@ -54,7 +55,7 @@ class Volume(object):
 
 def volume_for(aabb, voxel, margin=MARGIN, device=None):
     """The Volume around a box aabb [2,3] (low and high corner, metres) with `margin` voxels on every side."""
-    box = np.asarray(aabb.detach().cpu() if isinstance(aabb, torch.Tensor) else aabb, np.float64)
+    box = host(aabb, np.float64)
     require(box.shape == (2, 3) and np.all(np.isfinite(box)) and np.all(box[1] >= box[0]), "aabb must be a finite [2, 3] box, low <= high")
     s, margin = float(voxel), int(margin)
     require(np.isfinite(s) and s > 0.0 and margin >= 0, "voxel must be positive and margin >= 0")
@@ -66,27 +67,19 @@ def volume_for(aabb, voxel, margin=MARGIN, device=None):
 
 def _frames(dev, depth, intrinsics, poses, label, want):
     """The frames of a call as contiguous tensors on `dev`, shapes checked: (depth, intr, poses, label or None, want or None)."""
-    from .bop_score import _depth
-    from . import depth_components as dc_util
-    dt = _depth(dc_util._depth_tensor(depth, dev) if isinstance(depth, np.ndarray) else depth, "depth", 3)
+    dt = depth_frames(depth, dev)
     require(dt.device == dev, "the frames must be on the volume's device")
     F = int(dt.shape[0])
     require(1 <= F <= MAX_FRAMES, "1 <= F <= 2^19 frames per call")
-
-    def tensor(x, dtype, shape, name):
-        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-        t = t.to(device=dev, dtype=dtype).contiguous()
-        require(tuple(t.shape) == shape, "%s must be %s" % (name, list(shape)))
-        return t
-    intr = tensor(intrinsics, torch.float32, (F, 5), "intrinsics")
-    pose = tensor(poses, torch.float64, (F, 4, 4), "poses")
+    intr = on_device(intrinsics, torch.float32, dev, (F, 5), "intrinsics")
+    pose = on_device(poses, torch.float64, dev, (F, 4, 4), "poses")
     require((label is None) == (want is None), "label and want come together")
     lab = wnt = None
     if label is not None:
         require(isinstance(label, np.ndarray) or label.dtype == torch.uint8, "label must be uint8")
-        lab = tensor(label, torch.uint8, tuple(dt.shape), "label")
-        wnt = tensor(np.asarray(want, np.int64).astype(np.int32) if not isinstance(want, torch.Tensor) else want, torch.int32,
-                     (F,), "want")
+        lab = on_device(label, torch.uint8, dev, tuple(dt.shape), "label")
+        wnt = on_device(np.asarray(want, np.int64).astype(np.int32) if not isinstance(want, torch.Tensor) else want, torch.int32, dev,
+                        (F,), "want")
     return dt, intr, pose, lab, wnt
 
 
@@ -222,6 +215,24 @@ def mesh_counts(vertices, triangles):
     return V, len(t), int((cnt == 1).sum()), len(np.unique(comp[used])) if len(used) else 0
 
 
+def class_frames(path, target_cls, every=1):
+    """One class of a <seq>_pcnn.tfrecord: every `every`-th frame of the file that shows the class, in file order -> (depth
+    [F,H,W] uint16, label [F,H,W] uint8, intrinsics [F,5] float32, the record's poses of the class [F,4,4] float64, the
+    frames' records)."""
+    from .. import tfrecord_io
+    from .track import quat2mat
+    require(every >= 1, "--every must be >= 1")
+    frames = [fr for fr in list(tfrecord_io.read_frames(path))[::every] if bool(fr["class_one_hot"][target_cls])]
+    require(len(frames) >= 1, "no frame of %s shows class %d" % (path, target_cls))
+    depth = np.stack([fr["depth"] for fr in frames])
+    label = np.stack([fr["label"] for fr in frames]).astype(np.uint8)
+    intr = np.array([[fr[k] for k in ("fx", "fy", "cx", "cy", "factor_depth")] for fr in frames], np.float32)
+    poses = np.tile(np.eye(4), (len(frames), 1, 1))
+    for f, fr in enumerate(frames):
+        poses[f, :3, :3], poses[f, :3, 3] = quat2mat(fr["quaternions"][target_cls]), fr["translations"][target_cls]
+    return depth, label, intr, poses, frames
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description="fuse one class of a <seq>_pcnn.tfrecord into a mesh from the record's labels and poses")
     parser.add_argument("--files", required=True, help="one <seq>_pcnn.tfrecord; its frames are taken in file order")
@@ -232,20 +243,10 @@ def main(argv=None):
     parser.add_argument("--simplify", type=float, default=None, metavar="METRES", help="simplify the mesh on cells of this side")
     parser.add_argument("--gpu", type=int, default=0)
     args = parser.parse_args(argv)
-    from .. import tfrecord_io
     from . import mesh_models
-    from .track import quat2mat
     torch.cuda.set_device(args.gpu)
-    require(args.every >= 1, "--every must be >= 1")
     c = args.target_cls
-    frames = [fr for fr in list(tfrecord_io.read_frames(args.files))[::args.every] if bool(fr["class_one_hot"][c])]
-    require(len(frames) >= 1, "no frame of %s shows class %d" % (args.files, c))
-    depth = np.stack([fr["depth"] for fr in frames])
-    label = np.stack([fr["label"] for fr in frames]).astype(np.uint8)
-    intr = np.array([[fr[k] for k in ("fx", "fy", "cx", "cy", "factor_depth")] for fr in frames], np.float32)
-    poses = np.tile(np.eye(4), (len(frames), 1, 1))
-    for f, fr in enumerate(frames):
-        poses[f, :3, :3], poses[f, :3, 3] = quat2mat(fr["quaternions"][c]), fr["translations"][c]
+    depth, label, intr, poses, frames = class_frames(args.files, c, args.every)
     vertices, triangles, volume = fuse_frames(depth, label, intr, poses, np.full(len(frames), c + 1, np.int32), args.voxel,
                                               simplify=args.simplify)
     mesh_models.write_ply(args.out, vertices, triangles)

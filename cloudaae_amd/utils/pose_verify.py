@@ -16,7 +16,7 @@ import torch
 
 from .. import _lib
 from .._lib import ptr, require, stream
-from .bop_score import _depth, _pose_tensor
+from .frame_inputs import check_depth, check_int32, check_poses
 
 COUNTERS = ("rendered", "consistent", "in_front", "behind", "unknown", "explained")      # the order of counts [..., 6]
 MODE_SEGMENT, MODE_SILHOUETTE = 0, 1
@@ -124,7 +124,7 @@ def compose(base, class_id, table, p=None):
     require(isinstance(table, HypothesisTable), "table must be a HypothesisTable")
     require(isinstance(base, torch.Tensor) and base.dim() == 3 and base.shape[0] >= 1, "base must be a float64 [B, 4, 4] tensor")
     B, dev = int(base.shape[0]), base.device
-    base = _pose_tensor(base, "base", (3,), B, dev)
+    base = check_poses(base, "base", (3,), B, dev)
     require(isinstance(class_id, torch.Tensor) and tuple(class_id.shape) == (B,) and class_id.device == dev,
             "class_id must be [B], on the poses' device")
     P = max(table.max_members, 1) if p is None else int(p)
@@ -142,12 +142,6 @@ def compose(base, class_id, table, p=None):
     return out
 
 
-def _int32(t, name, shape, dev):
-    require(isinstance(t, torch.Tensor) and t.dtype == torch.int32 and tuple(t.shape) == shape and t.device == dev,
-            "%s must be an int32 %s tensor on the inputs' device" % (name, list(shape)))
-    return t.contiguous()
-
-
 def _fit_inputs(dt, dh, label, frame_of, want, tau):
     """What fit_counts and detect.fit_counts_window share: the checks of label [F,H,W], want (None without a label),
     frame_of and tau [B] against the test frames dt [F,H,W] and the hypothesis images dh [B,P,..], and the outputs.
@@ -158,10 +152,10 @@ def _fit_inputs(dt, dh, label, frame_of, want, tau):
         require(isinstance(label, torch.Tensor) and label.dtype == torch.uint8 and label.shape == dt.shape and
                 label.device == dev, "label must be a uint8 [F, H, W] tensor on the inputs' device, or None")
         label = label.contiguous()
-        want = _int32(want, "want", (B,), dev)
+        want = check_int32(want, "want", (B,), dev)
     else:
         want = None
-    frame_of, tau = _int32(frame_of, "frame_of", (B,), dev), _int32(tau, "tau", (B,), dev)
+    frame_of, tau = check_int32(frame_of, "frame_of", (B,), dev), check_int32(tau, "tau", (B,), dev)
     out = {"counts": _lib.empty((B, P, len(COUNTERS)), dtype=torch.int32, device=dev),
            "seg_total": _lib.empty((B,), dtype=torch.int32, device=dev),
            "abs_sum": _lib.empty((B, P), dtype=torch.int64, device=dev)}
@@ -174,7 +168,7 @@ def fit_counts(depth_test, label, frame_of, want, depth_hyp, tau, check_frames=T
     read-back unless check_frames is False: the kernel gives an entry outside zero counts); want [B] int32 (ignored
     without a label); tau [B] int32 in depth units.  -> dict of counts [B,P,6] int32 (COUNTERS), seg_total [B] int32 and
     abs_sum [B,P] int64 on the device."""
-    dt, dh = _depth(depth_test, "depth_test", 3), _depth(depth_hyp, "depth_hyp", 4)
+    dt, dh = check_depth(depth_test, "depth_test", 3), check_depth(depth_hyp, "depth_hyp", 4)
     F, H, W = (int(x) for x in dt.shape)
     B, P = int(dh.shape[0]), int(dh.shape[1])
     require(tuple(dh.shape) == (B, P, H, W) and B >= 1 and P >= 1, "depth_hyp must be [B, P, H, W] with the test frames' H and W")
@@ -197,12 +191,12 @@ def select(counts, seg_total, valid, pose, mode=MODE_SEGMENT):
             counts.shape[2] == len(COUNTERS) and counts.shape[0] >= 1 and counts.shape[1] >= 1,
             "counts must be an int32 [B, P, 6] tensor")
     B, P, dev = int(counts.shape[0]), int(counts.shape[1]), counts.device
-    seg_total = _int32(seg_total, "seg_total", (B,), dev)
+    seg_total = check_int32(seg_total, "seg_total", (B,), dev)
     if valid is None:
         valid = torch.ones((B, P), dtype=torch.int32, device=dev)
     require(isinstance(valid, torch.Tensor) and valid.dtype == torch.int32 and tuple(valid.shape) == (B, P) and
             valid.device == dev, "valid must be an int32 [B, P] tensor on the counts' device")
-    pose = _pose_tensor(pose, "pose", (4,), B, dev)
+    pose = check_poses(pose, "pose", (4,), B, dev)
     require(int(pose.shape[1]) == P, "pose must hold P poses per sample")
     require(int(mode) in (MODE_SEGMENT, MODE_SILHOUETTE), "mode must be 0 (segment rule) or 1 (silhouette rule)")
     out = dict(best=_lib.empty((B,), dtype=torch.int32, device=dev), score=_lib.empty((B, P), dtype=torch.float64, device=dev),
@@ -237,11 +231,11 @@ def verify_poses(meshes, mesh_index, poses, depth_test, label, want, intrinsics,
     from . import mesh_models, render
     p = mesh_models.pack_meshes(meshes)
     dev = p.device
-    dt = _depth(depth_test, "depth_test", 3)
+    dt = check_depth(depth_test, "depth_test", 3)
     F, H, W = (int(x) for x in dt.shape)
     require(isinstance(poses, torch.Tensor) and poses.dim() == 4, "poses must be a float64 [B, P, 4, 4] tensor")
     B, P = int(poses.shape[0]), int(poses.shape[1])
-    poses = _pose_tensor(poses, "poses", (4,), B, dev)
+    poses = check_poses(poses, "poses", (4,), B, dev)
     mesh = np.asarray(mesh_index.cpu() if isinstance(mesh_index, torch.Tensor) else mesh_index, np.int64).reshape(-1)
     require(len(mesh) == B and mesh.min() >= 0 and mesh.max() < len(p.num_triangles), "mesh_index must be [B], inside the meshes")
     fo_host = np.asarray(frame_of.cpu() if isinstance(frame_of, torch.Tensor) else frame_of, np.int64).reshape(-1)

@@ -19,8 +19,8 @@ import torch
 
 from .. import _lib
 from .._lib import ptr, require, stream
-from . import detect, fuse, render, track
-from .bop_score import _depth
+from . import fuse, render, track
+from .frame_inputs import depth_frames, host, intrinsics_per_frame, on_device
 from .pose_verify import tau_units
 
 # a choice, not a measurement
@@ -36,11 +36,7 @@ def raycast(volume, poses, intr_win, wh, ww, step=None, min_count=1, z_near=rend
     0 where the ray meets no surface from known outside.  No read-back."""
     require(isinstance(volume, fuse.Volume), "volume must be a Volume")
     dev = volume.device
-
-    def tensor(x, dtype):
-        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-        return t.to(device=dev, dtype=dtype).contiguous()
-    pose, rows = tensor(poses, torch.float64), tensor(intr_win, torch.float32)
+    pose, rows = on_device(poses, torch.float64, dev), on_device(intr_win, torch.float32, dev)
     require(pose.dim() == 3 and tuple(pose.shape[1:]) == (4, 4) and int(pose.shape[0]) >= 1, "poses must be [B, 4, 4], B >= 1")
     B, wh, ww = int(pose.shape[0]), int(wh), int(ww)
     require(tuple(rows.shape) == (B, 5), "intr_win must be [B, 5]")
@@ -86,31 +82,31 @@ def scan_object(depth, intrinsics, voxel, label=None, want=None, first_pose=None
     first_pose (model -> camera; default no rotation and the centre of the used pixels' box) and aabb [2,3], the object's
     extent in that frame (default fuse.used_points_aabb of frame 0 grown on every side by `grow` times its largest side: one
     view sees only the front); the volume is fuse.volume_for(aabb, voxel) and is not resized later.  Frame 0 is integrated at
-    first_pose.  Every later frame starts from the last pose (motion='velocity': track.predict), takes track.pose_windows of
-    that pose and the box, runs `iterations` times raycast + track.align_step, raycasts once more at the final pose and
-    counts it with detect.fit_counts_window (tau in metres); the score is the silhouette rule's, and the frame is lost when
-    num min_den < min_num den or it has no window, as in track_objects.  A frame that is not lost is integrated at its pose;
+    first_pose.  Every later frame starts from the last pose (motion='velocity': track.predict) and is one track.frame_attempt
+    with the raycast of the volume as hypothesis source, the box as the window's box and the label handed to the counts:
+    `iterations` times raycast + track.align_step in the window of the start, one more raycast at the final pose, counted
+    with detect.fit_counts_window (tau in metres); the score is the silhouette rule's, and the frame is lost when num
+    min_den < min_num den or it has no window, as in track_objects.  A frame that is not lost is integrated at its pose;
     a lost one is not, the pose stays at the last good one and the next frame starts from it at rest.  Nothing is read back
     inside the iterations; one read-back per frame.  step: the raycast's, metres (default 0.5 voxel).  Two hooks for tests and
     tools: on_step(f, dict(pose_in, depth_hyp, pose_out, n_pairs, status: device tensors; origin, wh, ww, rows, frame_of:
     host)) after every step and on_frame(f, pose, volume) after every frame.  -> Scan."""
-    from . import depth_components as dc_util
     require(motion in ("constant", "velocity"), "motion must be 'constant' or 'velocity'")
     num_min, den_min = int(min_score[0]), int(min_score[1])
     require(0 <= num_min <= den_min and den_min >= 1, "min_score must be (num, den) with 0 <= num <= den, den >= 1")
     require(int(iterations) >= 0 and int(min_count) >= 1, "iterations must be >= 0 and min_count >= 1")
     dev = depth.device if isinstance(depth, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
-    dt = _depth(dc_util._depth_tensor(depth, dev) if isinstance(depth, np.ndarray) else depth, "depth", 3)
-    F, H, W = (int(v) for v in dt.shape)
-    intr = np.ascontiguousarray(np.broadcast_to(track._host(intrinsics, np.float32).reshape(-1, 5), (F, 5)))
+    dt = depth_frames(depth, dev)
+    F = int(dt.shape[0])
+    intr = intrinsics_per_frame(intrinsics, F)
     require((label is None) or (want is not None), "label and want come together")
     if label is not None:
-        want = np.ascontiguousarray(np.broadcast_to(track._host(want, np.int64).astype(np.int32).reshape(-1), (F,)))
+        want = np.ascontiguousarray(np.broadcast_to(host(want, np.int64).astype(np.int32).reshape(-1), (F,)))
     dt, intr_dev, _, lab, wnt = fuse._frames(dev, dt, intr, np.tile(np.eye(4), (F, 1, 1)), label, want if label is not None else None)
-    first = _first_pose(dt, lab, intr_dev, wnt) if first_pose is None else track._host(first_pose, np.float64).reshape(4, 4).copy()
+    first = _first_pose(dt, lab, intr_dev, wnt) if first_pose is None else host(first_pose, np.float64).reshape(4, 4).copy()
 
     def pose_tensor(T):
-        return torch.from_numpy(np.ascontiguousarray(T, np.float64).reshape(1, 4, 4)).to(dev)
+        return on_device(np.reshape(T, (1, 4, 4)), torch.float64, dev)
 
     def integrate(f, pose_dev):
         fuse.integrate(volume, dt[f:f + 1], intr_dev[f:f + 1], pose_dev, None if lab is None else lab[f:f + 1],
@@ -121,9 +117,12 @@ def scan_object(depth, intrinsics, voxel, label=None, want=None, first_pose=None
                                     None if lab is None else wnt[:1])
         side = float((box[1] - box[0]).max())
         aabb = np.stack([box[0] - float(grow) * side, box[1] + float(grow) * side])
-    aabb = track._host(aabb, np.float64).reshape(2, 3)
+    aabb = host(aabb, np.float64).reshape(2, 3)
     volume = fuse.volume_for(aabb, voxel, device=dev)
     step = STEP_VOXELS * volume.voxel if step is None else float(step)
+
+    def cast(pose, rows, wh, ww):
+        return raycast(volume, pose, rows, wh, ww, step, min_count)
 
     s = Scan()
     s.volume, s.min_count, s.aabb = volume, int(min_count), aabb
@@ -137,43 +136,17 @@ def scan_object(depth, intrinsics, voxel, label=None, want=None, first_pose=None
     last, before = first.copy(), None
     for f in range(1, F):
         start = track.predict(last, before, motion)
-        origin, wh, ww, ok = track.pose_windows(start[None], aabb[None], intr[f][None], H, W, margin)
-        rows_host = intr[f][None].copy()
-        rows_host[:, 2] = intr[f, 2] - origin[:, 0].astype(np.float32)
-        rows_host[:, 3] = intr[f, 3] - origin[:, 1].astype(np.float32)
-        factor = np.array([intr[f, 4]], np.float64)
-        units = [int(tau_units(np.array([q], np.float64), factor)[0]) for q in (gate, jump, tau)]
-        # one upload of the integers: the frame (or -1 without a window), gate, jump, tau, the origin, want
-        ints = torch.from_numpy(np.array([[f if ok[0] else -1] + units + [int(origin[0, 0]), int(origin[0, 1]),
-                                                                          int(want[f]) if lab is not None else 0]], np.int32)).to(dev)
-        frame_dev, gate_dev, jump_dev, tau_dev = (ints[:, c].contiguous() for c in range(4))
-        org, want_dev = ints[:, 4:6].contiguous(), ints[:, 6].contiguous()
-        rows = torch.from_numpy(np.ascontiguousarray(rows_host)).to(dev)
-        pose = pose_tensor(start)
-        n_pairs = torch.zeros((1,), dtype=torch.int32, device=dev)
-        status = torch.zeros((1,), dtype=torch.int32, device=dev)
-        for _ in range(int(iterations)):
-            d = raycast(volume, pose, rows, wh, ww, step, min_count)
-            r = track.align_step(dt, frame_dev, org, d, rows, gate_dev, jump_dev, cos_min, pose)
-            if on_step is not None:
-                on_step(f, dict(pose_in=pose, depth_hyp=d, pose_out=r["pose_out"], n_pairs=r["n_pairs"], status=r["status"],
-                                origin=origin, wh=wh, ww=ww, rows=rows_host, frame_of=f if ok[0] else -1))
-            pose, n_pairs, status = r["pose_out"], r["n_pairs"], r["status"]
-        d = raycast(volume, pose, rows, wh, ww, step, min_count)
-        c = detect.fit_counts_window(dt, lab, frame_dev, want_dev if lab is not None else None, org, d.view(1, 1, wh, ww), tau_dev)
-        # the one read-back: the pose as its bits, the counters, the last step's pairs and status
-        host = torch.cat([pose.contiguous().view(torch.int32).reshape(-1), c["counts"].reshape(-1), n_pairs, status]).cpu().numpy()
-        final = host[:32].copy().view(np.float64).reshape(4, 4)
-        counts = host[32:38].astype(np.int64)
-        num, den = int(counts[1]), int(counts[1] + counts[2] + counts[3])
-        num, den = (num, den) if den > 0 else (0, 1)
-        lost = (not ok[0]) or (num * den_min < num_min * den)
-        if lost:
+        tau_u = tau_units(np.array([tau], np.float64), intr[f:f + 1, 4].astype(np.float64))[0]
+        pose, num, den, n_pairs, status, lost, pose_dev = track.frame_attempt(
+            dev, dt, intr, f, aabb[None], start[None], cast, tau_u, (num_min, den_min), lab, None if lab is None else wnt[f:f + 1],
+            iterations=iterations, gate=gate, jump=jump, cos_min=cos_min, margin=margin,
+            on_step=None if on_step is None else lambda info: on_step(f, dict(info, frame_of=int(info["frame_of"][0]))))
+        if lost[0]:
             before = None
         else:
-            before, last = last.copy(), final
-            integrate(f, pose)
-        s.poses[f], s.num[f], s.den[f], s.n_pairs[f], s.status[f], s.lost[f] = last, num, den, host[38], host[39], lost
+            before, last = last.copy(), pose[0]
+            integrate(f, pose_dev)
+        s.poses[f], s.num[f], s.den[f], s.n_pairs[f], s.status[f], s.lost[f] = last, num[0], den[0], n_pairs[0], status[0], lost[0]
         if on_frame is not None:
             on_frame(f, last, volume)
     return s
@@ -191,19 +164,10 @@ def main(argv=None):
     parser.add_argument("--simplify", type=float, default=None, metavar="METRES", help="simplify the mesh on cells of this side")
     parser.add_argument("--gpu", type=int, default=0)
     args = parser.parse_args(argv)
-    from .. import tfrecord_io
     from . import mesh_models
     torch.cuda.set_device(args.gpu)
-    require(args.every >= 1, "--every must be >= 1")
     c = args.target_cls
-    frames = [fr for fr in list(tfrecord_io.read_frames(args.files))[::args.every] if bool(fr["class_one_hot"][c])]
-    require(len(frames) >= 1, "no frame of %s shows class %d" % (args.files, c))
-    depth = np.stack([fr["depth"] for fr in frames])
-    label = np.stack([fr["label"] for fr in frames]).astype(np.uint8)
-    intr = np.array([[fr[k] for k in ("fx", "fy", "cx", "cy", "factor_depth")] for fr in frames], np.float32)
-    truth = np.tile(np.eye(4), (len(frames), 1, 1))
-    for f, fr in enumerate(frames):
-        truth[f, :3, :3], truth[f, :3, 3] = track.quat2mat(fr["quaternions"][c]), fr["translations"][c]
+    depth, label, intr, truth, frames = fuse.class_frames(args.files, c, args.every)
     # only the first pose is used; the others are what the printed errors are measured against
     s = scan_object(depth, intr, args.voxel, label=label, want=np.full(len(frames), c + 1, np.int32), first_pose=truth[0],
                     motion=args.motion)

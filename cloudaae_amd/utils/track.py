@@ -21,9 +21,9 @@ import torch
 
 from .. import _lib
 from .._lib import ptr, require, stream
-from . import detect
-from .bop_score import _depth
-from .pose_verify import _int32, tau_units
+from . import detect, mesh_models, render
+from .frame_inputs import check_depth, check_int32, depth_frames, host, intrinsics_per_frame
+from .pose_verify import tau_units
 
 # choices, not measurements
 ITERATIONS = 4
@@ -48,10 +48,10 @@ def _window_inputs(depth_test, frame_of, origin, columns, depth_hyp=None, size=N
     """The window bindings' common inputs, checked: depth_test [F,H,W]; depth_hyp [B,wh,ww], or size = (wh, ww) with B from
     frame_of; frame_of and the columns ((name, tensor), ...) int32 [B]; origin int32 [B,2]; intr_win, when given, float32 [B,5];
     one device.  -> (dt, dh or None, (F, H, W, B, wh, ww), device, frame_of, origin, [columns])."""
-    dt = _depth(depth_test, "depth_test", 3)
+    dt = check_depth(depth_test, "depth_test", 3)
     dev = dt.device
     if depth_hyp is not None:
-        dh = _depth(depth_hyp, "depth_hyp", 3)
+        dh = check_depth(depth_hyp, "depth_hyp", 3)
         B, wh, ww = (int(v) for v in dh.shape)
         require(B >= 1 and wh >= 1 and ww >= 1, "depth_hyp must be [B, wh, ww], none of them 0")
         require(dh.device == dev, "all inputs must be on one device")
@@ -59,9 +59,9 @@ def _window_inputs(depth_test, frame_of, origin, columns, depth_hyp=None, size=N
         require(isinstance(frame_of, torch.Tensor) and frame_of.dim() == 1 and frame_of.numel() >= 1, "frame_of must be [B], B >= 1")
         dh, B, wh, ww = None, int(frame_of.numel()), int(size[0]), int(size[1])
         require(wh >= 1 and ww >= 1, "wh and ww must be >= 1")
-    frame_of = _int32(frame_of, "frame_of", (B,), dev)
-    columns = [_int32(t, n, (B,), dev) for n, t in columns]
-    origin = _int32(origin, "origin", (B, 2), dev)
+    frame_of = check_int32(frame_of, "frame_of", (B,), dev)
+    columns = [check_int32(t, n, (B,), dev) for n, t in columns]
+    origin = check_int32(origin, "origin", (B, 2), dev)
     if intr_win is not None:
         require(isinstance(intr_win, torch.Tensor) and intr_win.dtype == torch.float32 and tuple(intr_win.shape) == (B, 5) and
                 intr_win.device == dev, "intr_win must be a float32 [B, 5] tensor on the inputs' device")
@@ -140,7 +140,7 @@ def contour_sums(depth_test, frame_of, origin, depth_hyp, intr_win, gate, step, 
         depth_test, frame_of, origin, (("gate", gate), ("step", step)), depth_hyp=depth_hyp, intr_win=intr_win)
     radius = int(radius)
     require(1 <= radius <= MAX_RADIUS, "radius must lie in [1, %d]" % MAX_RADIUS)
-    nearest = _int32(nearest, "nearest", (B, wh, ww), dev)
+    nearest = check_int32(nearest, "nearest", (B, wh, ww), dev)
     L = _lib.lib()
     nbytes = int(L.cloudaae_depth_contour_sums_workspace_bytes(B, wh, ww))
     require(nbytes > 0, "outside the limits: wh ww <= 2^24, B wh ww <= 2^28")
@@ -166,7 +166,7 @@ def solve_sums(plane, contour, weight, pose_in):
     cs = contour["sums"]
     require(isinstance(cs, torch.Tensor) and cs.dtype == torch.float64 and tuple(cs.shape) == (B, SUMS) and cs.device == dev,
             "contour sums must be float64 [B, 28] on the plane sums' device")
-    n_pairs, st, n_rows = (_int32(t, n, (B,), dev) for t, n in ((plane["n_pairs"], "n_pairs"), (plane["status"], "status"),
+    n_pairs, st, n_rows = (check_int32(t, n, (B,), dev) for t, n in ((plane["n_pairs"], "n_pairs"), (plane["status"], "status"),
                                                                (contour["n_rows"], "n_rows")))
     pose_in = _pose_in(pose_in, B, dev)
     weight = float(weight)
@@ -231,47 +231,36 @@ def pose_windows(poses, aabb, intrinsics, H, W, margin=MARGIN, z_near=Z_NEAR):
     return origin, wh, ww, ok
 
 
-def _host(x, dtype):
-    return np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype)
-
-
 # ---- the loop ---------------------------------------------------------------------------------------------------------------
-def align_poses(depth, intrinsics, meshes, mesh_of, frame_of, poses, iterations=ITERATIONS, gate=GATE, jump=JUMP, cos_min=COS_MIN,
-                margin=MARGIN, window=None, return_trajectory=False, contour=None):
-    """J poses refined against their frames.  depth [F,H,W] uint16 (numpy, or a device tensor holding the bits as int16),
-    intrinsics [F,5] float32 (host), meshes a PackedMeshes (or what mesh_models.pack_meshes takes), mesh_of and frame_of [J]
-    host integers, poses [J,4,4] float64 (host; a device tensor costs one read-back for the windows unless window is
-    given).  The window (pose_windows of the given poses; window=(origin [J,2], wh, ww) overrides it) is fixed over the
-    iterations; gate and jump in metres become depth units by tau_units of the track's frame.  Per iteration: one
-    render.render_instances call for all tracks (H = wh, W = ww, the windows' rows) and one align_step; nothing is read back
-    inside the loop.  contour=True or dict(radius=16, step=0.02, weight=1/16) adds the occluding-contour term (DESIGN.md,
-    "Contours"): one edge_nearest call before the loop (step in metres becomes units like the gates) and per iteration, after
-    the align_step, one contour_sums and one solve_sums, whose pose and status replace the step's; n_pairs stays the plane
-    pairs'.  With contour=None nothing of that is called.  A track without a window is given frame_of -1: status 4, its
-    pose unchanged.  -> dict of poses
-    [J,4,4] float64, n_pairs and status [J] int32 of the last step (device), origin [J,2], wh, ww, ok [J] (host); with
-    return_trajectory also trajectory [iterations + 1,J,4,4]: the pose before every step and after the last, and
-    n_pairs_steps, status_steps [iterations,J] (device)."""
-    from . import depth_components as dc_util
-    from . import mesh_models, render
-    p = mesh_models.pack_meshes(meshes)
-    dev = p.device
-    dt = _depth(dc_util._depth_tensor(depth, dev) if isinstance(depth, np.ndarray) else depth, "depth", 3)
+def align_windows(dev, dt, intr_host, frame_of, aabb, poses, hypothesis, iterations=ITERATIONS, gate=GATE, jump=JUMP, cos_min=COS_MIN,
+                  margin=MARGIN, window=None, return_trajectory=False, contour=None, on_step=None):
+    """The alignment loop: J poses refined against their frames.  Its one parameter is the hypothesis source: hypothesis(pose
+    [J,4,4] float64, rows [J,5] float32, both on the device, wh, ww) -> depth [J,wh,ww], the object seen under each pose in
+    its window (the meshes' renderer for align_poses, the raycast of a volume for scan.scan_object).  dt: the depth frames
+    [F,H,W] on `dev`; intr_host [F,5] float32 and frame_of [J] on the host; aabb [J,2,3]: the box each window is taken of;
+    poses [J,4,4] float64 (host; a device tensor costs one read-back for the windows unless window is given).  The window
+    (pose_windows of the given poses; window=(origin [J,2], wh, ww) overrides it) is fixed over the iterations; gate and jump
+    in metres become depth units by tau_units of the track's frame.  Per iteration: one hypothesis call for all tracks (the
+    windows' rows) and one align_step; nothing is read back inside the loop.  contour=True or dict(radius=16, step=0.02,
+    weight=1/16) adds the occluding-contour term ("Contours"): one edge_nearest call before the loop (step in
+    metres becomes units like the gates) and per iteration, after the align_step, one contour_sums and one solve_sums, whose
+    pose and status replace the step's; n_pairs stays the plane pairs'.  With contour=None nothing of that is called.  A
+    track without a window is given frame_of -1: status 4, its pose unchanged.  on_step(dict(pose_in, depth_hyp, pose_out,
+    n_pairs, status: device tensors; origin, wh, ww, rows, frame_of: host)) is called after every step.  -> dict of poses
+    [J,4,4] float64, n_pairs and status [J] int32 of the last step (device), origin [J,2], wh, ww, ok [J] (host), device:
+    dict(depth, frame_of, origin, rows) as the bindings take them; with return_trajectory also trajectory [iterations +
+    1,J,4,4]: the pose before every step and after the last, and n_pairs_steps, status_steps [iterations,J] (device)."""
     F, H, W = (int(v) for v in dt.shape)
-    mesh = np.asarray(mesh_of, np.int64).reshape(-1)
-    J = len(mesh)
     fo = np.asarray(frame_of, np.int64).reshape(-1)
-    require(J >= 1 and len(fo) == J, "mesh_of and frame_of must be [J], J >= 1")
-    require(mesh.min() >= 0 and mesh.max() < len(p.num_triangles), "mesh_of must lie inside the meshes")
+    J = len(fo)
     require(fo.min() >= 0 and fo.max() < F, "frame_of must lie in [0, F)")
-    intr_host = _host(intrinsics, np.float32)
     require(intr_host.shape == (F, 5), "intrinsics must be [F, 5], one row per frame")
     require(int(iterations) >= 0, "iterations must be >= 0")
     pose_dev = (poses if isinstance(poses, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(poses, np.float64))).to(dev)
     require(pose_dev.dtype == torch.float64 and pose_dev.numel() == 16 * J, "poses must be float64 [J, 4, 4]")
     pose_dev = pose_dev.reshape(J, 4, 4).contiguous()
     if window is None:
-        origin, wh, ww, ok = pose_windows(_host(poses, np.float64), mesh_aabb(p)[mesh], intr_host[fo], H, W, margin)
+        origin, wh, ww, ok = pose_windows(host(poses, np.float64), aabb, intr_host[fo], H, W, margin)
     else:
         origin, wh, ww = np.ascontiguousarray(window[0], np.int32), int(window[1]), int(window[2])
         require(origin.shape == (J, 2) and wh >= 1 and ww >= 1, "window must be (origin [J, 2], wh, ww)")
@@ -283,7 +272,8 @@ def align_poses(depth, intrinsics, meshes, mesh_of, frame_of, poses, iterations=
     gu, ju = tau_units(np.broadcast_to(np.asarray(gate, np.float64), (J,)), factor), \
         tau_units(np.broadcast_to(np.asarray(jump, np.float64), (J,)), factor)
     con = _contour_settings(contour)
-    cols = [np.where(ok, fo, -1), gu, ju, origin[:, 0], origin[:, 1]]
+    frame_host = np.where(ok, fo, -1)
+    cols = [frame_host, gu, ju, origin[:, 0], origin[:, 1]]
     if con:                                                # the edge step rides along in the one upload of the integers
         cols.append(tau_units(np.broadcast_to(np.asarray(con["step"], np.float64), (J,)), factor))
     ints = torch.from_numpy(np.stack(cols, axis=1).astype(np.int32)).to(dev)
@@ -293,18 +283,20 @@ def align_poses(depth, intrinsics, meshes, mesh_of, frame_of, poses, iterations=
     if con and int(iterations) > 0:
         step_dev = ints[:, 5].contiguous()
         near = edge_nearest(dt, frame_dev, org, wh, ww, step_dev, con["radius"])
-    offs, ones = np.arange(J + 1), np.ones(J, np.int64)
     traj, n_steps, s_steps = [pose_dev], [], []
     n_pairs = torch.zeros((J,), dtype=torch.int32, device=dev)
     status = torch.zeros((J,), dtype=torch.int32, device=dev)
     for _ in range(int(iterations)):
-        d = render.render_instances(p, rows, offs, mesh, ones, traj[-1].view(J, 16), wh, ww)[0]
+        d = hypothesis(traj[-1], rows, wh, ww)
         r = align_step(dt, frame_dev, org, d, rows, gate_dev, jump_dev, cos_min, traj[-1])
         n_pairs = r["n_pairs"]
         if con:
             c = contour_sums(dt, frame_dev, org, d, rows, gate_dev, step_dev, con["radius"], near)
             r = solve_sums(r, c, con["weight"], traj[-1])
         status = r["status"]
+        if on_step is not None:
+            on_step(dict(pose_in=traj[-1], depth_hyp=d, pose_out=r["pose_out"], n_pairs=n_pairs, status=status, origin=origin, wh=wh,
+                         ww=ww, rows=rows_host, frame_of=frame_host))
         if return_trajectory:
             traj.append(r["pose_out"])
             n_steps.append(n_pairs)
@@ -312,12 +304,62 @@ def align_poses(depth, intrinsics, meshes, mesh_of, frame_of, poses, iterations=
         else:
             traj = [r["pose_out"]]
     out = dict(poses=traj[-1], n_pairs=n_pairs, status=status, origin=origin, wh=wh, ww=ww, ok=ok,
-               device=dict(depth=dt, frame_of=frame_dev, origin=org, rows=rows, packed=p))
+               device=dict(depth=dt, frame_of=frame_dev, origin=org, rows=rows))
     if return_trajectory:
         out["trajectory"] = torch.stack(traj)
         out["n_pairs_steps"] = torch.stack(n_steps) if n_steps else torch.zeros((0, J), dtype=torch.int32, device=dev)
         out["status_steps"] = torch.stack(s_steps) if s_steps else torch.zeros((0, J), dtype=torch.int32, device=dev)
     return out
+
+
+def _mesh_source(p, mesh):
+    """What known objects give the loop: the boxes [J,2,3] of the meshes mesh [J] of the PackedMeshes p, and the hypothesis
+    source that draws each alone into its window (one render.render_instances call, H = wh, W = ww, the windows' rows)."""
+    require(mesh.min() >= 0 and mesh.max() < len(p.num_triangles), "mesh_of must lie inside the meshes")
+    J = len(mesh)
+    offs, ones = np.arange(J + 1), np.ones(J, np.int64)
+    return mesh_aabb(p)[mesh], lambda pose, rows, wh, ww: render.render_instances(p, rows, offs, mesh, ones, pose.view(J, 16), wh, ww)[0]
+
+
+def align_poses(depth, intrinsics, meshes, mesh_of, frame_of, poses, iterations=ITERATIONS, gate=GATE, jump=JUMP, cos_min=COS_MIN,
+                margin=MARGIN, window=None, return_trajectory=False, contour=None):
+    """J poses refined against their frames: align_windows (its keywords and its result, device with packed: the
+    PackedMeshes) with the meshes' renderer as hypothesis source -- one render.render_instances call for all tracks, H = wh, W
+    = ww -- and mesh_aabb as the windows' boxes.  depth [F,H,W] uint16 (numpy, or a device tensor holding the bits as int16),
+    intrinsics [F,5] float32 (host), meshes a PackedMeshes (or what mesh_models.pack_meshes takes), mesh_of and frame_of [J]
+    host integers, poses [J,4,4] float64."""
+    p = mesh_models.pack_meshes(meshes)
+    dt = depth_frames(depth, p.device)
+    mesh, fo = np.asarray(mesh_of, np.int64).reshape(-1), np.asarray(frame_of, np.int64).reshape(-1)
+    require(len(mesh) >= 1 and len(fo) == len(mesh), "mesh_of and frame_of must be [J], J >= 1")
+    aabb, renderer = _mesh_source(p, mesh)
+    out = align_windows(p.device, dt, host(intrinsics, np.float32), fo, aabb, poses, renderer, iterations, gate, jump, cos_min, margin,
+                        window, return_trajectory, contour)
+    out["device"]["packed"] = p
+    return out
+
+
+def frame_attempt(dev, dt, intr_host, f, aabb, start, hypothesis, tau_u, min_score, label=None, want=None, **align):
+    """One frame's attempt for n tracks, what tracking and scanning share: align_windows(**align) in frame f from the starts
+    [n,4,4] (host), one more hypothesis at the result in the same window, detect.fit_counts_window of it (tau_u in depth
+    units; label [F,H,W] uint8 with want [n] int32 on the device, or neither), one read-back -- the poses as their bits, the
+    counters, the last step's pairs and status -- and the silhouette rule: (num, den) = (consistent, consistent + in_front +
+    behind), 0 / 1 for den = 0; lost when num min_den < min_num den in integers, min_score = (min_num, min_den), or without
+    a window.  -> (pose [n,4,4], num, den, n_pairs, status, lost [n] on the host, the poses on the device)."""
+    n = len(start)
+    a = align_windows(dev, dt, intr_host, np.full(n, f), aabb, start, hypothesis, **align)
+    dv = a["device"]
+    d = hypothesis(a["poses"], dv["rows"], a["wh"], a["ww"])
+    tau_dev = torch.full((n,), int(tau_u), dtype=torch.int32, device=dev)
+    c = detect.fit_counts_window(dt, label, dv["frame_of"], want, dv["origin"], d.view(n, 1, a["wh"], a["ww"]), tau_dev)
+    got = torch.cat([a["poses"].contiguous().view(torch.int32).reshape(-1), c["counts"].reshape(-1), a["n_pairs"],
+                     a["status"]]).cpu().numpy()
+    pose = got[:32 * n].copy().view(np.float64).reshape(n, 4, 4)
+    counts = got[32 * n:38 * n].reshape(n, 6).astype(np.int64)
+    num, den = counts[:, 1].copy(), counts[:, 1] + counts[:, 2] + counts[:, 3]
+    num, den = np.where(den > 0, num, 0), np.where(den > 0, den, 1)
+    lost = ~a["ok"] | (num * int(min_score[1]) < int(min_score[0]) * den)
+    return pose, num, den, got[38 * n:39 * n], got[39 * n:40 * n], lost, a["poses"]
 
 
 # ---- tracking ---------------------------------------------------------------------------------------------------------------
@@ -360,7 +402,7 @@ def _initial_tracks(init):
         return cls[keep].astype(np.int64), pose[keep].copy()
     require(isinstance(init, (tuple, list)) and len(init) == 2, "init must be a Detections or (mesh_of [J], poses [J, 4, 4])")
     mesh = np.asarray(init[0], np.int64).reshape(-1)
-    return mesh, _host(init[1], np.float64).reshape(len(mesh), 4, 4).copy()
+    return mesh, host(init[1], np.float64).reshape(len(mesh), 4, 4).copy()
 
 
 def track_objects(depth, intrinsics, meshes, init, motion="constant", min_score=MIN_SCORE, tau=TAU, on_lost=None, first_frame=0,
@@ -369,24 +411,23 @@ def track_objects(depth, intrinsics, meshes, init, motion="constant", min_score=
     intrinsics [F,5] (or [5]) float32.  init: a Detections of frame 0 -- its assigned components become the tracks, mesh =
     the class id, as detect_objects assumes by default -- or (mesh_of [J], poses [J,4,4]).  Frames are taken in order, frame
     0 included.  The start of a frame is the track's last pose, or with motion='velocity' (T_{f-1} T_{f-2}^-1) T_{f-1} once
-    two poses exist.  Each frame runs align_poses(**align) from the starts, renders the result into the same window and counts
-    it with detect.fit_counts_window without a label (tau in metres); the score is the silhouette rule's (num, den) =
-    (consistent, consistent + in_front + behind), 0 / 1 for den = 0.  A track is lost in frame f when num min_den < min_num
+    two poses exist.  Each frame is one frame_attempt with the meshes' renderer: the loop of align_poses(**align) from the
+    starts, the result rendered into the same window and counted with detect.fit_counts_window without a label (tau in
+    metres); the score is the silhouette rule's (num, den) = (consistent, consistent + in_front + behind), 0 / 1 for den = 0.
+    A track is lost in frame f when num min_den < min_num
     den, in integers, or when it has no window; it keeps its last good pose and is tried again from it, at rest, in the next
     frame.  on_lost(f, track_indices), called when tracks are lost, may return new poses [len(track_indices),4,4] (or None):
     they are aligned and scored in the same frame -- the hook to hang detect_objects(depth[f:f+1], ..., first_frame =
     first_frame + f) on.  contour (None, True or dict(radius, step, weight)) is align_poses': the occluding-contour term that
     holds flat and thin objects, off by default.  One read-back per frame (one more when on_lost gives poses).  -> Tracks."""
-    from . import depth_components as dc_util
-    from . import mesh_models, render
     require(motion in ("constant", "velocity"), "motion must be 'constant' or 'velocity'")
     num_min, den_min = int(min_score[0]), int(min_score[1])
     require(0 <= num_min <= den_min and den_min >= 1, "min_score must be (num, den) with 0 <= num <= den, den >= 1")
     p = mesh_models.pack_meshes(meshes)
     dev = p.device
-    dt = _depth(dc_util._depth_tensor(depth, dev) if isinstance(depth, np.ndarray) else depth, "depth", 3)
+    dt = depth_frames(depth, dev)
     F = int(dt.shape[0])
-    intr = np.ascontiguousarray(np.broadcast_to(_host(intrinsics, np.float32).reshape(-1, 5), (F, 5)))
+    intr = intrinsics_per_frame(intrinsics, F)
     mesh_of, last = _initial_tracks(init)
     J = len(mesh_of)
     require(J >= 1, "no track to follow")
@@ -399,23 +440,8 @@ def track_objects(depth, intrinsics, meshes, init, motion="constant", min_score=
     t.n_pairs, t.status, t.lost = np.zeros((F, J), np.int32), np.zeros((F, J), np.int32), np.zeros((F, J), bool)
 
     def attempt(f, idx, start):
-        """align, render, count and read back -> (pose [n,4,4], num, den, n_pairs, status, lost [n])."""
-        n = len(idx)
-        a = align_poses(dt, intr, p, mesh_of[idx], np.full(n, f), start, contour=contour, **align)
-        dv = a["device"]
-        d = render.render_instances(p, dv["rows"], np.arange(n + 1), mesh_of[idx], np.ones(n, np.int64), a["poses"].view(n, 16),
-                                    a["wh"], a["ww"])[0]
-        tau_dev = torch.full((n,), int(tau_frame[f]), dtype=torch.int32, device=dev)
-        c = detect.fit_counts_window(dt, None, dv["frame_of"], None, dv["origin"], d.view(n, 1, a["wh"], a["ww"]), tau_dev)
-        # the one read-back: the poses as their bits, the counters, the last step's pairs and status
-        host = torch.cat([a["poses"].contiguous().view(torch.int32).reshape(-1), c["counts"].reshape(-1), a["n_pairs"],
-                          a["status"]]).cpu().numpy()
-        pose = host[:32 * n].copy().view(np.float64).reshape(n, 4, 4)
-        counts = host[32 * n:38 * n].reshape(n, 6).astype(np.int64)
-        num, den = counts[:, 1].copy(), counts[:, 1] + counts[:, 2] + counts[:, 3]
-        num, den = np.where(den > 0, num, 0), np.where(den > 0, den, 1)
-        lost = ~a["ok"] | (num * den_min < num_min * den)
-        return pose, num, den, host[38 * n:39 * n], host[39 * n:40 * n], lost
+        aabb, renderer = _mesh_source(p, mesh_of[idx])
+        return frame_attempt(dev, dt, intr, f, aabb, start, renderer, tau_frame[f], (num_min, den_min), contour=contour, **align)[:6]
 
     for f in range(F):
         idx = np.arange(J)
@@ -425,7 +451,7 @@ def track_objects(depth, intrinsics, meshes, init, motion="constant", min_score=
             again = np.nonzero(lost)[0]
             given = on_lost(f, again.copy())
             if given is not None:
-                given = _host(given, np.float64).reshape(len(again), 4, 4)
+                given = host(given, np.float64).reshape(len(again), 4, 4)
                 pose[again], num[again], den[again], n_pairs[again], status[again], lost[again] = attempt(f, again, given)
         for j in idx:
             if lost[j]:

@@ -327,6 +327,47 @@ def test_sequences(track, packed, obj):
     assert not t.lost.any() and np.all(t.status == 0)
 
 
+def test_tracking_with_the_term_replayed_by_hand(track, dev, packed):
+    """track_objects(contour=True) over two frames, then the same frames by hand with the bindings alone -- pose_windows, one
+    edge_nearest per frame, per step render, align_step, contour_sums, solve_sums, then the final render and the counts:
+    poses, num, den, n_pairs and status are equal bit for bit."""
+    from cloudaae_amd.utils import detect, render
+    depth, truth = CR.frames(CR.PRISM, TR.SLOW)
+    t = track.track_objects(depth[:2], TR.SCENE_INTR, packed, ([CR.PRISM], truth[:1]), contour=True)
+    dt = _bits(depth[:2]).to(dev)
+    intr = np.asarray(TR.SCENE_INTR, np.float32).reshape(-1, 5)[:1]
+    factor = [float(intr[0, 4])]
+    gate, jump, step, tau = (_i32(TR.V.tau_units([v], factor), dev) for v in (0.03, 0.005, CR.STEP, 0.01))
+    mesh, ones, offs = np.array([CR.PRISM]), np.ones(1, np.int64), np.arange(2)
+    last = truth[0]
+    for f in range(2):
+        origin, wh, ww, ok = track.pose_windows(last[None], track.mesh_aabb(packed)[mesh], intr, TR.SCENE_H, TR.SCENE_W)
+        assert ok[0]
+        rows_host = intr.copy()
+        rows_host[:, 2] = intr[0, 2] - origin[:, 0].astype(np.float32)
+        rows_host[:, 3] = intr[0, 3] - origin[:, 1].astype(np.float32)
+        rows, org, frame = torch.from_numpy(rows_host).to(dev), _i32(origin, dev), _i32([f], dev)
+        pose = torch.from_numpy(last[None].copy()).to(dev)
+        near = track.edge_nearest(dt, frame, org, wh, ww, step, CR.RADIUS)
+        for _ in range(4):
+            d = render.render_instances(packed, rows, offs, mesh, ones, pose.view(1, 16), wh, ww)[0]
+            plane = track.align_step(dt, frame, org, d, rows, gate, jump, 0.8, pose)
+            con = track.contour_sums(dt, frame, org, d, rows, gate, step, CR.RADIUS, near)
+            solved = track.solve_sums(plane, con, CR.WEIGHT, pose)
+            pose = solved['pose_out']
+        d = render.render_instances(packed, rows, offs, mesh, ones, pose.view(1, 16), wh, ww)[0]
+        c = detect.fit_counts_window(dt, None, frame, None, org, d.view(1, 1, wh, ww), tau)['counts'].cpu().numpy().reshape(6).astype(np.int64)
+        num, den = int(c[1]), int(c[1] + c[2] + c[3])
+        num, den = (num, den) if den > 0 else (0, 1)
+        assert not num * 2 < 1 * den and not t.lost[f, 0]
+        last = pose.cpu().numpy()[0]
+        print("frame %d: score %d / %d, pairs %d, rows %d" % (f, num, den, int(plane['n_pairs'][0]), int(con['n_rows'][0])))
+        assert t.poses[f, 0].tobytes() == last.tobytes(), f
+        assert (int(t.num[f, 0]), int(t.den[f, 0])) == (num, den), f
+        assert (int(t.n_pairs[f, 0]), int(t.status[f, 0])) == (int(plane['n_pairs'][0]), int(solved['status'][0])), f
+    assert t.poses.dtype == np.float64 and t.n_pairs.dtype == np.int32 and t.status.dtype == np.int32
+
+
 def test_contour_none_is_the_tracker_as_before(track, dev, packed, monkeypatch):
     """With contour=None none of the new entries is called, and the loop is render + align_step, bit for bit."""
     from cloudaae_amd.utils import render

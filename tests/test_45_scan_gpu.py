@@ -254,6 +254,67 @@ def test_orbit_end_to_end(scan, orbit_gpu):
     assert not g.lost.any() and np.all(err <= ref_err + 1e-5)
 
 
+def test_scan_is_the_frame_attempt_replayed_by_hand(scan, dev):
+    """Three frames of the orbit, then the same frames by hand from the recorded start poses with the bindings alone --
+    track.pose_windows, scan.raycast, track.align_step, detect.fit_counts_window, fuse.integrate: every step's image and pose,
+    every frame's volume and every column of the Scan are equal bit for bit."""
+    from cloudaae_amd.utils import detect, fuse, track
+    o = S.orbit()
+    depth, truth, aabb = o['depth'][:3], o['truth'], S.cube_aabb()
+    steps, states = [], []
+    s = run_scan(scan, depth, truth, on_step=lambda f, info: steps.append((f, {
+        k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in info.items()})),
+        on_frame=lambda f, pose, volume: states.append(volume.state.cpu().numpy()))
+    assert len(steps) == 8 and len(states) == 3
+
+    def up(a, dtype):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype)).to(dev)
+    dt = torch.from_numpy(np.ascontiguousarray(depth).view(np.int16)).to(dev)
+    intr = up(np.tile(FR.SCENE_INTR, (3, 1)), np.float32)
+    vol = fuse.volume_for(aabb, S.ORBIT_VOXEL, device=dev)
+    fuse.integrate(vol, dt[:1], intr[:1], up(truth[:1], np.float64))
+    assert states[0].tobytes() == vol.state.cpu().numpy().tobytes()
+    assert s.poses[0].tobytes() == truth[0].tobytes() and (s.num[0], s.den[0], s.lost[0]) == (0, 1, False)
+    factor = np.float64(FR.SCENE_INTR[4])
+    gate, jump, tau = (up(V.tau_units(np.array([q], np.float64), factor), np.int32)
+                       for q in (S.ORBIT_SETTINGS['gate'], S.ORBIT_SETTINGS['jump'], 0.01))
+    last = truth[0]
+    for f in (1, 2):
+        mine = [info for g, info in steps if g == f]
+        start = mine[0]['pose_in']
+        assert start.tobytes() == last[None].tobytes()                                  # at rest: the frame starts from the last pose
+        origin, wh, ww, ok = track.pose_windows(start, aabb[None], FR.SCENE_INTR[None], FR.SCENE_H, FR.SCENE_W, S.ORBIT_SETTINGS['margin'])
+        assert ok[0]
+        rows_host = np.asarray(FR.SCENE_INTR, np.float32)[None].copy()
+        rows_host[:, 2] = FR.SCENE_INTR[2] - origin[:, 0].astype(np.float32)
+        rows_host[:, 3] = FR.SCENE_INTR[3] - origin[:, 1].astype(np.float32)
+        rows, org, frame = up(rows_host, np.float32), up(origin, np.int32), up([f], np.int32)
+        pose = up(start, np.float64)
+        for i in range(4):
+            d = scan.raycast(vol, pose, rows, wh, ww)
+            r = track.align_step(dt, frame, org, d, rows, gate, jump, S.ORBIT_SETTINGS['cos_min'], pose)
+            assert mine[i]['pose_in'].tobytes() == pose.cpu().numpy().tobytes(), (f, i)
+            assert mine[i]['depth_hyp'].tobytes() == d.cpu().numpy().tobytes(), (f, i)
+            assert mine[i]['pose_out'].tobytes() == r['pose_out'].cpu().numpy().tobytes(), (f, i)
+            assert (mine[i]['wh'], mine[i]['ww'], mine[i]['frame_of']) == (wh, ww, f) and np.array_equal(mine[i]['origin'], origin)
+            assert mine[i]['rows'].tobytes() == rows_host.tobytes()
+            pose = r['pose_out']
+        d = scan.raycast(vol, pose, rows, wh, ww)
+        c = detect.fit_counts_window(dt, None, frame, None, org, d.view(1, 1, wh, ww), tau)['counts'].cpu().numpy().reshape(6).astype(np.int64)
+        num, den = int(c[1]), int(c[1] + c[2] + c[3])
+        num, den = (num, den) if den > 0 else (0, 1)
+        lost = num * 2 < 1 * den
+        if not lost:
+            fuse.integrate(vol, dt[f:f + 1], intr[f:f + 1], pose)
+            last = pose.cpu().numpy()[0]
+        print("frame %d: score %d / %d, pairs %d" % (f, num, den, int(r['n_pairs'][0])))
+        assert states[f].tobytes() == vol.state.cpu().numpy().tobytes(), f
+        assert s.poses[f].tobytes() == last.tobytes(), f
+        assert (int(s.num[f]), int(s.den[f]), bool(s.lost[f])) == (num, den, lost), f
+        assert (int(s.n_pairs[f]), int(s.status[f])) == (int(r['n_pairs'][0]), int(r['status'][0])), f
+    assert s.poses.dtype == np.float64 and s.n_pairs.dtype == np.int32 and s.status.dtype == np.int32 and s.lost.dtype == bool
+
+
 def test_lost_and_resumed(scan, dev):
     from cloudaae_amd.utils import mesh_models
     o = S.orbit(8, S.ORBIT_VOXEL, S.STEP_VOXELS, (5,))
