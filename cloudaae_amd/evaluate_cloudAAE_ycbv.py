@@ -26,7 +26,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, tfrecord_io
 from ._lib import ptr, require, stream
 from .losses import angular_distance_taylor, chamfer_loss, trans_distance
 from .tf_ops.sampling import tf_sampling
@@ -34,12 +34,14 @@ from .train_cloudAAE_ycbv import NUM_CLASS
 from .utils import _functions as F
 from .utils import bop_score as bop_util
 from .utils import icp as icp_util
+from .utils import mesh_models
 from .utils import normals as normals_util
 from .utils import pose_equiv
 from .utils import pose_score as score_util
 from .utils import pose_verify as verify_util
 from .utils import ppf as ppf_util
 from .utils import segment as seg_util
+from .utils.frame_inputs import record_intrinsics
 
 
 def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None, symmetries=None, verify=None, propose=None):
@@ -124,9 +126,9 @@ def evaluate_batch(graph, element, replay=False, icp=None, score=None, bop=None,
     if verify is not None:
         out.update(_verify(graph, element, out, verify, icp, score, symmetries, prop))
     if bop is not None:
-        out.update(_bop(element, out, bop))
+        out.update(_bop(element, bop, *_pred_icp_poses(out)))
         if verify is not None:
-            out.update(_bop(element, out, bop, only_ver=True))
+            out.update(_bop(element, bop, ("ver",), out['transformation_ver'].unsqueeze(1)))
     return out
 
 
@@ -189,25 +191,19 @@ def _verify(graph, element, out, verify, icp, score, symmetries, prop=None):
         pick = v['best'].to(torch.int64).view(B, 1, 1).expand(B, 1, 3)
         rot_ver = rot.gather(1, pick).squeeze(1).contiguous()
         trans_ver = trans.gather(1, pick).squeeze(1).contiguous()
-        rot_ver32 = icp_util.to_float32(rot_ver)
-        trans_loss, trans_per = trans_distance.get_translation_error(trans_ver, translation)
-        axag_loss, axag_per = angular_distance_taylor.get_rotation_error(rot_ver32, element['axisangle'])
     res = dict(verify_best=v['best'], verify_score=v['score'], verify_margin=v['margin'], verify_counts=v['counts'],
-               verify_candidates=cand, transformation_ver=v['pose_best'], rot_ver=rot_ver, trans_ver=trans_ver,
-               trans_loss_ver=trans_loss, trans_loss_perSample_ver=trans_per, axag_loss_ver=axag_loss,
-               axag_loss_perSample_ver=axag_per)
+               verify_candidates=cand, transformation_ver=v['pose_best'], rot_ver=rot_ver, trans_ver=trans_ver)
+    res.update(_pose_errors(element, cls, icp_util.to_float32(rot_ver), trans_ver, translation, '_ver', symmetries))
     if score:
-        with torch.no_grad():
-            gt = score_util.pose_matrix(element['axisangle'], translation.contiguous())
-            s = score_util.score_poses(element['obj_batch'], v['pose_best'], gt)
-        res.update(add_ver=s['add'][:, 0], adds_ver=s['adds'][:, 0])
-    if symmetries is not None:
-        res.update(_equivalent_errors(element, cls, rot_ver32, trans_ver, translation, symmetries, '_ver'))
+        res.update(_add_scores(element, translation, ("ver",), v['pose_best'].unsqueeze(1)))
     return res
 
 
 def _icp_call(element, obj, scene, rot, trans, params, repeat=1):
-    """refine_pose_icp as _refine calls it, on models and scenes that hold every sample `repeat` times in a row."""
+    """The evaluation's one refine_pose_icp call, on models and scenes that hold every sample `repeat` times in a row.
+    Point to point (:606-628): the class's object model (source, object frame) onto the network's input points (target,
+    camera frame, not centred).  Point to plane: the input points onto the model along the model's normals; the poses
+    given and returned stay model -> camera."""
     if params.get('estimation', 'point_to_point') == 'point_to_plane':
         params = dict(params)
         normal_radius = params.pop('normal_radius', NORMAL_RADIUS)
@@ -215,15 +211,25 @@ def _icp_call(element, obj, scene, rot, trans, params, repeat=1):
         normals = element.get('obj_normals')
         if normals is None:
             normals = normals_util.estimate_normals(element['obj_batch'], radius=normal_radius)[0]
-        return icp_util.refine_pose_icp(scene, obj, rot.contiguous(), trans.contiguous(),
-                                        normals=normals.repeat_interleave(repeat, dim=0).contiguous(),
+        if repeat != 1:                         # a torch kernel: not in the recorded pass, which refines every sample once
+            normals = normals.repeat_interleave(repeat, dim=0).contiguous()
+        return icp_util.refine_pose_icp(scene, obj, rot.contiguous(), trans.contiguous(), normals=normals,
                                         pose_maps_target_to_source=True, **params)
     return icp_util.refine_pose_icp(obj, scene, rot.contiguous(), trans.contiguous(), **params)
 
 
-def _bop(element, out, bop, only_ver=False):
-    """VSD, MSSD and MSPD of the predicted pose and, when there is one, of the refined pose; only_ver: of the verified
-    pose alone (a call of its own, so that the others' numbers are formed as without verification)."""
+def _pred_icp_poses(out):
+    """(names, est [B,K,4,4]) of the predicted pose and, when there is one, of the refined pose: one launch scores both."""
+    with torch.no_grad():
+        est = score_util.pose_matrix(out['rot_pred'].contiguous(), out['trans_pred'].contiguous())
+        if out.get('transformation_icp') is None:
+            return ("pred",), est.unsqueeze(1)
+        return ("pred", "icp"), score_util.stack_poses(est, out['transformation_icp'])
+
+
+def _bop(element, bop, names, est):
+    """VSD, MSSD and MSPD of the poses est [B,K,4,4], one per name.  The verified pose comes in a call of its own, so that
+    the others' numbers are formed as without verification."""
     obj, depth, intr = element.get('obj_batch'), element.get('frame_depth'), element.get('frame_intrinsics')
     require(obj is not None and depth is not None and intr is not None,
             "bop needs element['obj_batch'], ['frame_depth'] and ['frame_intrinsics'] (element_from_frames(keep_frames=True))")
@@ -231,15 +237,6 @@ def _bop(element, out, bop, only_ver=False):
     B = int(cls.shape[0])
     with torch.no_grad():
         gt = score_util.pose_matrix(element['axisangle'], element['translation'].to(torch.float32).contiguous())
-        est = score_util.pose_matrix(out['rot_pred'].contiguous(), out['trans_pred'].contiguous())
-        names = ("pred",)
-        if only_ver:
-            est, names = out['transformation_ver'].unsqueeze(1), ("ver",)
-        elif out.get('transformation_icp') is not None:
-            est = score_util.stack_poses(est, out['transformation_icp'])
-            names = ("pred", "icp")
-        else:
-            est = est.unsqueeze(1)
         diam = bop['diameters']
         diam = diam if isinstance(diam, torch.Tensor) else torch.from_numpy(np.asarray(diam, np.float64))
         diam = diam.to(device=cls.device, dtype=torch.float64).index_select(0, cls)
@@ -331,84 +328,64 @@ def _evaluate(graph, element, icp=None, score=False, symmetries=None):
         visiblePoints_final = element['visiblePoints_org'][:, 0:N, :].to(torch.float32).contiguous()   # :431-433
         xyz_loss, xyz_per = chamfer_loss.get_loss(xyz_recon_FPS, visiblePoints_final)
         translation = element['translation'].to(torch.float32)
-        trans_loss, trans_per = trans_distance.get_translation_error(trans_pred, translation)            # :455
         mean_dist_loss, mean_dist_per = trans_distance.get_translation_error(element_mean, translation)  # :457
-        axag_loss, axag_per = angular_distance_taylor.get_rotation_error(rot_pred, element['axisangle'])  # :470-474
     out = dict(xyz_recon=xyz_recon, xyz_recon_FPS=xyz_recon_FPS, rot_pred=rot_pred, trans_pred=trans_pred,
-               xyz_loss=xyz_loss, xyz_loss_per_sample=xyz_per, trans_loss=trans_loss,
-               trans_loss_perSample=trans_per, mean_dist_loss=mean_dist_loss,
-               mean_dist_loss_perSample=mean_dist_per, axag_loss=axag_loss, axag_loss_perSample=axag_per,
-               element_mean=element_mean, end_points=end_points)
+               xyz_loss=xyz_loss, xyz_loss_per_sample=xyz_per, mean_dist_loss=mean_dist_loss,
+               mean_dist_loss_perSample=mean_dist_per, element_mean=element_mean, end_points=end_points)
+    out.update(_pose_errors(element, cls, rot_pred, trans_pred, translation, '', symmetries))           # :455, :470-474
     if icp is not None:
-        out.update(_refine(element, xyz[:, 0:N, :], rot_pred, trans_pred, translation, icp))
+        out.update(_refine(element, cls, xyz[:, 0:N, :], rot_pred, trans_pred, translation, icp, symmetries))
     if score:
-        out.update(_score(element, rot_pred, trans_pred, translation, out.get('transformation_icp')))
-    if symmetries is not None:
-        out.update(_equivalent_errors(element, cls, rot_pred, trans_pred, translation, symmetries, ''))
-        if icp is not None:
-            out.update(_equivalent_errors(element, cls, icp_util.to_float32(out['rot_icp']), out['trans_icp'], translation,
-                                          symmetries, '_icp'))
+        out.update(_add_scores(element, translation, *_pred_icp_poses(out)))
     return out
 
 
-def _equivalent_errors(element, cls, rot, trans, translation, table, tag):
-    """The errors of the pose (rot, trans) against the equivalent label nearest its rotation."""
+def _pose_errors(element, cls, rot32, trans, translation, tag, symmetries):
+    """The translation and rotation errors of one pose set (rot32: its rotation in fp32, as the rotation error kernel takes
+    it) under the keys of `tag` ('', '_icp', '_ver'); with a symmetry table also those against the equivalent label nearest
+    the pose's rotation, under the same keys with '_sym' behind."""
+    def errors(trans_label, rot_label, suffix):
+        trans_loss, trans_per = trans_distance.get_translation_error(trans, trans_label)
+        axag_loss, axag_per = angular_distance_taylor.get_rotation_error(rot32, rot_label)
+        return {'trans_loss' + suffix: trans_loss, 'trans_loss_perSample' + suffix: trans_per,
+                'axag_loss' + suffix: axag_loss, 'axag_loss_perSample' + suffix: axag_per}
     with torch.no_grad():
-        near = pose_equiv.nearest_equivalent_pose(rot, element['axisangle'], translation, cls, table)
-        trans_loss, trans_per = trans_distance.get_translation_error(trans, near['trans_equiv'])
-        axag_loss, axag_per = angular_distance_taylor.get_rotation_error(rot, near['rot_equiv'])
-    return {'trans_loss%s_sym' % tag: trans_loss, 'trans_loss_perSample%s_sym' % tag: trans_per,
-            'axag_loss%s_sym' % tag: axag_loss, 'axag_loss_perSample%s_sym' % tag: axag_per}
+        res = errors(translation, element['axisangle'], tag)
+        if symmetries is not None:
+            near = pose_equiv.nearest_equivalent_pose(rot32, element['axisangle'], translation, cls, symmetries)
+            res.update(errors(near['trans_equiv'], near['rot_equiv'], tag + '_sym'))
+    return res
 
 
-def _score(element, rot_pred, trans_pred, translation, transformation_icp):
-    """ADD and ADD-S of the predicted pose and, when given, of the refined one against the ground-truth pose."""
+def _add_scores(element, translation, names, est):
+    """ADD and ADD-S of the poses est [B,K,4,4], one per name, against the ground-truth pose: one launch."""
     obj = element.get('obj_batch')
     require(obj is not None, "score needs element['obj_batch'] [B, M, >=3] (the object model of each sample's class)")
-    require(obj.dim() == 3 and obj.shape[0] == rot_pred.shape[0] and obj.shape[2] >= 3 and obj.dtype == torch.float32,
+    require(obj.dim() == 3 and obj.shape[0] == est.shape[0] and obj.shape[2] >= 3 and obj.dtype == torch.float32,
             "obj_batch must be a float32 [B, M, >=3] tensor")
     axisangle = element['axisangle']
     require(axisangle.dtype in (torch.float32, torch.float64), "axisangle must be float32 or float64")
     with torch.no_grad():
-        gt = score_util.pose_matrix(axisangle, translation.contiguous())
-        est = score_util.pose_matrix(rot_pred.contiguous(), trans_pred.contiguous())
-        if transformation_icp is not None:
-            est = score_util.stack_poses(est, transformation_icp)
-        r = score_util.score_poses(obj, est, gt)
-    out = dict(add_pred=r['add'][:, 0], adds_pred=r['adds'][:, 0])
-    if transformation_icp is not None:
-        out.update(add_icp=r['add'][:, 1], adds_icp=r['adds'][:, 1])
-    return out
+        r = score_util.score_poses(obj, est, score_util.pose_matrix(axisangle, translation.contiguous()))
+    res = {}
+    for k, name in enumerate(names):
+        res['add_' + name], res['adds_' + name] = r['add'][:, k], r['adds'][:, k]
+    return res
 
 
-def _refine(element, scene, rot_pred, trans_pred, translation, params):
-    """:606-628 -- ICP of the class's object model (source, object frame) onto the network's input points (target,
-    camera frame, not centred), from the predicted pose; then the errors of the refined pose."""
+def _refine(element, cls, scene, rot_pred, trans_pred, translation, params, symmetries):
+    """The predicted pose refined by ICP against the network's input points (_icp_call); then the errors of the refined
+    pose."""
     obj = element.get('obj_batch')
     require(obj is not None, "icp needs element['obj_batch'] [B, M, >=3] (the object model of each sample's class)")
     require(obj.dim() == 3 and obj.shape[0] == scene.shape[0] and obj.shape[2] >= 3 and obj.dtype == torch.float32,
             "obj_batch must be a float32 [B, M, >=3] tensor")
     with torch.no_grad():
-        if params.get('estimation', 'point_to_point') == 'point_to_plane':
-            # scene -> model along the model's normals; the poses given and returned stay model -> camera
-            params = dict(params)
-            normal_radius = params.pop('normal_radius', NORMAL_RADIUS)
-            params.pop('pose_maps_target_to_source', None)
-            normals = element.get('obj_normals')
-            if normals is None:
-                normals = normals_util.estimate_normals(obj, radius=normal_radius)[0]
-            r = icp_util.refine_pose_icp(scene, obj, rot_pred.contiguous(), trans_pred.contiguous(), normals=normals,
-                                         pose_maps_target_to_source=True, **params)
-        else:
-            r = icp_util.refine_pose_icp(obj, scene, rot_pred.contiguous(), trans_pred.contiguous(), **params)
-        trans_loss, trans_per = trans_distance.get_translation_error(r['trans'], translation)
-        # the rotation error kernel takes an fp32 prediction, as for the network's output
-        axag_loss, axag_per = angular_distance_taylor.get_rotation_error(icp_util.to_float32(r['rot_axag']),
-                                                                         element['axisangle'])
-    return dict(rot_icp=r['rot_axag'], trans_icp=r['trans'], transformation_icp=r['transformation'],
-                fitness_icp=r['fitness'], inlier_rmse_icp=r['inlier_rmse'], iterations_icp=r['iterations'],
-                trans_loss_icp=trans_loss, trans_loss_perSample_icp=trans_per, axag_loss_icp=axag_loss,
-                axag_loss_perSample_icp=axag_per)
+        r = _icp_call(element, obj, scene, rot_pred, trans_pred, params)
+    res = dict(rot_icp=r['rot_axag'], trans_icp=r['trans'], transformation_icp=r['transformation'],
+               fitness_icp=r['fitness'], inlier_rmse_icp=r['inlier_rmse'], iterations_icp=r['iterations'])
+    res.update(_pose_errors(element, cls, icp_util.to_float32(r['rot_axag']), r['trans'], translation, '_icp', symmetries))
+    return res
 
 
 # ---- the input side: frames -> element (:125-335) -------------------------------------------------------------------
@@ -467,41 +444,14 @@ def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, devic
     require(len(shapes) == 1, "frames of one call must share their size")
     depth = np.stack([f["depth"] for f in frames])
     label = np.stack([f["label"] for f in frames])
-    intr = np.array([[f["fx"], f["fy"], f["cx"], f["cy"], f["factor_depth"]] for f in frames], np.float32)
+    intr = record_intrinsics(frames)
     segment_iou, agree = None, None
     if labels == "components":
-        from .utils import depth_components as dc_util
-        # every frame of the call is segmented, also those without the class: frame i of the call then has the global
-        # index first_frame + i whatever its neighbours hold
-        found = dc_util.segment_depth(
-            np.stack([f["depth"] for f in chunk]),
-            np.array([[f["fx"], f["fy"], f["cx"], f["cy"], f["factor_depth"]] for f in chunk], np.float32), device=device,
-            **(components or {}))
-        found_label = found.label.index_select(0, torch.tensor(position, dtype=torch.int64, device=device))
-        ks, ious = dc_util.match_components(found_label, torch.from_numpy(np.ascontiguousarray(label, np.uint8)).to(device),
-                                            depth, int(target_cls) + 1)
-        if choose == "detect":
-            ks_record = ks
-            ks, ious = _detected_components(chunk, position, found, found_label, label, depth, target_cls, components, detector)
-            agree = ks == ks_record
-        hit = np.nonzero(ks > 0)[0]
-        if counts is not None:
-            counts["frames"] = counts.get("frames", 0) + len(frames)
-            key = "matched" if choose == "record" else "detected"
-            counts[key] = counts.get(key, 0) + len(hit)
-            if agree is not None:
-                counts["agree"] = counts.get("agree", 0) + int(agree[hit].sum())
-        if len(hit) == 0:
+        found = _component_labels(chunk, position, (frames, depth, intr, label), target_cls, device, components, counts,
+                                  detector)
+        if found is None:
             return None
-        k_dev = torch.from_numpy(ks[hit]).to(device=device, dtype=torch.uint8)[:, None, None]
-        sel_f = torch.from_numpy(hit).to(device)
-        relabelled = torch.where(found_label.index_select(0, sel_f) == k_dev,
-                                 torch.full((), int(target_cls) + 1, dtype=torch.uint8, device=device),
-                                 torch.zeros((), dtype=torch.uint8, device=device))
-        frames = [frames[int(i)] for i in hit]
-        depth, intr, segment_iou = depth[hit], intr[hit], ious[hit]
-        agree = None if agree is None else agree[hit]
-        label = relabelled.cpu().numpy()
+        frames, depth, intr, label, segment_iou, agree = found
     r = seg_util.extract_segments(depth, label, intr, classes=[[target_cls]] * len(frames),
                                   quaternions=np.stack([f["quaternions"] for f in frames]),
                                   translations=np.stack([f["translations"] for f in frames]), num_point=num_point,
@@ -524,34 +474,69 @@ def element_from_frames(frames, target_cls, num_point, obj_models, seed=0, devic
     x = transform_object_model(get_rotation_matrix(get_object_model(x, models)))
     x = hpr.hidden_point_removal_org(hpr.sphericalFlip_org(x, None, 0.8 * math.pi), seed=int(seed))
     el["visiblePoints_org"] = x["visiblePoints_org"]
-    el["seq_id"] = np.array([int(frames[int(r.frame[i])]["seq_id"]) for i in keep], np.int64)
-    el["frame_id"] = np.array([int(frames[int(r.frame[i])]["frame_id"]) for i in keep], np.int64)
+    of = np.asarray(r.frame, np.int64)[keep]                                      # the kept samples' frames
+    el["seq_id"] = np.array([int(frames[i]["seq_id"]) for i in of], np.int64)
+    el["frame_id"] = np.array([int(frames[i]["frame_id"]) for i in of], np.int64)
     el["num_valid_points_in_segment"] = r.num_valid_points_in_segment[keep]
     if keep_frames:
-        of = np.asarray(r.frame, np.int64)[keep]
         el["frame_depth"] = torch.from_numpy(np.ascontiguousarray(depth[of].astype(np.uint16)).view(np.int16)).to(device)
         el["frame_intrinsics"] = torch.from_numpy(intr[of]).to(device)
     if keep_labels:
-        of = np.asarray(r.frame, np.int64)[keep]
         el["frame_label"] = torch.from_numpy(np.ascontiguousarray(label[of].astype(np.uint8))).to(device)
         el["frame_want"] = torch.full((B,), int(target_cls) + 1, dtype=torch.int32, device=device)
     if segment_iou is not None:
-        el["segment_iou"] = segment_iou[np.asarray(r.frame, np.int64)[keep]]
+        el["segment_iou"] = segment_iou[of]
     if agree is not None:
-        el["detect_agree"] = agree[np.asarray(r.frame, np.int64)[keep]]
+        el["detect_agree"] = agree[of]
     return el
 
 
-def _detected_components(chunk, position, found, found_label, label, depth, target_cls, components, detector):
+def _component_labels(chunk, position, held, target_cls, device, components, counts, detector):
+    """labels="components" of element_from_frames.  held: (frames, depth, intr, label) of the frames `position` of the call,
+    those that hold the class.  -> those of them that have a component for the class, their label images holding that
+    component alone as target_cls + 1, with the components' IoUs and, with a detector, whether the record's label agrees:
+    (frames, depth, intr, label, segment_iou, agree); None when no frame has one.  counts is updated either way."""
+    from .utils import depth_components as dc_util
+    frames, depth, intr, label = held
+    # every frame of the call is segmented, also those without the class: frame i of the call then has the global
+    # index first_frame + i whatever its neighbours hold
+    chunk_depth, chunk_intr = np.stack([f["depth"] for f in chunk]), record_intrinsics(chunk)
+    found = dc_util.segment_depth(chunk_depth, chunk_intr, device=device, **(components or {}))
+    found_label = found.label.index_select(0, torch.tensor(position, dtype=torch.int64, device=device))
+    ks, ious = dc_util.match_components(found_label, torch.from_numpy(np.ascontiguousarray(label, np.uint8)).to(device),
+                                        depth, int(target_cls) + 1)
+    agree = None
+    if detector is not None:
+        ks_record = ks
+        ks, ious = _detected_components(chunk_depth, chunk_intr, position, found, found_label, label, depth, target_cls,
+                                        components, detector)
+        agree = ks == ks_record
+    hit = np.nonzero(ks > 0)[0]
+    if counts is not None:
+        counts["frames"] = counts.get("frames", 0) + len(frames)
+        key = "matched" if detector is None else "detected"
+        counts[key] = counts.get(key, 0) + len(hit)
+        if agree is not None:
+            counts["agree"] = counts.get("agree", 0) + int(agree[hit].sum())
+    if len(hit) == 0:
+        return None
+    k_dev = torch.from_numpy(ks[hit]).to(device=device, dtype=torch.uint8)[:, None, None]
+    sel_f = torch.from_numpy(hit).to(device)
+    relabelled = torch.where(found_label.index_select(0, sel_f) == k_dev,
+                             torch.full((), int(target_cls) + 1, dtype=torch.uint8, device=device),
+                             torch.zeros((), dtype=torch.uint8, device=device))
+    return ([frames[int(i)] for i in hit], depth[hit], intr[hit], relabelled.cpu().numpy(), ious[hit],
+            None if agree is None else agree[hit])
+
+
+def _detected_components(chunk_depth, chunk_intr, position, found, found_label, label, depth, target_cls, components, detector):
     """For the frames `position` of the call: the label value (k + 1; 0: none) of the component that detect_objects assigned
     to target_cls, and that component's IoU against the record's target_cls + 1 pixels with depth (the report)."""
     from .utils import detect as detect_util
     device = found_label.device
     comp = components or {}
-    det = detect_util.detect_objects(
-        np.stack([f["depth"] for f in chunk]),
-        np.array([[f["fx"], f["fy"], f["cx"], f["cy"], f["factor_depth"]] for f in chunk], np.float32), segments=found,
-        seed=comp.get("seed", 0), first_frame=comp.get("first_frame", 0), **detector)
+    det = detect_util.detect_objects(chunk_depth, chunk_intr, segments=found, seed=comp.get("seed", 0),
+                                     first_frame=comp.get("first_frame", 0), **detector)
     ks = np.zeros(len(position), np.int64)
     for i, f in enumerate(position):
         mine = np.nonzero(det.table["det_class"][f] == int(target_cls))[0]
@@ -631,8 +616,67 @@ def main(argv=None):
     record's label (element_from_frames(choose="detect")); the last line then reads `detect class c frames n detected m
     agree a mean_iou x`: the frames that held the class, those in which a component was assigned to it, those of them in
     which the record's label would have picked the same component, and the mean IoU of the segments that were kept."""
-    from . import tfrecord_io
     from . import train_cloudAAE_ycbv as T
+    args = _arguments(argv)
+    torch.cuda.set_device(args.gpu)
+    obj_path = args.object_model or os.path.join(os.path.dirname(os.path.abspath(args.data_dir)),
+                                                 "object_model_tfrecord", "obj_models.tfrecords")
+    models, _ = tfrecord_io.read_and_decode_obj_model(obj_path)
+    graph = T.TrainGraph({"num_point": args.num_point, "gpu": args.gpu}, {}, {"batch_size": args.batch_size})
+    graph.restore(args.trained_model)
+    files = _record_files(args)
+    icp, model_normals = args.icp, None
+    if args.icp_plane:
+        icp = {'estimation': 'point_to_plane'}
+        # the normals of the 21 class models, once; a batch selects its classes' rows
+        model_normals = normals_util.estimate_normals(
+            torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda(), radius=NORMAL_RADIUS)[0]
+    sym_sets, sym_lines, sym_table = _symmetry_inputs(args, models, graph.device)
+    names = ("pred",) + (("icp",) if args.icp else ()) + (("ver",) if args.verify else ())      # the scored poses
+    log, bop, bop_log, verify, propose, detector = _scoring_inputs(args, models, names, sym_sets)
+    comp_counts, comp_iou, verify_rows = {}, [], []
+    comp = _components_inputs(args, comp_counts, detector)
+    batch_idx = 0
+    tot = {}                                     # sums of the batch lines' means, by key
+    for b in _batches(args, files, models, comp, comp_iou):
+        el_b = {k: v for k, v in b.items() if isinstance(v, torch.Tensor)}
+        if model_normals is not None:
+            el_b['obj_normals'] = model_normals.index_select(0, el_b['class_id'])
+        out = evaluate_batch(graph, el_b, icp=icp, score=args.score, bop=bop, symmetries=sym_table, verify=verify,
+                             propose=propose)
+        if verify is not None:
+            verify_rows.append((b["class_id"].to(torch.int64), out["verify_best"].to(torch.int64), out["verify_margin"]))
+        if bop_log is not None:
+            bop_log.append(b["class_id"], *[torch.stack([out[m + n] for n in bop_log.poses], dim=1)
+                                            for m in ("vsd_", "mssd_", "mspd_")],
+                           width=int(b["frame_depth"].shape[2]), seq=b["seq_id"], frame=b["frame_id"])
+        if log is not None:
+            log.append(b["class_id"], torch.stack([out["add_" + n] for n in log.poses], dim=1),
+                       torch.stack([out["adds_" + n] for n in log.poses], dim=1), seq=b["seq_id"], frame=b["frame_id"])
+        line, values = _batch_line(batch_idx, b, out, names, sym_table is not None)
+        for k, v in values.items():
+            tot[k] = tot.get(k, 0.0) + v
+        print(line)
+        batch_idx += 1
+    print("batch size %d" % batch_idx)
+    if batch_idx:
+        print("trans_loss %f axag_loss %f" % (tot["trans_loss"] / batch_idx, tot["axag_loss"] / batch_idx))
+        if sym_table is not None:
+            print(" ".join("%s %f" % (k, v / batch_idx) for k, v in tot.items() if k.endswith("_sym")))
+    lines = sym_lines + (log.lines() if log is not None else []) + (bop_log.lines() if bop_log is not None else [])
+    lines += verify_lines(verify_rows)
+    if propose is not None:
+        lines += propose_lines([r[:2] for r in verify_rows], verify['hypotheses'].max_members)
+    if args.labels == "components":
+        lines.append(_components_line(args, comp_counts, comp_iou))
+    for line in lines:
+        print(line)
+    sys.stdout.flush()
+    return 0
+
+
+def _arguments(argv):
+    """The command line's arguments, parsed and checked; --icp_plane sets --icp."""
     from .utils import depth_components as dc_util
     from .utils import detect as detect_util
     p = argparse.ArgumentParser()
@@ -702,193 +746,152 @@ def main(argv=None):
     if args.choose == "detect" and not (args.labels == "components" and args.meshes):
         p.error("--choose detect needs --labels components and --meshes DIR")
     args.icp = args.icp or args.icp_plane
-    torch.cuda.set_device(args.gpu)
-    obj_path = args.object_model or os.path.join(os.path.dirname(os.path.abspath(args.data_dir)),
-                                                 "object_model_tfrecord", "obj_models.tfrecords")
-    models, _ = tfrecord_io.read_and_decode_obj_model(obj_path)
-    graph = T.TrainGraph({"num_point": args.num_point, "gpu": args.gpu}, {}, {"batch_size": args.batch_size})
-    graph.restore(args.trained_model)
+    return args
+
+
+def _record_files(args):
+    """The frame record files to read: those of --files, or the class's test sequences under --data_dir that exist."""
     if args.files:
         files = [f for f in args.files.split(",") if f]
         missing = [f for f in files if not os.path.exists(f)]
         require(files and not missing, "--files: no such file: %s" % ", ".join(missing))
-    else:
-        files = [os.path.join(args.data_dir, str(i).zfill(4) + "_pcnn.tfrecord") for i in VALID_SEQ_ID[args.target_cls]]
-        files = [f for f in files if os.path.exists(f)]
-        require(files, "no <seq>_pcnn.tfrecord of class %d under %s" % (args.target_cls, args.data_dir))
-    pending, batch_idx, tot_trans, tot_axag, n_launch = None, 0, 0.0, 0.0, 0
-    tot_sym = {}                                 # sums of the *_sym means (--symmetries)
-    icp, model_normals = args.icp, None
-    if args.icp_plane:
-        icp = {'estimation': 'point_to_plane'}
-        # the normals of the 21 class models, once; a batch selects its classes' rows
-        model_normals = normals_util.estimate_normals(
-            torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda(), radius=NORMAL_RADIUS)[0]
-    sym_sets, sym_lines, sym_table = None, [], None
-    if args.symmetries != "none":
-        from .utils import symmetry as sym_util
-        if args.symmetries == "auto":
-            c = args.target_cls                      # the one class this run evaluates
-            if args.meshes:
-                from .utils import mesh_models
-                found = sym_util.symmetries_of_meshes([mesh_models.mesh_files(args.meshes)[c]], scale=args.mesh_scale,
-                                                      mesh_ids=[c])
-            else:
-                found = sym_util.symmetries_of_models(models[c:c + 1])
-            sym_sets = {c: found[0]["transforms"]}
-            sym_lines = sym_util.kind_lines(found, classes=[c])
-            sym_table = pose_equiv.SymmetryTable.from_results(found, len(models), [c], graph.device)
+        return files
+    files = [os.path.join(args.data_dir, str(i).zfill(4) + "_pcnn.tfrecord") for i in VALID_SEQ_ID[args.target_cls]]
+    files = [f for f in files if os.path.exists(f)]
+    require(files, "no <seq>_pcnn.tfrecord of class %d under %s" % (args.target_cls, args.data_dir))
+    return files
+
+
+def _frame_chunks(files, frames_per_launch):
+    """The decoded records of the files in order, frames_per_launch at a time; a chunk does not span two files."""
+    for fn in files:
+        buf = []
+        for rec in tfrecord_io.tf_record_iterator(fn):
+            buf.append(tfrecord_io.decode_frame(rec))
+            if len(buf) == frames_per_launch:
+                yield buf
+                buf = []
+        if buf:
+            yield buf
+
+
+def _batches(args, files, models, comp, comp_iou):
+    """The elements of the record files, one per chunk of frames (its seed --seed + the chunk's number), cut into batches
+    of --batch_size, host and device entries alike; a last smaller batch is not given.  comp: _components_inputs, whose
+    first_frame is set per chunk; the kept segments' IoUs are added to comp_iou."""
+    pending, n_frames_seen = None, 0
+    for n_launch, chunk in enumerate(_frame_chunks(files, args.frames_per_launch)):
+        if comp:
+            comp["components"]["first_frame"] = n_frames_seen
+        el = element_from_frames(chunk, args.target_cls, args.num_point, models, seed=args.seed + n_launch,
+                                 keep_frames=args.bop or args.verify, keep_labels=args.verify, **comp)
+        n_frames_seen += len(chunk)
+        if el is None:
+            continue
+        if "segment_iou" in el:
+            comp_iou.append(el["segment_iou"])
+        pending = el if pending is None else {k: (torch.cat([pending[k], v]) if isinstance(v, torch.Tensor)
+                                                  else np.concatenate([pending[k], v])) for k, v in el.items()}
+        while len(pending["class_id"]) >= args.batch_size:
+            yield _take(pending, 0, args.batch_size)
+            pending = _take(pending, args.batch_size, len(pending["class_id"]))
+
+
+def _components_line(args, counts, ious):
+    """The closing line of --labels components, or of --choose detect: the frames that held the class, those with a
+    component for it (and, detected, those where the record's label agrees), and the mean IoU of the kept segments."""
+    iou = float(np.concatenate(ious).mean()) if ious else 0.0
+    if args.choose == "detect":
+        return "detect class %d frames %d detected %d agree %d mean_iou %f" % (
+            args.target_cls, counts.get("frames", 0), counts.get("detected", 0), counts.get("agree", 0), iou)
+    return "components class %d frames %d matched %d mean_iou %f" % (
+        args.target_cls, counts.get("frames", 0), counts.get("matched", 0), iou)
+
+
+def _symmetry_inputs(args, models, device):
+    """--symmetries -> (sym_sets {class: [n,4,4]} or None, the lines that report them, the SymmetryTable or None)."""
+    if args.symmetries == "none":
+        return None, [], None
+    from .utils import symmetry as sym_util
+    if args.symmetries == "auto":
+        c = args.target_cls                      # the one class this run evaluates
+        if args.meshes:
+            found = sym_util.symmetries_of_meshes([mesh_models.mesh_files(args.meshes)[c]], scale=args.mesh_scale, mesh_ids=[c])
         else:
-            require(os.path.exists(args.symmetries), "--symmetries: no such file: %s" % args.symmetries)
-            sym_sets = sym_util.load_symmetries(args.symmetries)
-            sym_table = pose_equiv.load_symmetry_table(args.symmetries, len(models), graph.device)
-            sym_lines = ["symmetry class %d transforms %d" % (c, len(t)) for c, t in sorted(sym_sets.items())]
-    names = ("pred",) + (("icp",) if args.icp else ()) + (("ver",) if args.verify else ())      # the scored poses
-    log = None
+            found = sym_util.symmetries_of_models(models[c:c + 1])
+        return ({c: found[0]["transforms"]}, sym_util.kind_lines(found, classes=[c]),
+                pose_equiv.SymmetryTable.from_results(found, len(models), [c], device))
+    require(os.path.exists(args.symmetries), "--symmetries: no such file: %s" % args.symmetries)
+    sym_sets = sym_util.load_symmetries(args.symmetries)
+    return (sym_sets, ["symmetry class %d transforms %d" % (c, len(t)) for c, t in sorted(sym_sets.items())],
+            pose_equiv.load_symmetry_table(args.symmetries, len(models), device))
+
+
+def _scoring_inputs(args, models, names, sym_sets):
+    """What --score, --bop, --verify, --propose and --choose detect need -> (log, bop, bop_log, verify, propose, detector),
+    None where the option is off.  The mesh directory is packed once and the class models' diameters are taken once: the
+    consumers get the same PackedMeshes, which none of them writes into (they pass its tensors to the kernels as inputs)."""
+    c = args.target_cls
+    log = bop = bop_log = verify = propose = detector = None
+    if args.score or args.bop:
+        diam = score_util.model_diameter(torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda())
+    if args.bop or args.verify or args.choose == "detect":
+        mesh_paths = mesh_models.mesh_files(args.meshes)
+        packed = mesh_models.pack_meshes(mesh_paths, args.mesh_scale)
     if args.score:
-        diam = score_util.model_diameter(torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda())
-        if sym_sets is None:
-            log = score_util.PoseScoreLog(names, diameters=diam)
-        else:
-            log = score_util.PoseScoreLog(names, diameters=diam,
-                                          symmetric=[c for c, t in sym_sets.items() if len(t) > 1])
-    bop, bop_log = None, None
+        symmetric = {} if sym_sets is None else dict(symmetric=[k for k, t in sym_sets.items() if len(t) > 1])
+        log = score_util.PoseScoreLog(names, diameters=diam, **symmetric)
     if args.bop:
-        from .utils import mesh_models
-        diam = score_util.model_diameter(torch.from_numpy(np.ascontiguousarray(models, np.float32)).cuda())
-        bop = dict(meshes=mesh_models.pack_meshes(mesh_models.mesh_files(args.meshes), args.mesh_scale), diameters=diam)
+        bop = dict(meshes=packed, diameters=diam)
         if sym_sets is not None:
             bop['symmetries'] = sym_sets
         bop_log = bop_util.BopScoreLog(names, diameters=diam)
-    verify, verify_rows = None, []
     if args.verify:
-        from .utils import mesh_models
-        c = args.target_cls
-        verify = dict(meshes=bop['meshes'] if bop is not None else
-                      mesh_models.pack_meshes(mesh_models.mesh_files(args.meshes), args.mesh_scale),
-                      hypotheses=verify_util.HypothesisTable.from_models(models[c:c + 1], [c], len(models)),
+        verify = dict(meshes=packed, hypotheses=verify_util.HypothesisTable.from_models(models[c:c + 1], [c], len(models)),
                       tau=args.verify_tau)
-    propose = None
     if args.propose:
-        c = args.target_cls
-        propose = dict(models=ppf_util.PPFModels.from_meshes([mesh_models.mesh_files(args.meshes)[c]], num_point=args.propose_points,
+        propose = dict(models=ppf_util.PPFModels.from_meshes([mesh_paths[c]], num_point=args.propose_points,
                                                               scale=args.mesh_scale, classes=[c], num_class=len(models)),
                        top=args.propose_top)
-
-    detector = None
     if args.choose == "detect":
-        from .utils import mesh_models
-        mesh_paths = mesh_models.mesh_files(args.meshes)
         det_classes = (list(range(len(mesh_paths))) if args.detect_classes is None
-                       else [int(c) for c in args.detect_classes.split(",") if c])
+                       else [int(k) for k in args.detect_classes.split(",") if k])
         num, den = (int(x) for x in args.detect_min_score.split("/"))
-        detector = dict(meshes=mesh_models.pack_meshes(mesh_paths, args.mesh_scale),
-                        ppf_models=ppf_util.PPFModels.from_meshes([mesh_paths[c] for c in det_classes],
+        detector = dict(meshes=packed,
+                        ppf_models=ppf_util.PPFModels.from_meshes([mesh_paths[k] for k in det_classes],
                                                                   num_point=args.propose_points, scale=args.mesh_scale,
                                                                   classes=det_classes, num_class=len(mesh_paths)),
                         classes=det_classes, top=args.detect_top, min_score=(num, den), margin=args.detect_margin,
                         num_point=args.num_point)
+    return log, bop, bop_log, verify, propose, detector
 
-    def frames():
-        for fn in files:
-            buf = []
-            for rec in tfrecord_io.tf_record_iterator(fn):
-                buf.append(tfrecord_io.decode_frame(rec))
-                if len(buf) == args.frames_per_launch:
-                    yield buf
-                    buf = []
-            if buf:
-                yield buf
 
-    comp_counts, comp_iou, n_frames_seen = {}, [], 0
-    for chunk in frames():
-        comp = {}
-        if args.labels == "components":
-            comp = dict(labels="components", counts=comp_counts,
-                        components=dict(seed=args.seed, first_frame=n_frames_seen, n_hyp=args.components_n_hyp,
-                                        stride=args.components_stride, tol=args.components_tol,
-                                        max_height=args.components_max_height,
-                                        min_plane_percent=args.components_min_plane_percent, jump=args.components_jump,
-                                        min_pixels=args.components_min_pixels, max_components=args.components_max))
-            if args.components_creases:
-                comp["components"]["creases"] = dict(step=args.components_crease_step, smooth=args.components_crease_smooth,
-                                                     angle=args.components_crease_angle)
-            if detector is not None:
-                comp.update(choose="detect", detector=detector)
-        el = element_from_frames(chunk, args.target_cls, args.num_point, models, seed=args.seed + n_launch,
-                                 keep_frames=args.bop or args.verify, keep_labels=args.verify, **comp)
-        n_launch += 1
-        n_frames_seen += len(chunk)
-        if el is not None and "segment_iou" in el:
-            comp_iou.append(el["segment_iou"])
-        if el is None:
-            continue
-        pending = el if pending is None else {k: (torch.cat([pending[k], v]) if isinstance(v, torch.Tensor)
-                                                  else np.concatenate([pending[k], v])) for k, v in el.items()}
-        while len(pending["class_id"]) >= args.batch_size:
-            b = _take(pending, 0, args.batch_size)
-            pending = _take(pending, args.batch_size, len(pending["class_id"]))
-            el_b = {k: v for k, v in b.items() if isinstance(v, torch.Tensor)}
-            if model_normals is not None:
-                el_b['obj_normals'] = model_normals.index_select(0, el_b['class_id'])
-            out = evaluate_batch(graph, el_b, icp=icp, score=args.score, bop=bop, symmetries=sym_table, verify=verify,
-                                 propose=propose)
-            if verify is not None:
-                verify_rows.append((b["class_id"].to(torch.int64), out["verify_best"].to(torch.int64), out["verify_margin"]))
-            if bop_log is not None:
-                bop_log.append(b["class_id"], *[torch.stack([out[m + n] for n in bop_log.poses], dim=1)
-                                                for m in ("vsd_", "mssd_", "mspd_")],
-                               width=int(b["frame_depth"].shape[2]), seq=b["seq_id"], frame=b["frame_id"])
-            if log is not None:
-                log.append(b["class_id"], torch.stack([out["add_" + n] for n in log.poses], dim=1),
-                           torch.stack([out["adds_" + n] for n in log.poses], dim=1), seq=b["seq_id"], frame=b["frame_id"])
-            tl, al = float(out["trans_loss"]), float(out["axag_loss"])
-            tot_trans += tl
-            tot_axag += al
-            line = "Validation batch %d seq_id %d frame_id %d trans_loss %f rot_loss %f" % (
-                batch_idx, int(b["seq_id"][0]), int(b["frame_id"][0]), tl, al)
-            if args.icp:
-                line += " trans_loss_icp %f rot_loss_icp %f" % (float(out["trans_loss_icp"]), float(out["axag_loss_icp"]))
-            if args.verify:
-                line += " trans_loss_ver %f rot_loss_ver %f" % (float(out["trans_loss_ver"]), float(out["axag_loss_ver"]))
-            if sym_table is not None:
-                for k in (("trans_loss_sym", "axag_loss_sym") + (("trans_loss_icp_sym", "axag_loss_icp_sym") if args.icp else ()) +
-                          (("trans_loss_ver_sym", "axag_loss_ver_sym") if args.verify else ())):
-                    tot_sym[k] = tot_sym.get(k, 0.0) + float(out[k])
-                    line += " %s %f" % (k.replace("axag", "rot"), float(out[k]))
-            print(line)
-            batch_idx += 1
-    print("batch size %d" % batch_idx)
-    if batch_idx:
-        print("trans_loss %f axag_loss %f" % (tot_trans / batch_idx, tot_axag / batch_idx))
-        if tot_sym:
-            print(" ".join("%s %f" % (k, v / batch_idx) for k, v in tot_sym.items()))
-    for line in sym_lines:
-        print(line)
-    if log is not None:
-        for line in log.lines():
-            print(line)
-    if bop_log is not None:
-        for line in bop_log.lines():
-            print(line)
-    for line in verify_lines(verify_rows):
-        print(line)
-    if propose is not None:
-        for line in propose_lines([r[:2] for r in verify_rows], verify['hypotheses'].max_members):
-            print(line)
-    if args.choose == "detect":
-        iou = np.concatenate(comp_iou) if comp_iou else np.zeros(0)
-        print("detect class %d frames %d detected %d agree %d mean_iou %f" % (args.target_cls, comp_counts.get("frames", 0),
-                                                                              comp_counts.get("detected", 0),
-                                                                              comp_counts.get("agree", 0),
-                                                                              float(iou.mean()) if len(iou) else 0.0))
-    elif args.labels == "components":
-        iou = np.concatenate(comp_iou) if comp_iou else np.zeros(0)
-        print("components class %d frames %d matched %d mean_iou %f" % (args.target_cls, comp_counts.get("frames", 0),
-                                                                        comp_counts.get("matched", 0),
-                                                                        float(iou.mean()) if len(iou) else 0.0))
-    sys.stdout.flush()
-    return 0
+def _components_inputs(args, counts, detector):
+    """The labels, components, counts, choose and detector arguments of element_from_frames under --labels components
+    (first_frame is set per chunk); nothing otherwise."""
+    if args.labels != "components":
+        return {}
+    comp = dict(labels="components", counts=counts,
+                components=dict(seed=args.seed, first_frame=0, n_hyp=args.components_n_hyp, stride=args.components_stride,
+                                tol=args.components_tol, max_height=args.components_max_height,
+                                min_plane_percent=args.components_min_plane_percent, jump=args.components_jump,
+                                min_pixels=args.components_min_pixels, max_components=args.components_max))
+    if args.components_creases:
+        comp["components"]["creases"] = dict(step=args.components_crease_step, smooth=args.components_crease_smooth,
+                                             angle=args.components_crease_angle)
+    if detector is not None:
+        comp.update(choose="detect", detector=detector)
+    return comp
+
+
+def _batch_line(batch_idx, b, out, names, with_sym):
+    """(the line of one batch, {key: value} of the means it prints): the errors of the poses `names` in turn, then,
+    with_sym, their _sym twins in the same order; axag is printed as rot."""
+    tags = ["" if n == "pred" else "_" + n for n in names]
+    keys = [k + tag + sym for sym in (("", "_sym") if with_sym else ("",)) for tag in tags for k in ("trans_loss", "axag_loss")]
+    values = {k: float(out[k]) for k in keys}
+    line = "Validation batch %d seq_id %d frame_id %d" % (batch_idx, int(b["seq_id"][0]), int(b["frame_id"][0]))
+    return line + "".join(" %s %f" % (k.replace("axag", "rot"), v) for k, v in values.items()), values
 
 
 if __name__ == "__main__":

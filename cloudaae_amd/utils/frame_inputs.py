@@ -68,6 +68,11 @@ def on_device(x, dtype, dev, shape=None, name=None):
     return t
 
 
+def record_intrinsics(frames):
+    """Decoded frame records (tfrecord_io.decode_frame) -> float32 [F,5] on the host: each record's intrinsics row."""
+    return np.array([[fr[k] for k in ("fx", "fy", "cx", "cy", "factor_depth")] for fr in frames], np.float32)
+
+
 def intrinsics_per_frame(intrinsics, F):
     """Intrinsics [5] or [F,5] -> float32 [F,5] on the host, one row per frame."""
     return np.ascontiguousarray(np.broadcast_to(host(intrinsics, np.float32).reshape(-1, 5), (F, 5)))

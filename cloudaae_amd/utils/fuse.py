@@ -22,7 +22,7 @@ import torch
 from .. import _lib
 from .._lib import ptr, require, stream
 from . import render
-from .frame_inputs import depth_frames, host, on_device
+from .frame_inputs import depth_frames, host, on_device, record_intrinsics
 
 # choices, not measurements on data
 FRONT_VOXELS = 4.0        # the truncation in front of a surface, and the deep band's far end behind it
@@ -220,17 +220,14 @@ def class_frames(path, target_cls, every=1):
     [F,H,W] uint16, label [F,H,W] uint8, intrinsics [F,5] float32, the record's poses of the class [F,4,4] float64, the
     frames' records)."""
     from .. import tfrecord_io
-    from .track import quat2mat
+    from .track import record_poses
     require(every >= 1, "--every must be >= 1")
     frames = [fr for fr in list(tfrecord_io.read_frames(path))[::every] if bool(fr["class_one_hot"][target_cls])]
     require(len(frames) >= 1, "no frame of %s shows class %d" % (path, target_cls))
     depth = np.stack([fr["depth"] for fr in frames])
     label = np.stack([fr["label"] for fr in frames]).astype(np.uint8)
-    intr = np.array([[fr[k] for k in ("fx", "fy", "cx", "cy", "factor_depth")] for fr in frames], np.float32)
-    poses = np.tile(np.eye(4), (len(frames), 1, 1))
-    for f, fr in enumerate(frames):
-        poses[f, :3, :3], poses[f, :3, 3] = quat2mat(fr["quaternions"][target_cls]), fr["translations"][target_cls]
-    return depth, label, intr, poses, frames
+    poses = np.concatenate([record_poses(fr, [target_cls]) for fr in frames])
+    return depth, label, record_intrinsics(frames), poses, frames
 
 
 def main(argv=None):

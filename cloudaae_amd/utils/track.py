@@ -22,7 +22,7 @@ import torch
 from .. import _lib
 from .._lib import ptr, require, stream
 from . import detect, mesh_models, render
-from .frame_inputs import check_depth, check_int32, depth_frames, host, intrinsics_per_frame
+from .frame_inputs import check_depth, check_int32, depth_frames, host, intrinsics_per_frame, record_intrinsics
 from .pose_verify import tau_units
 
 # choices, not measurements
@@ -471,6 +471,14 @@ def quat2mat(q):
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
+def record_poses(fr, classes):
+    """The poses that the frame record fr holds for `classes`, model -> camera: [len(classes),4,4] float64."""
+    out = np.tile(np.eye(4), (len(classes), 1, 1))
+    for i, c in enumerate(classes):
+        out[i, :3, :3], out[i, :3, 3] = quat2mat(fr["quaternions"][c]), fr["translations"][c]
+    return out
+
+
 def pose_errors(T, truth):
     """(rotation error in degrees, translation error in metres) of T against truth."""
     c = (np.trace(T[:3, :3] @ truth[:3, :3].T) - 1.0) / 2.0
@@ -496,18 +504,11 @@ def main(argv=None):
     classes = [int(c) for c in np.nonzero(frames[0]["class_one_hot"])[0] if c < len(packed.num_triangles)]
     require(len(classes) >= 1, "the first frame names no class that has a mesh")
 
-    def truth(fr):
-        out = np.tile(np.eye(4), (len(classes), 1, 1))
-        for i, c in enumerate(classes):
-            out[i, :3, :3], out[i, :3, 3] = quat2mat(fr["quaternions"][c]), fr["translations"][c]
-        return out
-
     depth = np.stack([fr["depth"] for fr in frames])
-    intr = np.array([[fr[k] for k in ("fx", "fy", "cx", "cy", "factor_depth")] for fr in frames], np.float32)
-    t = track_objects(depth, intr, packed, (classes, truth(frames[0])), motion=args.motion, iterations=args.iterations,
-                      contour=True if args.contour else None)
+    t = track_objects(depth, record_intrinsics(frames), packed, (classes, record_poses(frames[0], classes)), motion=args.motion,
+                      iterations=args.iterations, contour=True if args.contour else None)
     for f, fr in enumerate(frames):
-        gt = truth(fr)
+        gt = record_poses(fr, classes)
         for i, c in enumerate(classes):
             here = bool(fr["class_one_hot"][c])
             rot, trans = pose_errors(t.poses[f, i], gt[i]) if here else (float("nan"), float("nan"))
