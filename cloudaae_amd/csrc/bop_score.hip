@@ -16,6 +16,7 @@
 //                            on the bit pattern of the non-negative double (wave, LDS, one atomic per workgroup, symmetry
 //                            and error); a second launch takes the minimum over the symmetries and the square root.
 #include "common.h"
+#include "depth_frame.h"
 #include "pose_math.h"
 #include "../../include/cloudaae_hip.h"
 
@@ -32,8 +33,6 @@ constexpr int VS_PIX = 8;                          // pixels of a thread
 constexpr int VS_TILE = VS_BLOCK * VS_PIX;         // pixels of a workgroup
 constexpr int VS_MAX_K = 16;                       // thresholds tau of a call (a choice: they live in registers)
 constexpr int VS_SLOTS = 3 + VS_MAX_K;             // inter, union, visib_gt, over[k]
-constexpr long long VS_MAX_PIXELS = 1ll << 24;     // H W
-constexpr long long VS_MAX_TOTAL = 1ll << 28;      // B P H W
 
 struct VsdArgs {
     int f, h, w, b, p, k, tiles;
@@ -247,8 +246,8 @@ CLOUDAAE_API int cloudaae_vsd_counts(int f, int h, int w, const uint16_t *depth_
     const char *name = "cloudaae_vsd_counts";
     CLOUDAAE_REQUIRE(f >= 1 && h >= 1 && w >= 1 && b >= 1 && p >= 1, name, "f, h, w, b and p must be >= 1");
     CLOUDAAE_REQUIRE(k >= 1 && k <= VS_MAX_K, name, "k must lie in [1, 16]");
-    CLOUDAAE_REQUIRE((long long)h * w <= VS_MAX_PIXELS, name, "h * w above 2^24");
-    CLOUDAAE_REQUIRE((long long)b * p <= VS_MAX_TOTAL && (long long)b * p * ((long long)h * w) <= VS_MAX_TOTAL, name,
+    CLOUDAAE_REQUIRE((long long)h * w <= FRAME_MAX_PIXELS, name, "h * w above 2^24");
+    CLOUDAAE_REQUIRE((long long)b * p <= FRAME_MAX_TOTAL && (long long)b * p * ((long long)h * w) <= FRAME_MAX_TOTAL, name,
                      "b * p * h * w above 2^28");
     CLOUDAAE_REQUIRE(!isnan(delta), name, "delta is not a number");
     CLOUDAAE_REQUIRE(depth_test && intrinsics && frame_of && depth_gt && depth_est && tau && inter && uni && over && visib_gt,

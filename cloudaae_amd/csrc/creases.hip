@@ -15,6 +15,8 @@
 // Frame borders and partial tiles are predicates (a staged -1), never padding.  Every loop is bounded by smooth, step or
 // the tile; no workgroup waits for another.
 #include "common.h"
+#include "depth_frame.h"
+#include "workspace.h"
 #include "../../include/cloudaae_hip.h"
 
 namespace cloudaae {
@@ -28,8 +30,6 @@ constexpr int CR_MAX_STEP = 8, CR_MAX_SMOOTH = 7;
 constexpr int CR_SMOOTH_SIDE = CR_TW + 2 * CR_MAX_SMOOTH;          // 46: 46 x 46 ints = 8 464 bytes
 constexpr size_t CR_CELL_BYTES = 3 * sizeof(double) + sizeof(int);   // a staged pixel of the test: its point, its raw depth
 constexpr size_t CR_MAX_LDS = (size_t)(CR_TW + 2 * CR_MAX_STEP) * (CR_TH + 2 * CR_MAX_STEP) * CR_CELL_BYTES;
-constexpr long long CR_MAX_PIXELS = 1ll << 24;                    // the limits of cloudaae_depth_components
-constexpr long long CR_MAX_TOTAL = 1ll << 28;
 
 struct CrArgs {
     int f, h, w, tx, ty, step, smooth;
@@ -108,8 +108,7 @@ __global__ __launch_bounds__(CR_BLOCK) void depth_creases_test_kernel(CrArgs a)
     double *px = cr_lds, *py = px + cells, *pz = py + cells;
     int *raw = (int *)(pz + cells);
     const size_t base = (size_t)fr * ((size_t)a.h * a.w);
-    const float *k = a.intrinsics + 5 * (size_t)fr;
-    const double fx = (double)k[0], fy = (double)k[1], cx = (double)k[2], cy = (double)k[3], factor = (double)k[4];
+    const Pinhole<double> cam = pinhole<double>(a.intrinsics + 5 * (size_t)fr);
     const long long reach = (long long)s * (long long)a.jump_units[fr];
     for (int e = tid; e < cells; e += CR_BLOCK) {
         const int x = x0 - s + e % side, y = y0 - s + e / side;
@@ -119,13 +118,10 @@ __global__ __launch_bounds__(CR_BLOCK) void depth_creases_test_kernel(CrArgs a)
             continue;                              // no foreground: no float64 work, and its point is never read
         const unsigned word = a.smooth_map[base + (size_t)y * a.w + x];
         const unsigned n = word & 255u;
-        double X = 0.0, Y = 0.0, Z = 0.0;
-        if (n) {                                   // (n = 0 only in a frame with jump_units < 0, where nothing is tested)
-            Z = (double)(word >> 8) / ((double)n * factor);
-            X = (((double)x - cx) * Z) / fx;
-            Y = (((double)y - cy) * Z) / fy;
-        }
-        px[e] = X, py[e] = Y, pz[e] = Z;
+        double P[3] = {0.0, 0.0, 0.0};
+        if (n)                                     // (n = 0 only in a frame with jump_units < 0, where nothing is tested)
+            backproject_metres(cam, x, y, (double)(word >> 8) / ((double)n * cam.factor), P);
+        px[e] = P[0], py[e] = P[1], pz[e] = P[2];
     }
     __syncthreads();
     int flagged = 0;
@@ -181,20 +177,15 @@ __global__ __launch_bounds__(CR_BLOCK) void depth_creases_test_kernel(CrArgs a)
     }
 }
 
-static bool cr_within_limits(long long f, long long h, long long w)
-{
-    return f >= 0 && h >= 1 && w >= 1 && h * w <= CR_MAX_PIXELS && f * h * w <= CR_MAX_TOTAL;
-}
-
 } // namespace cloudaae
 
 using namespace cloudaae;
 
 CLOUDAAE_API long long cloudaae_depth_creases_workspace_bytes(int f, int h, int w)
 {
-    if (!cr_within_limits(f, h, w))
+    if (!frame_within_limits(0, f, h, w))
         return 0;
-    return (long long)((sizeof(unsigned) * (size_t)f * h * w + 1 + 255) / 256 * 256);
+    return (long long)workspace_pad(sizeof(unsigned) * (size_t)f * h * w + 1);
 }
 
 CLOUDAAE_API int cloudaae_depth_creases(int f, int h, int w, const uint16_t *depth, const uint8_t *fg, const float *intrinsics,
@@ -203,7 +194,7 @@ CLOUDAAE_API int cloudaae_depth_creases(int f, int h, int w, const uint16_t *dep
                                         long long workspace_bytes, cloudaae_stream_t stream)
 {
     const char *name = "cloudaae_depth_creases";
-    CLOUDAAE_REQUIRE(cr_within_limits(f, h, w), name, "outside the limits: f >= 0; h, w >= 1; h * w <= 2^24; f * h * w <= 2^28");
+    CLOUDAAE_REQUIRE(frame_within_limits(0, f, h, w), name, CLOUDAAE_FRAME_LIMITS_F0);
     CLOUDAAE_REQUIRE(step >= 1 && step <= CR_MAX_STEP && smooth >= 0 && smooth <= CR_MAX_SMOOTH && cos2 >= 0.0 && cos2 <= 1.0,
                      name, "outside the limits: 1 <= step <= 8; 0 <= smooth <= 7; cos2 a number in [0, 1]");
     if (f == 0)

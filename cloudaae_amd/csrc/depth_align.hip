@@ -16,8 +16,8 @@
 // plain loads, as in depth_noise.hip: neighbouring lanes share their cache lines.
 //
 // Here are the pairing, the normals of the two depth images and the plane row.  What the step shares with the contour term
-// of depth_contour.hip is in depth_gn.h: the limits and the launch shape (gn_within_limits, gn_runs), the window's camera and
-// the bounds-checked depth load (GnCam, gn_backproject, gn_depth), the 28 sums of a row (gn_add_row), the workgroup's
+// of depth_contour.hip is in depth_gn.h: the limits and the launch shape (gn_within_limits, gn_runs), the bounds-checked
+// depth load (gn_depth; the window's camera and its back-projection are depth_frame.h's), the 28 sums of a row (gn_add_row), the workgroup's
 // reduction (gn_store_run), the sum over a sample's runs (gn_add_runs), the LDL^T solve with x -> U (gn_solve) and the
 // write of U pose_in (gn_write_update).  icp_plane_update of icp.hip restates that factorisation on its own layout of sums.
 #include "common.h"
@@ -43,18 +43,18 @@ __device__ __forceinline__ int da_depth(const DaImage &im, int x, int y)
 }
 
 // the neighbour (x, y) of a pixel of depth zs: valid when inside the image, with depth, and within `jump` units of zs
-__device__ __forceinline__ bool da_tap(const DaImage &im, const GnCam &c, int x, int y, int zs, int jump, double (&p)[3])
+__device__ __forceinline__ bool da_tap(const DaImage &im, const Pinhole<double> &c, int x, int y, int zs, int jump, double (&p)[3])
 {
     const int z = da_depth(im, x, y);
     const int diff = z - zs, mag = diff < 0 ? -diff : diff;
     if (z == 0 || mag > jump)
         return false;
-    gn_backproject(c, x, y, z, p);
+    backproject(c, x, y, z, p);
     return true;
 }
 
 // the difference along one axis: central when both neighbours are valid, one-sided with the valid one, else none
-__device__ __forceinline__ bool da_axis(const DaImage &im, const GnCam &c, int x, int y, int dx, int dy, int zs, int jump,
+__device__ __forceinline__ bool da_axis(const DaImage &im, const Pinhole<double> &c, int x, int y, int dx, int dy, int zs, int jump,
                                        const double (&centre)[3], double (&g)[3])
 {
     double lo[3], hi[3];
@@ -69,7 +69,7 @@ __device__ __forceinline__ bool da_axis(const DaImage &im, const GnCam &c, int x
 
 // The unsigned unit normal of the image at window pixel (x, y), whose depth zs is not 0 and whose point is `centre`.
 // false: the pixel is flat.
-__device__ __forceinline__ bool da_normal(const DaImage &im, const GnCam &c, int x, int y, int zs, int jump,
+__device__ __forceinline__ bool da_normal(const DaImage &im, const Pinhole<double> &c, int x, int y, int zs, int jump,
                                          const double (&centre)[3], double (&n)[3])
 {
     double gx[3], gy[3];
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(GN_BLOCK) void depth_align_sums_kernel(DepthAlignAr
     const int q0 = tile * GN_RUN + tid * GN_PIX;   // the lane's first window pixel (may lie past n)
     const int gate = a.gate[s], jump = a.jump[s];
     const bool use_normals = a.cos_min > 0.0;
-    const GnCam cam = gn_cam(a.intr_win + 5 * (size_t)s);
+    const Pinhole<double> cam = pinhole<double>(a.intr_win + 5 * (size_t)s);
     DaImage hyp, test;
     hyp.pix = a.depth_hyp + (size_t)s * n;
     hyp.h = a.wh, hyp.w = a.ww, hyp.ox = 0, hyp.oy = 0;
@@ -132,8 +132,8 @@ __global__ __launch_bounds__(GN_BLOCK) void depth_align_sums_kernel(DepthAlignAr
             const int diff = d - t, mag = diff < 0 ? -diff : diff;
             if (d != 0 && t != 0 && mag <= gate) {
                 double p[3], q[3], nh[3], mo[3];
-                gn_backproject(cam, x, y, d, p);
-                gn_backproject(cam, x, y, t, q);
+                backproject(cam, x, y, d, p);
+                backproject(cam, x, y, t, q);
                 bool pair = da_normal(hyp, cam, x, y, d, jump, p, nh);
                 if (pair && use_normals) {
                     pair = da_normal(test, cam, x, y, t, jump, q, mo);

@@ -23,7 +23,9 @@
 // Every device loop has a bound: a walk along label words ends after as many steps as the tile or the frame has pixels
 // (labels only ever decrease along a walk, so a correct walk is shorter) and sets a bit of the frame's status otherwise.
 #include "common.h"
+#include "depth_frame.h"
 #include "philox.h"
+#include "workspace.h"
 #include "../../include/cloudaae_hip.h"
 
 namespace cloudaae {
@@ -33,8 +35,6 @@ typedef unsigned long long u64;
 constexpr int DC_BLOCK = 256;
 constexpr int DC_WAVES = DC_BLOCK / 64;
 constexpr unsigned DC_STREAM_PLANE = 25u;          // r0..r2 of counter ((first_frame + f) << 20) | h: the three pixels
-constexpr long long DC_MAX_PIXELS = 1ll << 24;     // H W
-constexpr long long DC_MAX_TOTAL = 1ll << 28;      // F H W
 constexpr int DC_MAX_HYP = 4096;
 constexpr long long DC_MAX_FIRST_FRAME = 1ll << 40;
 constexpr int DC_MAX_COMPONENTS = 254;
@@ -46,17 +46,13 @@ constexpr int DC_TILE = DC_TW * DC_TH;
 constexpr int DC_TILE_PASSES = DC_TILE / DC_BLOCK;
 constexpr int DC_STATUS_TILE = 1, DC_STATUS_SEAM = 2, DC_STATUS_FLATTEN = 4;
 
-// pixel p of frame fr, back-projected as segment.hip does (fp32, no fma, correctly rounded division), then widened
+// pixel p of frame fr, back-projected in fp32 as the frame segments are, then widened
 __device__ __forceinline__ void dc_point(const float *intrinsics, int fr, int w, int p, unsigned short d, double &x, double &y,
                                          double &z)
 {
-    const float *k = intrinsics + 5 * (size_t)fr;
-    const float fx = k[0], fy = k[1], cx = k[2], cy = k[3], factor = k[4];
-    const int u = p % w, v = p / w;
-    const float dm = (float)d / factor;
-    x = (double)((((float)u - cx) * dm) / fx);
-    y = (double)((((float)v - cy) * dm) / fy);
-    z = (double)dm;
+    float q[3];
+    backproject(pinhole<float>(intrinsics + 5 * (size_t)fr), p % w, p / w, d, q);
+    x = (double)q[0], y = (double)q[1], z = (double)q[2];
 }
 
 struct DcPlane {
@@ -467,7 +463,7 @@ __global__ __launch_bounds__(DC_BLOCK) void component_select_kernel(ClArgs a)
         u64 best = 0;
         for (int i = tid; i < n; i += DC_BLOCK) {
             const int r = a.cand[base + i];
-            const u64 key = ((u64)(unsigned)a.size[base + r] << 24) | (u64)(DC_MAX_PIXELS - 1 - r);
+            const u64 key = ((u64)(unsigned)a.size[base + r] << 24) | (u64)(FRAME_MAX_PIXELS - 1 - r);
             best = key < below && key > best ? key : best;
         }
         best = wave_max_u64(best);
@@ -484,7 +480,7 @@ __global__ __launch_bounds__(DC_BLOCK) void component_select_kernel(ClArgs a)
         below = best;
         keep = k + 1;
         if (tid == 0) {
-            const int r = (int)(DC_MAX_PIXELS - 1 - (long long)(best & (u64)(DC_MAX_PIXELS - 1)));
+            const int r = (int)(FRAME_MAX_PIXELS - 1 - (long long)(best & (u64)(FRAME_MAX_PIXELS - 1)));
             const size_t o = (size_t)fr * a.max_components + k;
             a.comp_root[o] = r;
             a.comp_size[o] = (int)(best >> 24);
@@ -547,12 +543,24 @@ __global__ __launch_bounds__(DC_BLOCK) void component_label_kernel(ClArgs a)
     }
 }
 
-static bool dc_within_limits(long long f, long long h, long long w)
-{
-    return f >= 0 && h >= 1 && w >= 1 && h * w <= DC_MAX_PIXELS && f * h * w <= DC_MAX_TOTAL;
-}
+// The workspace of cloudaae_component_labels (null: the size alone is asked for): counts = size [m] | rank [m] | ncand [f]
+// ints, which one memset of `cleared` bytes clears together, then cand [m] ints, written before it is read.  (The byte added
+// to either region keeps the size above zero at f = 0.)
+struct ClWorkspace {
+    int *counts, *cand;
+    size_t cleared, bytes;
+};
 
-static size_t dc_pad(size_t bytes) { return (bytes + 255) / 256 * 256; }
+static ClWorkspace cl_workspace(size_t m, size_t f, void *workspace)
+{
+    Carver ws(workspace);
+    ClWorkspace L;
+    L.cleared = sizeof(int) * (2 * m + f);
+    L.counts = (int *)ws.take<char>(L.cleared + 1);
+    L.cand = (int *)ws.take<char>(sizeof(int) * m + 1);
+    L.bytes = ws.bytes();
+    return L;
+}
 
 } // namespace cloudaae
 
@@ -564,7 +572,7 @@ CLOUDAAE_API int cloudaae_depth_plane(int f, int h, int w, const uint16_t *depth
                                       cloudaae_stream_t stream)
 {
     const char *name = "cloudaae_depth_plane";
-    CLOUDAAE_REQUIRE(dc_within_limits(f, h, w), name, "outside the limits: f >= 0; h, w >= 1; h * w <= 2^24; f * h * w <= 2^28");
+    CLOUDAAE_REQUIRE(frame_within_limits(0, f, h, w), name, CLOUDAAE_FRAME_LIMITS_F0);
     CLOUDAAE_REQUIRE(n_hyp >= 1 && n_hyp <= DC_MAX_HYP && stride >= 1 && first_frame >= 0 && first_frame <= DC_MAX_FIRST_FRAME &&
                          min_plane_percent >= 0 && min_plane_percent <= 100 && tol >= 0.0,
                      name, "outside the limits: 1 <= n_hyp <= 4096; stride >= 1; 0 <= first_frame <= 2^40; "
@@ -599,7 +607,7 @@ CLOUDAAE_API int cloudaae_depth_foreground(int f, int h, int w, const uint16_t *
                                            uint8_t *fg, cloudaae_stream_t stream)
 {
     const char *name = "cloudaae_depth_foreground";
-    CLOUDAAE_REQUIRE(dc_within_limits(f, h, w), name, "outside the limits: f >= 0; h, w >= 1; h * w <= 2^24; f * h * w <= 2^28");
+    CLOUDAAE_REQUIRE(frame_within_limits(0, f, h, w), name, CLOUDAAE_FRAME_LIMITS_F0);
     CLOUDAAE_REQUIRE(tol >= 0.0 && max_height >= 0.0, name, "tol and max_height must be numbers >= 0");
     if (f == 0)
         return 0;
@@ -613,9 +621,9 @@ CLOUDAAE_API int cloudaae_depth_foreground(int f, int h, int w, const uint16_t *
 
 CLOUDAAE_API long long cloudaae_depth_components_workspace_bytes(int f, int h, int w)
 {
-    if (!dc_within_limits(f, h, w))
+    if (!frame_within_limits(0, f, h, w))
         return 0;
-    return (long long)dc_pad(sizeof(int) * (size_t)f * h * w + 1);
+    return (long long)workspace_pad(sizeof(int) * (size_t)f * h * w + 1);
 }
 
 CLOUDAAE_API int cloudaae_depth_components(int f, int h, int w, const uint16_t *depth, const uint8_t *fg, const int *jump_units,
@@ -623,7 +631,7 @@ CLOUDAAE_API int cloudaae_depth_components(int f, int h, int w, const uint16_t *
                                            cloudaae_stream_t stream)
 {
     const char *name = "cloudaae_depth_components";
-    CLOUDAAE_REQUIRE(dc_within_limits(f, h, w), name, "outside the limits: f >= 0; h, w >= 1; h * w <= 2^24; f * h * w <= 2^28");
+    CLOUDAAE_REQUIRE(frame_within_limits(0, f, h, w), name, CLOUDAAE_FRAME_LIMITS_F0);
     if (f == 0)
         return 0;
     CLOUDAAE_REQUIRE(depth && fg && jump_units && root && status && workspace, name, "null pointer");
@@ -652,10 +660,9 @@ CLOUDAAE_API int cloudaae_depth_components(int f, int h, int w, const uint16_t *
 
 CLOUDAAE_API long long cloudaae_component_labels_workspace_bytes(int f, int h, int w)
 {
-    if (!dc_within_limits(f, h, w))
+    if (!frame_within_limits(0, f, h, w))
         return 0;
-    const size_t m = (size_t)f * h * w;
-    return (long long)(dc_pad(sizeof(int) * (2 * m + (size_t)f) + 1) + dc_pad(sizeof(int) * m + 1));
+    return (long long)cl_workspace((size_t)f * h * w, (size_t)f, nullptr).bytes;
 }
 
 CLOUDAAE_API int cloudaae_component_labels(int f, int h, int w, const int *root, int min_pixels, int max_components,
@@ -663,28 +670,26 @@ CLOUDAAE_API int cloudaae_component_labels(int f, int h, int w, const int *root,
                                            int *comp_box, void *workspace, long long workspace_bytes, cloudaae_stream_t stream)
 {
     const char *name = "cloudaae_component_labels";
-    CLOUDAAE_REQUIRE(dc_within_limits(f, h, w), name, "outside the limits: f >= 0; h, w >= 1; h * w <= 2^24; f * h * w <= 2^28");
+    CLOUDAAE_REQUIRE(frame_within_limits(0, f, h, w), name, CLOUDAAE_FRAME_LIMITS_F0);
     CLOUDAAE_REQUIRE(min_pixels >= 1 && max_components >= 1 && max_components <= DC_MAX_COMPONENTS, name,
                      "outside the limits: min_pixels >= 1; 1 <= max_components <= 254");
     if (f == 0)
         return 0;
     CLOUDAAE_REQUIRE(root && label && n_components && n_candidates && comp_root && comp_size && comp_box && workspace, name,
                      "null pointer");
-    CLOUDAAE_REQUIRE(workspace_bytes >= cloudaae_component_labels_workspace_bytes(f, h, w), name,
-                     "workspace smaller than cloudaae_component_labels_workspace_bytes");
     const size_t m = (size_t)f * h * w;
+    const ClWorkspace L = cl_workspace(m, (size_t)f, workspace);
+    CLOUDAAE_REQUIRE(workspace_bytes >= (long long)L.bytes, name,
+                     "workspace smaller than cloudaae_component_labels_workspace_bytes");
     ClArgs a;
     a.f = f, a.h = h, a.w = w, a.min_pixels = min_pixels, a.max_components = max_components;
     a.root = root;
-    a.size = (int *)workspace;                     // size | rank | ncand are cleared together; cand is written before it is read
-    a.rank = a.size + m;
-    a.ncand = a.rank + m;
-    a.cand = (int *)((char *)workspace + dc_pad(sizeof(int) * (2 * m + (size_t)f) + 1));
+    a.size = L.counts, a.rank = a.size + m, a.ncand = a.rank + m, a.cand = L.cand;
     a.label = (unsigned char *)label;
     a.n_components = n_components, a.n_candidates = n_candidates;
     a.comp_root = comp_root, a.comp_size = comp_size, a.comp_box = comp_box;
     hipStream_t sm = (hipStream_t)stream;
-    CLOUDAAE_CHECK_HIP(hipMemsetAsync(workspace, 0, sizeof(int) * (2 * m + (size_t)f), sm), name);
+    CLOUDAAE_CHECK_HIP(hipMemsetAsync(L.counts, 0, L.cleared, sm), name);
     const dim3 pixels(ceil_div((long long)m, DC_BLOCK));
     hipLaunchKernelGGL(component_size_kernel, pixels, dim3(DC_BLOCK), 0, sm, a);
     CLOUDAAE_CHECK_LAUNCH(name);

@@ -23,8 +23,8 @@
 //
 // Here are the nearest map, the pairing of the rendered edges with it, the two contour rows and the total of the two terms.
 // What the sums and the solve share with the plane step of depth_align.hip is in depth_gn.h: the limits and the launch shape
-// (gn_within_limits, gn_runs), the window's camera and the bounds-checked depth load (GnCam, gn_backproject, gn_depth, here
-// with -1 outside the image, which dc_open reads), the 28 sums of a row (gn_add_row), the workgroup's reduction
+// (gn_within_limits, gn_runs), the bounds-checked depth load (gn_depth, here with -1 outside the image, which dc_open reads;
+// the window's camera and its back-projection are depth_frame.h's), the 28 sums of a row (gn_add_row), the workgroup's reduction
 // (gn_store_run), the sum over a sample's runs (gn_add_runs), the LDL^T solve with x -> U (gn_solve) and the write of
 // U pose_in (gn_write_update): weight 0 gives the plane step's own pose because both run that one text.
 #include "common.h"
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(GN_BLOCK) void depth_contour_sums_kernel(ContourSum
     const int n = a.wh * a.ww;                     // window pixels of a sample
     const int q0 = run * GN_RUN + tid * GN_PIX;    // the lane's first window pixel (may lie past n)
     const int gate = a.gate[s], step = a.step[s], R = a.radius;
-    const GnCam cam = gn_cam(a.intr_win + 5 * (size_t)s);
+    const Pinhole<double> cam = pinhole<double>(a.intr_win + 5 * (size_t)s);
     const unsigned short *hyp = a.depth_hyp + (size_t)s * n;
     const unsigned short *test = a.depth_test + (size_t)fr * a.h * a.w;
     const int *near = a.nearest + (size_t)s * n;
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(GN_BLOCK) void depth_contour_sums_kernel(ContourSum
                 const int diff = d - t, mag = diff < 0 ? -diff : diff;
                 if (t >= 0 && mag <= gate) {
                     double p[3];
-                    gn_backproject(cam, x, y, d, p);
+                    backproject(cam, x, y, d, p);
                     rows += 2;
 #pragma unroll 1
                     for (int axis = 0; axis < 2; ++axis) {             // the u row, then the v row
@@ -318,7 +318,7 @@ CLOUDAAE_API int cloudaae_depth_align_solve(int b, const double *plane_sums, con
                                             double *x, int *status, double *pose_out, cloudaae_stream_t stream)
 {
     const char *name = "cloudaae_depth_align_solve";
-    CLOUDAAE_REQUIRE(b >= 1 && b <= GN_MAX_TOTAL, name, "outside the limits: 1 <= b <= 2^28");
+    CLOUDAAE_REQUIRE(b >= 1 && b <= FRAME_MAX_TOTAL, name, "outside the limits: 1 <= b <= 2^28");
     CLOUDAAE_REQUIRE(!isnan(weight), name, "weight must be a number");
     CLOUDAAE_REQUIRE(plane_sums && n_pairs && plane_status && contour_sums && n_rows && pose_in && x && status && pose_out, name,
                      "null pointer");

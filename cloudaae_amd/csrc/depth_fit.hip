@@ -21,6 +21,7 @@
 //                               one row" whatever w is, and only the lanes of a run's tail and the arrays whose base is
 //                               not aligned go pixel by pixel.
 #include "common.h"
+#include "depth_frame.h"
 #include "depth_fit.h"
 #include "../../include/cloudaae_hip.h"
 
@@ -29,8 +30,6 @@ namespace cloudaae {
 typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
 typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
 
-constexpr long long DF_MAX_PIXELS = 1ll << 24;     // h w, wh ww
-constexpr long long DF_MAX_TOTAL = 1ll << 28;      // b p wh ww, b p
 
 constexpr int DF_BLOCK = 256;
 constexpr int DF_WAVES = DF_BLOCK / 64;
@@ -209,9 +208,9 @@ static int depth_fit_counts(const char *name, bool window, int f, int h, int w, 
 {
     CLOUDAAE_REQUIRE(f >= 1 && h >= 1 && w >= 1 && b >= 1 && p >= 1 && wh >= 1 && ww >= 1, name,
                      window ? "f, h, w, b, p, wh and ww must be >= 1" : "f, h, w, b and p must be >= 1");
-    CLOUDAAE_REQUIRE((long long)h * w <= DF_MAX_PIXELS, name, "h * w above 2^24");
-    CLOUDAAE_REQUIRE((long long)wh * ww <= DF_MAX_PIXELS, name, "wh * ww above 2^24");
-    CLOUDAAE_REQUIRE((long long)b * p <= DF_MAX_TOTAL && (long long)b * p * ((long long)wh * ww) <= DF_MAX_TOTAL, name,
+    CLOUDAAE_REQUIRE((long long)h * w <= FRAME_MAX_PIXELS, name, "h * w above 2^24");
+    CLOUDAAE_REQUIRE((long long)wh * ww <= FRAME_MAX_PIXELS, name, "wh * ww above 2^24");
+    CLOUDAAE_REQUIRE((long long)b * p <= FRAME_MAX_TOTAL && (long long)b * p * ((long long)wh * ww) <= FRAME_MAX_TOTAL, name,
                      window ? "b * p * wh * ww above 2^28" : "b * p * h * w above 2^28");
     CLOUDAAE_REQUIRE(depth_test && frame_of && (origin || !window) && depth_hyp && tau && counts && seg_total && abs_sum, name,
                      "null pointer");

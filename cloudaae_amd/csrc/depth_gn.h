@@ -1,20 +1,19 @@
 // depth_gn.h -- what the two terms of depth-image tracking share: the point-to-plane step (depth_align.hip) and the
 // occluding-contour term with the combined solve (depth_contour.hip) both add rows (J[6], r) of one Gauss-Newton system into
 // 28 sums per run of 2048 window pixels, add a sample's runs in run order, and solve the 6 x 6 system for the pose update.
-// Here are the limits and the launch shape, the workspace's layout, the window's camera, the row accumulation, the
+// Here are the limits and the launch shape, the workspace's layout, the row accumulation, the
 // workgroup's reduction, the sum over a sample's runs, the LDL^T solve and the write of the updated pose.  DESIGN.md,
 // "Tracking" and "Contours", are the definitions.  Both includers are compiled un-fused (-ffp-contract=off) and without
 // packed fp32, so this text gives the same bits in both.  One restatement of the factorisation remains: icp_plane_update of
 // icp.hip, on another layout of the sums.
 #pragma once
 #include "common.h"
+#include "depth_frame.h"
+#include "workspace.h"
 
 #include <math.h>
 
 namespace cloudaae {
-
-constexpr long long GN_MAX_PIXELS = 1ll << 24;     // h w, wh ww
-constexpr long long GN_MAX_TOTAL = 1ll << 28;      // b wh ww
 
 constexpr int GN_BLOCK = 256;
 constexpr int GN_WAVES = GN_BLOCK / 64;
@@ -26,8 +25,8 @@ constexpr int GN_SUMS = 28;                        // sum r^2, A's upper triangl
 
 static inline bool gn_within_limits(long long f, long long h, long long w, long long b, long long wh, long long ww)
 {
-    return f >= 1 && h >= 1 && w >= 1 && b >= 1 && wh >= 1 && ww >= 1 && h * w <= GN_MAX_PIXELS && wh * ww <= GN_MAX_PIXELS &&
-           b * (wh * ww) <= GN_MAX_TOTAL;
+    // (f frames are indexed, only b windows are read: the frames' total has no limit, one frame's pixels have)
+    return f >= 1 && frame_within_limits(1, 1, h, w) && frame_within_limits(1, b, wh, ww);
 }
 
 // The runs of b windows of wh x ww pixels and where their partial results lie in a workspace: part_sums [b, runs, 28]
@@ -45,33 +44,14 @@ static inline GnRuns gn_runs(int b, int wh, int ww, void *workspace)
     GnRuns g;
     g.runs = ceil_div((long long)wh * ww, GN_RUN);
     g.all = (long long)b * g.runs;
-    const long long sums_bytes = g.all * (long long)(GN_SUMS * sizeof(double));
-    g.bytes = sums_bytes + (g.all * (long long)sizeof(int) + 7) / 8 * 8;
-    g.part_sums = (double *)workspace;
-    g.part_count = (int *)((uintptr_t)workspace + (uintptr_t)sums_bytes);
+    Carver ws(workspace);
+    g.part_sums = ws.take<double>((size_t)g.all * GN_SUMS, 8);
+    g.part_count = ws.take<int>((size_t)g.all, 8);
+    g.bytes = (long long)ws.bytes();
     return g;
 }
 
-// The window's camera: the row (fx, fy, cx - u0, cy - v0, factor_depth), widened
-struct GnCam {
-    double fx, fy, cx, cy, factor;
-};
-
-__device__ __forceinline__ GnCam gn_cam(const float *k)
-{
-    GnCam c;
-    c.fx = (double)k[0], c.fy = (double)k[1], c.cx = (double)k[2], c.cy = (double)k[3], c.factor = (double)k[4];
-    return c;
-}
-
-// P(x, y, z) = (((x - cxw) dm) / fx, ((y - cyw) dm) / fy, dm) with dm = z / factor_depth
-__device__ __forceinline__ void gn_backproject(const GnCam &c, int x, int y, int z, double (&p)[3])
-{
-    const double dm = (double)z / c.factor;
-    p[0] = (((double)x - c.cx) * dm) / c.fx;
-    p[1] = (((double)y - c.cy) * dm) / c.fy;
-    p[2] = dm;
-}
+// (the window's camera is depth_frame.h's Pinhole<double> of the row (fx, fy, cx - u0, cy - v0, factor_depth))
 
 // the depth of image [h, w] at pixel (u, v); `outside` where that is no pixel of the image (nothing is read there)
 __device__ __forceinline__ int gn_depth(const unsigned short *pix, int h, int w, long long u, long long v, int outside)

@@ -12,6 +12,7 @@
 // their cache lines.  A counter is a ballot + popcount per wave, the four waves meet in LDS, and one integer atomic per
 // workgroup and counter (none for a zero) adds into the zeroed output, as in bop_score.hip.
 #include "common.h"
+#include "depth_frame.h"
 #include "philox.h"
 #include "../../include/cloudaae_hip.h"
 
@@ -25,8 +26,6 @@ constexpr int DN_BLOCK = 256;
 constexpr int DN_WAVES = DN_BLOCK / 64;
 constexpr unsigned DN_STREAM_NORMALS = 21u;        // normal2(r0, r1) -> n_u, n_v; normal2(r2, r3) -> n_z, (unused)
 constexpr unsigned DN_STREAM_DROP = 22u;           // r0: the dropout word
-constexpr long long DN_MAX_PIXELS = 1ll << 24;     // H W
-constexpr long long DN_MAX_TOTAL = 1ll << 28;      // F H W
 constexpr u64 DN_MAX_FRAME = 1ull << 40;           // global frame indices lie below
 constexpr double DN_HALF_PI = 1.5707963267948966;  // the double nearest pi / 2
 
@@ -34,7 +33,7 @@ struct DnFrame {
     const unsigned short *depth;                   // this frame's [h, w]
     const unsigned char *label;
     int h, w;
-    double fx, fy, cx, cy, factor;
+    Pinhole<double> cam;
 };
 
 // adds the workgroup's totals of N per-lane predicates into dst[0 .. N): every lane of the workgroup must call it
@@ -60,15 +59,6 @@ __device__ __forceinline__ void dn_add_counts(const bool (&pred)[N], int *dst)
     }
 }
 
-// P = (((u - cx) dm) / fx, ((v - cy) dm) / fy, dm) with dm = d / factor
-__device__ __forceinline__ void dn_backproject(const DnFrame &fr, int u, int v, unsigned short d, double (&p)[3])
-{
-    const double dm = (double)d / fr.factor;
-    p[0] = (((double)u - fr.cx) * dm) / fr.fx;
-    p[1] = (((double)v - fr.cy) * dm) / fr.fy;
-    p[2] = dm;
-}
-
 // the neighbour (u, v) of a pixel with label l: valid when inside the image, with depth and with that label
 __device__ __forceinline__ bool dn_tap(const DnFrame &fr, int u, int v, unsigned char l, double (&p)[3])
 {
@@ -78,7 +68,7 @@ __device__ __forceinline__ bool dn_tap(const DnFrame &fr, int u, int v, unsigned
     const unsigned short d = fr.depth[i];
     if (d == 0 || fr.label[i] != l)
         return false;
-    dn_backproject(fr, u, v, d, p);
+    backproject(fr.cam, u, v, d, p);
     return true;
 }
 
@@ -109,7 +99,7 @@ __device__ __forceinline__ bool dn_slope(const DnFrame &fr, int u, int v, unsign
     theta = 0.0;
     const unsigned char l = fr.label[(size_t)v * fr.w + u];
     double ray[3], gx[3], gy[3];
-    dn_backproject(fr, u, v, d, ray);
+    backproject(fr.cam, u, v, d, ray);
     const bool hx = dn_axis(fr, u, v, 1, 0, l, ray, gx), hy = dn_axis(fr, u, v, 0, 1, l, ray, gy);
     if (!hx || !hy)
         return false;
@@ -140,8 +130,7 @@ __device__ __forceinline__ DnFrame dn_frame(int f, int h, int w, const unsigned 
     fr.depth = depth + (size_t)f * hw;
     fr.label = label + (size_t)f * hw;
     fr.h = h, fr.w = w;
-    const float *k = intrinsics + 5 * (size_t)f;
-    fr.fx = (double)k[0], fr.fy = (double)k[1], fr.cx = (double)k[2], fr.cy = (double)k[3], fr.factor = (double)k[4];
+    fr.cam = pinhole<double>(intrinsics + 5 * (size_t)f);
     return fr;
 }
 
@@ -214,7 +203,7 @@ __global__ __launch_bounds__(DN_BLOCK) void depth_sensor_noise_kernel(int h, int
             // 2. axial noise
             double n[3], theta_raw;
             dn_slope(fr, su, sv, d, n, theta_raw);
-            const double z = (double)d / fr.factor;
+            const double z = (double)d / fr.cam.factor;
             const double theta = theta_raw < s.theta_max ? theta_raw : s.theta_max;
             const double dz = z - s.z0, rest = DN_HALF_PI - theta;
             const double sigma_z = (s.a0 + s.a1 * (dz * dz)) + ((s.a2 / sqrt(z)) * (theta * theta)) / (rest * rest);
@@ -229,13 +218,13 @@ __global__ __launch_bounds__(DN_BLOCK) void depth_sensor_noise_kernel(int h, int
                 double zq = zn;
                 bool lost = false;
                 if (s.disparity_step > 0.0) {
-                    const double fb = fr.fx * s.baseline;
+                    const double fb = fr.cam.fx * s.baseline;
                     const double k = rint((fb / zn) / s.disparity_step);
                     lost = !(k >= 1.0);
                     zq = fb / (k * s.disparity_step);
                 }
                 // 5. quantisation (a NaN fails the comparisons)
-                const double du = floor(zq * fr.factor + 0.5);
+                const double du = floor(zq * fr.cam.factor + 0.5);
                 if (!lost && du >= 1.0 && du <= 65535.0)
                     out = (unsigned short)(int)du;
                 else
@@ -253,11 +242,6 @@ __global__ __launch_bounds__(DN_BLOCK) void depth_sensor_noise_kernel(int h, int
     dn_add_counts<4>(what, counts + 4 * (size_t)f);
 }
 
-static bool dn_within_limits(long long f, long long h, long long w)
-{
-    return f >= 1 && h >= 1 && w >= 1 && h * w <= DN_MAX_PIXELS && f * h * w <= DN_MAX_TOTAL;
-}
-
 } // namespace cloudaae
 
 using namespace cloudaae;
@@ -266,7 +250,7 @@ CLOUDAAE_API int cloudaae_depth_normals(int f, int h, int w, const uint16_t *dep
                                         float *normals, float *theta, int *flat_counts, cloudaae_stream_t stream)
 {
     const char *name = "cloudaae_depth_normals";
-    CLOUDAAE_REQUIRE(dn_within_limits(f, h, w), name, "outside the limits: f, h, w >= 1; h * w <= 2^24; f * h * w <= 2^28");
+    CLOUDAAE_REQUIRE(frame_within_limits(1, f, h, w), name, CLOUDAAE_FRAME_LIMITS);
     CLOUDAAE_REQUIRE(depth && label && intrinsics && normals && flat_counts, name, "null pointer");
     hipStream_t sm = (hipStream_t)stream;
     const int tiles = ceil_div((long long)h * w, DN_BLOCK);
@@ -286,7 +270,7 @@ CLOUDAAE_API int cloudaae_depth_sensor_noise(int f, int h, int w, const uint16_t
                                              cloudaae_stream_t stream)
 {
     const char *name = "cloudaae_depth_sensor_noise";
-    CLOUDAAE_REQUIRE(dn_within_limits(f, h, w), name, "outside the limits: f, h, w >= 1; h * w <= 2^24; f * h * w <= 2^28");
+    CLOUDAAE_REQUIRE(frame_within_limits(1, f, h, w), name, CLOUDAAE_FRAME_LIMITS);
     CLOUDAAE_REQUIRE(first_frame < DN_MAX_FRAME && first_frame + (u64)f <= DN_MAX_FRAME, name,
                      "global frame indices (first_frame + f) must lie below 2^40");
     CLOUDAAE_REQUIRE(sigma_l >= 0.0 && isfinite(sigma_l), name, "sigma_l must be >= 0 and finite");

@@ -11,7 +11,9 @@
 //                           for itself whether its pixel is a row, back-projects and writes); the rows that are re-draws
 //                           or the fallback, one lane per (cloud, row)
 #include "common.h"
+#include "depth_frame.h"
 #include "philox.h"
+#include "workspace.h"
 #include "../../include/cloudaae_hip.h"
 
 namespace cloudaae {
@@ -24,8 +26,6 @@ constexpr int FC_PASSES = 4;                       // pixels per lane
 constexpr int FC_TILE = FC_BLOCK * FC_PASSES;      // pixels per workgroup, in pixel order: pass, wave, lane
 constexpr unsigned FC_STREAM_STRATUM = 23u;        // r0 of counter g 2^24 + j: the pixel of stratum j (n >= rows)
 constexpr unsigned FC_STREAM_REDRAW = 24u;         // r0 of counter g 2^24 + j: the source of row j >= n (n < rows)
-constexpr long long FC_MAX_PIXELS = 1ll << 24;     // H W
-constexpr long long FC_MAX_TOTAL = 1ll << 28;      // F H W
 constexpr long long FC_MAX_ROWS = 1ll << 20;
 constexpr long long FC_MAX_INDEX = 1ll << 39;      // global cloud indices lie below
 constexpr long long FC_MAX_GRID = (1ll << 31) - 1; // c * tiles and c * rows
@@ -129,16 +129,12 @@ __global__ __launch_bounds__(FC_BLOCK) void frame_clouds_scan_kernel(FcArgs a)
 // row j of cloud c: the back-projection of pixel p with depth d
 __device__ __forceinline__ void fc_write_row(const FcArgs &a, int c, int fr, int j, int p, unsigned short d)
 {
-    const float *k = a.intrinsics + 5 * (size_t)fr;
-    const float fx = k[0], fy = k[1], cx = k[2], cy = k[3], factor = k[4];
-    const int u = p % a.w, v = p / a.w;
-    const float dm = (float)d / factor;
-    const float x = (((float)u - cx) * dm) / fx;
-    const float y = (((float)v - cy) * dm) / fy;
+    float q[3];
+    backproject(pinhole<float>(a.intrinsics + 5 * (size_t)fr), p % a.w, p / a.w, d, q);
     const size_t o = (size_t)c * a.rows + j;
-    a.cloud[3 * o + 0] = x;
-    a.cloud[3 * o + 1] = y;
-    a.cloud[3 * o + 2] = dm;
+    a.cloud[3 * o + 0] = q[0];
+    a.cloud[3 * o + 1] = q[1];
+    a.cloud[3 * o + 2] = q[2];
     a.row_src[o] = j;
 }
 
@@ -231,9 +227,8 @@ static int fc_tiles(long long h, long long w) { return (int)((h * w + FC_TILE - 
 
 static bool fc_within_limits(long long f, long long h, long long w, long long c, long long rows)
 {
-    if (!(f >= 1 && h >= 1 && w >= 1 && h * w <= FC_MAX_PIXELS && f * h * w <= FC_MAX_TOTAL))
-        return false;
-    return c >= 1 && rows >= 1 && rows <= FC_MAX_ROWS && c * fc_tiles(h, w) <= FC_MAX_GRID && c * rows <= FC_MAX_GRID;
+    return frame_within_limits(1, f, h, w) && c >= 1 && rows >= 1 && rows <= FC_MAX_ROWS && c * fc_tiles(h, w) <= FC_MAX_GRID &&
+           c * rows <= FC_MAX_GRID;
 }
 
 } // namespace cloudaae
@@ -244,7 +239,7 @@ CLOUDAAE_API long long cloudaae_frame_clouds_workspace_bytes(int f, int h, int w
 {
     if (!fc_within_limits(f, h, w, c, rows))
         return 0;
-    return (long long)(((size_t)c * fc_tiles(h, w) * sizeof(int) + 255) / 256 * 256);
+    return (long long)workspace_pad((size_t)c * fc_tiles(h, w) * sizeof(int));
 }
 
 CLOUDAAE_API int cloudaae_frame_clouds(int f, int h, int w, const uint16_t *depth, const uint8_t *label, const float *intrinsics,

@@ -15,6 +15,7 @@
 //   cloudaae_mesh_gather_rows  one launch, one lane per output element
 #include "common.h"
 #include "philox.h"
+#include "workspace.h"
 #include "../../include/cloudaae_hip.h"
 #include <math.h>
 
@@ -309,7 +310,25 @@ __global__ __launch_bounds__(256) void mesh_gather_rows_kernel(long long total, 
     dst[row * dst_row_stride + c] = v;
 }
 
-static size_t ms_align(size_t b) { return (b + 255) / 256 * 256; }
+// the workspace of cloudaae_mesh_weights (null: the size alone is asked for)
+struct MsWorkspace {
+    double *a2;                                    // [num_triangles]
+    u64 *local, *block_sum, *block_prefix;         // [num_triangles], [blocks], [blocks]
+    size_t bytes;
+};
+
+static MsWorkspace ms_workspace(long long num_triangles, void *workspace)
+{
+    const size_t blocks = (size_t)ceil_div(num_triangles, MS_SCAN_BLOCK);
+    Carver ws(workspace);
+    MsWorkspace L;
+    L.a2 = ws.take<double>((size_t)num_triangles);
+    L.local = ws.take<u64>((size_t)num_triangles);
+    L.block_sum = ws.take<u64>(blocks);
+    L.block_prefix = ws.take<u64>(blocks);
+    L.bytes = ws.bytes();
+    return L;
+}
 
 } // namespace cloudaae
 
@@ -319,8 +338,7 @@ CLOUDAAE_API long long cloudaae_mesh_weights_workspace_bytes(long long num_trian
 {
     if (num_triangles < 1 || num_triangles > MS_MAX_TOTAL)
         return -1;
-    const size_t blocks = (size_t)ceil_div(num_triangles, MS_SCAN_BLOCK);
-    return (long long)(2 * ms_align(8 * (size_t)num_triangles) + 2 * ms_align(8 * blocks));
+    return (long long)ms_workspace(num_triangles, nullptr).bytes;
 }
 
 CLOUDAAE_API int cloudaae_mesh_weights(int s, const int *vert_offsets, const int *tri_offsets, long long num_vertices,
@@ -334,26 +352,21 @@ CLOUDAAE_API int cloudaae_mesh_weights(int s, const int *vert_offsets, const int
     CLOUDAAE_REQUIRE(num_triangles >= 1 && num_triangles <= MS_MAX_TOTAL, name, "num_triangles must lie in [1, 2^28]");
     CLOUDAAE_REQUIRE(vert_offsets && tri_offsets && vertices && triangles && weights && cum && a2max && invalid && workspace,
                      name, "null pointer");
-    CLOUDAAE_REQUIRE(workspace_bytes >= cloudaae_mesh_weights_workspace_bytes(num_triangles), name,
-                     "workspace smaller than cloudaae_mesh_weights_workspace_bytes");
+    const MsWorkspace L = ms_workspace(num_triangles, workspace);
+    CLOUDAAE_REQUIRE(workspace_bytes >= (long long)L.bytes, name, "workspace smaller than cloudaae_mesh_weights_workspace_bytes");
     const int nt = (int)num_triangles, blocks = ceil_div(num_triangles, MS_SCAN_BLOCK);
-    char *ws = (char *)workspace;
-    double *a2 = (double *)ws;
-    u64 *local = (u64 *)(ws + ms_align(8 * (size_t)nt));
-    u64 *block_sum = (u64 *)(ws + 2 * ms_align(8 * (size_t)nt));
-    u64 *block_prefix = (u64 *)(ws + 2 * ms_align(8 * (size_t)nt) + ms_align(8 * (size_t)blocks));
     hipStream_t st = (hipStream_t)stream;
     CLOUDAAE_CHECK_HIP(hipMemsetAsync(a2max, 0, sizeof(double) * (size_t)s, st), name);
     CLOUDAAE_CHECK_HIP(hipMemsetAsync(invalid, 0, sizeof(int) * (size_t)s, st), name);
     hipLaunchKernelGGL(mesh_area_kernel, dim3(blocks), dim3(MS_SCAN_BLOCK), 0, st, s, vert_offsets, tri_offsets,
-                       (int)num_vertices, nt, vertices, triangles, a2, (u64 *)a2max, invalid);
+                       (int)num_vertices, nt, vertices, triangles, L.a2, (u64 *)a2max, invalid);
     CLOUDAAE_CHECK_LAUNCH(name);
-    hipLaunchKernelGGL(mesh_weight_kernel, dim3(blocks), dim3(MS_SCAN_BLOCK), 0, st, s, tri_offsets, nt, a2, (const u64 *)a2max,
-                       (u64 *)weights, local, block_sum);
+    hipLaunchKernelGGL(mesh_weight_kernel, dim3(blocks), dim3(MS_SCAN_BLOCK), 0, st, s, tri_offsets, nt, L.a2, (const u64 *)a2max,
+                       (u64 *)weights, L.local, L.block_sum);
     CLOUDAAE_CHECK_LAUNCH(name);
-    hipLaunchKernelGGL(mesh_block_prefix_kernel, dim3(1), dim3(MS_SCAN_BLOCK), 0, st, blocks, block_sum, block_prefix);
+    hipLaunchKernelGGL(mesh_block_prefix_kernel, dim3(1), dim3(MS_SCAN_BLOCK), 0, st, blocks, L.block_sum, L.block_prefix);
     CLOUDAAE_CHECK_LAUNCH(name);
-    hipLaunchKernelGGL(mesh_cum_kernel, dim3(blocks), dim3(MS_SCAN_BLOCK), 0, st, s, tri_offsets, nt, local, block_prefix,
+    hipLaunchKernelGGL(mesh_cum_kernel, dim3(blocks), dim3(MS_SCAN_BLOCK), 0, st, s, tri_offsets, nt, L.local, L.block_prefix,
                        (u64 *)cum);
     CLOUDAAE_CHECK_LAUNCH(name);
     return 0;

@@ -13,6 +13,7 @@
 //                     and mean, then covariance), cyclic Jacobi on the 3x3 matrix, orientation.  fp64 on the widened
 //                     coordinates, every sum in the array's order, no atomics on floating-point values.
 #include "common.h"
+#include "workspace.h"
 #include "../../include/cloudaae_hip.h"
 
 #include <math.h>
@@ -32,25 +33,23 @@ struct NrmGrid {                                           // per set, in the wo
     double ox, oy, oz, inv_h;
 };
 
-struct NrmLayout {
-    size_t grids, cell_start, tmp, sorted, total;
+// the workspace of s sets of m points in all (null: the size alone is asked for)
+struct NrmWorkspace {
+    NrmGrid *grids;                                        // [s]
+    int *cell_start;                                       // [s, NRM_CELLS + 1]
+    float4 *tmp, *sorted;                                  // [m] each
+    size_t bytes;
 };
 
-size_t nrm_align(size_t x) { return (x + 255) / 256 * 256; }
-
-NrmLayout nrm_layout(int s, long long m)
+NrmWorkspace nrm_workspace(int s, long long m, void *workspace)
 {
-    NrmLayout L;
-    size_t o = 0;
-    L.grids = o;
-    o += nrm_align(sizeof(NrmGrid) * (size_t)s);
-    L.cell_start = o;
-    o += nrm_align(sizeof(int) * (size_t)s * (NRM_CELLS + 1));
-    L.tmp = o;
-    o += nrm_align(sizeof(float4) * (size_t)m);
-    L.sorted = o;
-    o += nrm_align(sizeof(float4) * (size_t)m);
-    L.total = o;
+    Carver ws(workspace);
+    NrmWorkspace L;
+    L.grids = ws.take<NrmGrid>((size_t)s);
+    L.cell_start = ws.take<int>((size_t)s * (NRM_CELLS + 1));
+    L.tmp = ws.take<float4>((size_t)m);
+    L.sorted = ws.take<float4>((size_t)m);
+    L.bytes = ws.bytes();
     return L;
 }
 
@@ -321,7 +320,7 @@ CLOUDAAE_API long long cloudaae_estimate_normals_workspace_bytes(int s, long lon
 {
     if (s < 1 || max_points < 1 || max_points > NRM_MAX_POINTS)
         return -1;
-    return (long long)nrm_layout(s, max_points).total;
+    return (long long)nrm_workspace(s, max_points, nullptr).bytes;
 }
 
 CLOUDAAE_API int cloudaae_estimate_normals(int s, const int *offsets, const float *xyz, int xyz_point_stride,
@@ -343,18 +342,14 @@ CLOUDAAE_API int cloudaae_estimate_normals(int s, const int *offsets, const floa
     CLOUDAAE_REQUIRE(offsets && xyz && queries && normals && eigenvalues && count && workspace, name, "null pointer");
     CLOUDAAE_REQUIRE(!viewpoint || (isfinite(viewpoint[0]) && isfinite(viewpoint[1]) && isfinite(viewpoint[2])), name,
                      "viewpoint must be finite");
-    const NrmLayout L = nrm_layout(s, max_points);
-    CLOUDAAE_REQUIRE(workspace_bytes >= (long long)L.total, name,
+    const NrmWorkspace L = nrm_workspace(s, max_points, workspace);
+    CLOUDAAE_REQUIRE(workspace_bytes >= (long long)L.bytes, name,
                      "workspace smaller than cloudaae_estimate_normals_workspace_bytes");
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    NrmGrid *grids = (NrmGrid *)(ws + L.grids);
-    int *cell_start = (int *)(ws + L.cell_start);
-    float4 *tmp = (float4 *)(ws + L.tmp), *sorted = (float4 *)(ws + L.sorted);
     hipLaunchKernelGGL(nrm_grid_kernel, dim3(s), dim3(NRM_THREADS), 0, st, offsets, max_points, xyz, xyz_point_stride,
-                       radius, grids, cell_start, tmp, sorted);
+                       radius, L.grids, L.cell_start, L.tmp, L.sorted);
     hipLaunchKernelGGL(nrm_query_kernel, dim3(ceil_div(k, NRM_QBLOCK), s), dim3(NRM_QBLOCK), 0, st, offsets, max_points,
-                       grids, cell_start, sorted, k, queries, query_point_stride, query_set_stride, radius,
+                       L.grids, L.cell_start, L.sorted, k, queries, query_point_stride, query_set_stride, radius,
                        min_neighbors, viewpoint ? 1 : 0, viewpoint ? viewpoint[0] : 0.0, viewpoint ? viewpoint[1] : 0.0,
                        viewpoint ? viewpoint[2] : 0.0, normals, eigenvalues, count);
     CLOUDAAE_CHECK_LAUNCH(name);

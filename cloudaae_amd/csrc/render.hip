@@ -11,7 +11,9 @@
 //                            with the small triangles rasterised by their lane and the large ones queued; the queue,
 //                            one wave per triangle; the resolve, one lane per pixel
 #include "common.h"
+#include "depth_frame.h"
 #include "pose_math.h"
+#include "workspace.h"
 #include "../../include/cloudaae_hip.h"
 #include <math.h>
 
@@ -28,8 +30,7 @@ constexpr int RN_QUEUE_BLOCKS = 1024;      // the fixed grid that strides over t
 constexpr int RN_FRAC = 8;                 // fractional bits of a screen coordinate
 constexpr double RN_GUARD = 16777216.0;    // |ix|, |iy| <= 2^24: differences below 2^26, edge values below 2^52
 constexpr int RN_UNUSABLE = INT32_MIN;     // ix of a vertex that no triangle may use
-constexpr long long RN_MAX_PIXELS = 1ll << 24;     // H W
-constexpr long long RN_MAX_TOTAL = 1ll << 28;      // F H W; vertices and triangles of the packed meshes
+constexpr long long RN_MAX_TOTAL = 1ll << 28;      // vertices and triangles of the packed meshes
 constexpr long long RN_MAX_RANK = (1ll << 31) - 1; // instance triangles (and instance vertices) of a call
 constexpr int RN_MAX_MESH_TRIANGLES = 1 << 24;
 constexpr int RN_MAX_MESHES = 65535;
@@ -291,13 +292,24 @@ __global__ __launch_bounds__(RN_BLOCK) void render_resolve_kernel(long long pixe
         tri[p] = r;
 }
 
-static size_t rn_align(size_t b) { return (b + 255) / 256 * 256; }
-
 static bool rn_within_limits(long long f, long long h, long long w, long long j, long long sum_v, long long sum_t)
 {
-    return f >= 1 && h >= 1 && w >= 1 && h * w <= RN_MAX_PIXELS && f * h * w <= RN_MAX_TOTAL && j >= 1 && j <= RN_MAX_RANK &&
-           sum_v >= 0 && sum_v <= RN_MAX_RANK && sum_t >= 0 && sum_t <= RN_MAX_RANK &&
+    return frame_within_limits(1, f, h, w) && j >= 1 && j <= RN_MAX_RANK && sum_v >= 0 && sum_v <= RN_MAX_RANK && sum_t >= 0 &&
+           sum_t <= RN_MAX_RANK &&
            sum_t <= j * RN_MAX_MESH_TRIANGLES;     // (what the sums can show of "at most 2^24 triangles per mesh")
+}
+
+// the workspace pointers of a (null workspace: the size alone is asked for); returns the workspace's bytes
+static size_t rn_carve(RenderArgs &a, size_t pixels, size_t sum_v, size_t sum_t, void *workspace)
+{
+    Carver ws(workspace);
+    a.zbuf = ws.take<u64>(pixels);
+    a.viz = ws.take<double>(sum_v);
+    a.vx = ws.take<int>(sum_v);
+    a.vy = ws.take<int>(sum_v);
+    a.queue = ws.take<int>(sum_t);
+    a.queue_len = ws.take<int>(1);
+    return ws.bytes();
 }
 
 } // namespace cloudaae
@@ -309,8 +321,8 @@ CLOUDAAE_API long long cloudaae_render_workspace_bytes(int f, int h, int w, int 
 {
     if (!rn_within_limits(f, h, w, j, sum_inst_vertices, sum_inst_triangles))
         return 0;
-    const size_t sv = (size_t)sum_inst_vertices, st = (size_t)sum_inst_triangles;
-    return (long long)(rn_align(8 * (size_t)f * h * w) + rn_align(8 * sv) + 2 * rn_align(4 * sv) + rn_align(4 * st) + 256);
+    RenderArgs a;
+    return (long long)rn_carve(a, (size_t)f * h * w, (size_t)sum_inst_vertices, (size_t)sum_inst_triangles, nullptr);
 }
 
 CLOUDAAE_API int cloudaae_render_frames(int s, const int *vert_offsets, const int *tri_offsets, long long num_vertices,
@@ -333,28 +345,16 @@ CLOUDAAE_API int cloudaae_render_frames(int s, const int *vert_offsets, const in
                          inst_label && inst_pose && inst_vert_base && inst_tri_base && depth && label && dropped &&
                          degenerate && workspace,
                      name, "null pointer");
-    CLOUDAAE_REQUIRE(workspace_bytes >= cloudaae_render_workspace_bytes(f, h, w, j, sum_inst_vertices, sum_inst_triangles), name,
-                     "workspace smaller than cloudaae_render_workspace_bytes");
     const size_t pixels = (size_t)f * h * w, sv = (size_t)sum_inst_vertices, st = (size_t)sum_inst_triangles;
     RenderArgs a;
+    CLOUDAAE_REQUIRE(workspace_bytes >= (long long)rn_carve(a, pixels, sv, st, workspace), name,
+                     "workspace smaller than cloudaae_render_workspace_bytes");
     a.s = s, a.nv = (int)num_vertices, a.nt = (int)num_triangles;
     a.vert_offsets = vert_offsets, a.tri_offsets = tri_offsets, a.vertices = vertices, a.triangles = triangles;
     a.f = f, a.h = h, a.w = w, a.intrinsics = intrinsics, a.inst_offsets = inst_offsets;
     a.j = j, a.inst_mesh = inst_mesh, a.inst_label = inst_label, a.inst_pose = inst_pose;
     a.vert_base = inst_vert_base, a.tri_base = inst_tri_base, a.sum_v = (int)sv, a.sum_t = (int)st;
     a.z_near = z_near;
-    char *ws = (char *)workspace;
-    a.zbuf = (u64 *)ws;
-    ws += rn_align(8 * pixels);
-    a.viz = (double *)ws;
-    ws += rn_align(8 * sv);
-    a.vx = (int *)ws;
-    ws += rn_align(4 * sv);
-    a.vy = (int *)ws;
-    ws += rn_align(4 * sv);
-    a.queue = (int *)ws;
-    ws += rn_align(4 * st);
-    a.queue_len = (int *)ws;
     a.dropped = dropped, a.degenerate = degenerate;
     hipStream_t sm = (hipStream_t)stream;
     CLOUDAAE_CHECK_HIP(hipMemsetAsync(a.zbuf, 0xFF, 8 * pixels, sm), name);

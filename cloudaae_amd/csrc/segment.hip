@@ -23,6 +23,8 @@
 // Point counts are bounded by F*H*W (a pixel belongs to one segment at most), so every buffer is sized without
 // reading a count back; grids are sized by that bound and blocks past the device-side total do nothing.
 #include "common.h"
+#include "depth_frame.h"
+#include "workspace.h"
 #include "../../include/cloudaae_hip.h"
 
 #include <math.h>
@@ -41,8 +43,6 @@ constexpr int FPS_THREADS = 512;
 constexpr int FPS_WAVES = FPS_THREADS / 64;
 constexpr int FPS_PER_LANE = 24;           // points held in registers: 12288 per set; the rest in the workspace
 constexpr int FPS_REG_POINTS = FPS_THREADS * FPS_PER_LANE;
-
-inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ---- one workgroup: exclusive scan of n ints in[i * stride] -> out[i], out[n] = total ------------------------------
 __device__ void block_exclusive_scan(const int *in, long long stride, int n, int *out, int *lds /*[blockDim]*/)
@@ -166,17 +166,12 @@ __global__ __launch_bounds__(SEG_BLOCK) void fs_scatter_kernel(
     int rank = 0;
     for (int j = 0; j < t; ++j)
         rank += segs[j] == s;
-    // back-projection (:164-178), fp32, no fma (-ffp-contract=off), correctly rounded division
-    const float fx = intr[5 * fr], fy = intr[5 * fr + 1], cx = intr[5 * fr + 2], cy = intr[5 * fr + 3];
-    const float factor = intr[5 * fr + 4];
-    const int u = px % w, v = px / w;
-    const float dm = (float)depth[p] / factor;
-    const float x = (((float)u - cx) * dm) / fx;
-    const float y = (((float)v - cy) * dm) / fy;
+    float xyz[3];                                  // back-projection (:164-178) in fp32
+    backproject(pinhole<float>(intr + 5 * fr), px % w, px / w, depth[p], xyz);
     const long long q = (long long)mask_off[s] + seg_blk_off[(long long)s * (nblk + 1) + b] + rank;
-    mxyz[3 * q] = x;
-    mxyz[3 * q + 1] = y;
-    mxyz[3 * q + 2] = dm;
+    mxyz[3 * q] = xyz[0];
+    mxyz[3 * q + 1] = xyz[1];
+    mxyz[3 * q + 2] = xyz[2];
     mseg[q] = s;
 }
 
@@ -586,50 +581,61 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_ragged_kernel(
     }
 }
 
-// ---- workspace layouts (bytes, each part 256-aligned) -----------------------------------------------------------
+// ---- workspace layouts: one function each, for the query (null workspace) and the launcher ---------------------------
 
-struct FsLayout {
-    size_t table, blk_count, seg_blk_off, seg_size, mask_off, mxyz, mseg, flags, fblk_count, fblk_off, total;
+struct FsWorkspace {
+    int nblk, gblk;                            // 256-pixel blocks of a frame, 256-point blocks of all frames
+    int *table, *blk_count, *seg_blk_off, *seg_size, *mask_off, *mseg, *fblk_count, *fblk_off;
+    float *mxyz;
+    uint8_t *flags;
+    size_t bytes;
 };
 
-FsLayout fs_layout(int f, int h, int w, int s)
+FsWorkspace fs_workspace(int f, int h, int w, int s, void *workspace)
 {
     const long long hw = (long long)h * w, m = (long long)f * hw;
     const long long nblk = (hw + SEG_BLOCK - 1) / SEG_BLOCK, gblk = (m + SEG_BLOCK - 1) / SEG_BLOCK;
-    FsLayout L;
-    size_t o = 0;
-    L.table = o;       o += align_up(sizeof(int) * (size_t)f * SEG_CLASSES);
-    L.blk_count = o;   o += align_up(sizeof(int) * (size_t)f * nblk * SEG_CLASSES);
-    L.seg_blk_off = o; o += align_up(sizeof(int) * (size_t)s * (nblk + 1));
-    L.seg_size = o;    o += align_up(sizeof(int) * (size_t)s);
-    L.mask_off = o;    o += align_up(sizeof(int) * (size_t)(s + 1));
-    L.mxyz = o;        o += align_up(sizeof(float) * 3 * (size_t)m);
-    L.mseg = o;        o += align_up(sizeof(int) * (size_t)m);
-    L.flags = o;       o += align_up((size_t)m);
-    L.fblk_count = o;  o += align_up(sizeof(int) * (size_t)gblk);
-    L.fblk_off = o;    o += align_up(sizeof(int) * (size_t)(gblk + 1));
-    L.total = o;
+    Carver ws(workspace);
+    FsWorkspace L;
+    L.nblk = (int)nblk, L.gblk = (int)gblk;
+    L.table = ws.take<int>((size_t)f * SEG_CLASSES);
+    L.blk_count = ws.take<int>((size_t)f * nblk * SEG_CLASSES);
+    L.seg_blk_off = ws.take<int>((size_t)s * (nblk + 1));
+    L.seg_size = ws.take<int>((size_t)s);
+    L.mask_off = ws.take<int>((size_t)(s + 1));
+    L.mxyz = ws.take<float>(3 * (size_t)m);
+    L.mseg = ws.take<int>((size_t)m);
+    L.flags = ws.take<uint8_t>((size_t)m);
+    L.fblk_count = ws.take<int>((size_t)gblk);
+    L.fblk_off = ws.take<int>((size_t)(gblk + 1));
+    L.bytes = ws.bytes();
     return L;
 }
 
-struct RoLayout {
-    size_t grids, cell_start, sorted, seg, flags, seg_count, blk_count, blk_off, total;
+struct RoWorkspace {
+    int gblk;                                  // 256-point blocks
+    RoGrid *grids;
+    int *cell_start, *seg, *seg_count, *blk_count, *blk_off;
+    float4 *sorted;
+    uint8_t *flags;
+    size_t bytes;
 };
 
-RoLayout ro_layout(int s, long long m)
+RoWorkspace ro_workspace(int s, long long m, void *workspace)
 {
     const long long gblk = (m + SEG_BLOCK - 1) / SEG_BLOCK;
-    RoLayout L;
-    size_t o = 0;
-    L.grids = o;      o += align_up(sizeof(RoGrid) * (size_t)s);
-    L.cell_start = o; o += align_up(sizeof(int) * (size_t)s * (RO_CELLS + 1));
-    L.sorted = o;     o += align_up(sizeof(float4) * (size_t)m);
-    L.seg = o;        o += align_up(sizeof(int) * (size_t)m);
-    L.flags = o;      o += align_up((size_t)m);
-    L.seg_count = o;  o += align_up(sizeof(int) * (size_t)s);
-    L.blk_count = o;  o += align_up(sizeof(int) * (size_t)gblk);
-    L.blk_off = o;    o += align_up(sizeof(int) * (size_t)(gblk + 1));
-    L.total = o;
+    Carver ws(workspace);
+    RoWorkspace L;
+    L.gblk = (int)gblk;
+    L.grids = ws.take<RoGrid>((size_t)s);
+    L.cell_start = ws.take<int>((size_t)s * (RO_CELLS + 1));
+    L.sorted = ws.take<float4>((size_t)m);
+    L.seg = ws.take<int>((size_t)m);
+    L.flags = ws.take<uint8_t>((size_t)m);
+    L.seg_count = ws.take<int>((size_t)s);
+    L.blk_count = ws.take<int>((size_t)gblk);
+    L.blk_off = ws.take<int>((size_t)(gblk + 1));
+    L.bytes = ws.bytes();
     return L;
 }
 
@@ -650,7 +656,7 @@ CLOUDAAE_API long long cloudaae_frame_segments_workspace_bytes(int f, int h, int
 {
     if (f < 1 || h < 1 || w < 1 || s < 0 || (long long)f * h * w > SEG_MAX_POINTS)
         return -1;
-    return (long long)fs_layout(f, h, w, s).total;
+    return (long long)fs_workspace(f, h, w, s, nullptr).bytes;
 }
 
 CLOUDAAE_API int cloudaae_frame_segments(int f, int h, int w, const uint16_t *depth, const uint8_t *label,
@@ -665,38 +671,30 @@ CLOUDAAE_API int cloudaae_frame_segments(int f, int h, int w, const uint16_t *de
     CLOUDAAE_REQUIRE(threshold == threshold, name, "threshold must not be NaN");
     CLOUDAAE_REQUIRE(depth && label && intrinsics && seg_frame && seg_class && offsets && xyz && mean && workspace,
                      name, "null pointer");
-    const FsLayout L = fs_layout(f, h, w, s);
-    CLOUDAAE_REQUIRE(workspace_bytes >= (long long)L.total, name,
+    const FsWorkspace L = fs_workspace(f, h, w, s, workspace);
+    CLOUDAAE_REQUIRE(workspace_bytes >= (long long)L.bytes, name,
                      "workspace smaller than cloudaae_frame_segments_workspace_bytes");
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    int *table = (int *)(ws + L.table), *blk_count = (int *)(ws + L.blk_count);
-    int *seg_blk_off = (int *)(ws + L.seg_blk_off), *seg_size = (int *)(ws + L.seg_size);
-    int *mask_off = (int *)(ws + L.mask_off), *mseg = (int *)(ws + L.mseg);
-    float *mxyz = (float *)(ws + L.mxyz);
-    uint8_t *flags = (uint8_t *)(ws + L.flags);
-    int *fblk_count = (int *)(ws + L.fblk_count), *fblk_off = (int *)(ws + L.fblk_off);
-    const int hw = h * w, nblk = ceil_div(hw, SEG_BLOCK);
+    const int hw = h * w, nblk = L.nblk, gblk = L.gblk;
     const long long m = (long long)f * hw;
-    const int gblk = ceil_div(m, SEG_BLOCK);
 
-    CLOUDAAE_CHECK_HIP(hipMemsetAsync(table, 0xff, sizeof(int) * (size_t)f * SEG_CLASSES, st), name);
-    hipLaunchKernelGGL(fs_table_kernel, dim3(ceil_div(s, 256)), dim3(256), 0, st, f, s, seg_frame, seg_class, table);
-    hipLaunchKernelGGL(fs_count_kernel, dim3(nblk, f), dim3(SEG_BLOCK), 0, st, hw, nblk, depth, label, table,
-                       blk_count);
+    CLOUDAAE_CHECK_HIP(hipMemsetAsync(L.table, 0xff, sizeof(int) * (size_t)f * SEG_CLASSES, st), name);
+    hipLaunchKernelGGL(fs_table_kernel, dim3(ceil_div(s, 256)), dim3(256), 0, st, f, s, seg_frame, seg_class, L.table);
+    hipLaunchKernelGGL(fs_count_kernel, dim3(nblk, f), dim3(SEG_BLOCK), 0, st, hw, nblk, depth, label, L.table,
+                       L.blk_count);
     hipLaunchKernelGGL(fs_seg_scan_kernel, dim3(s), dim3(SEG_SCAN_THREADS), 0, st, f, nblk, seg_frame, seg_class,
-                       table, blk_count, seg_blk_off, seg_size);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SEG_SCAN_THREADS), 0, st, seg_size, s, mask_off);
+                       L.table, L.blk_count, L.seg_blk_off, L.seg_size);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SEG_SCAN_THREADS), 0, st, L.seg_size, s, L.mask_off);
     hipLaunchKernelGGL(fs_scatter_kernel, dim3(nblk, f), dim3(SEG_BLOCK), 0, st, hw, w, nblk, depth, label,
-                       intrinsics, table, seg_blk_off, mask_off, mxyz, mseg);
-    hipLaunchKernelGGL(fs_mean_kernel, dim3(ceil_div(3ll * s, 64)), dim3(64), 0, st, s, mask_off, mxyz, mean);
-    hipLaunchKernelGGL(fs_filter_flags_kernel, dim3(gblk), dim3(SEG_BLOCK), 0, st, mask_off + s, m, mxyz, mseg, mean,
-                       threshold, flags, fblk_count);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SEG_SCAN_THREADS), 0, st, fblk_count, gblk, fblk_off);
-    hipLaunchKernelGGL(compact_scatter_kernel, dim3(gblk), dim3(SEG_BLOCK), 0, st, mask_off + s, m, flags, fblk_off, mxyz,
-                       mseg, mask_off, xyz, (int *)nullptr, (int *)nullptr);
-    hipLaunchKernelGGL(compact_offsets_kernel, dim3(ceil_div(s + 1, 256)), dim3(256), 0, st, s, mask_off, flags,
-                       fblk_off, offsets);
+                       intrinsics, L.table, L.seg_blk_off, L.mask_off, L.mxyz, L.mseg);
+    hipLaunchKernelGGL(fs_mean_kernel, dim3(ceil_div(3ll * s, 64)), dim3(64), 0, st, s, L.mask_off, L.mxyz, mean);
+    hipLaunchKernelGGL(fs_filter_flags_kernel, dim3(gblk), dim3(SEG_BLOCK), 0, st, L.mask_off + s, m, L.mxyz, L.mseg, mean,
+                       threshold, L.flags, L.fblk_count);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SEG_SCAN_THREADS), 0, st, L.fblk_count, gblk, L.fblk_off);
+    hipLaunchKernelGGL(compact_scatter_kernel, dim3(gblk), dim3(SEG_BLOCK), 0, st, L.mask_off + s, m, L.flags, L.fblk_off, L.mxyz,
+                       L.mseg, L.mask_off, xyz, (int *)nullptr, (int *)nullptr);
+    hipLaunchKernelGGL(compact_offsets_kernel, dim3(ceil_div(s + 1, 256)), dim3(256), 0, st, s, L.mask_off, L.flags,
+                       L.fblk_off, offsets);
     CLOUDAAE_CHECK_LAUNCH(name);
     return 0;
 }
@@ -705,7 +703,7 @@ CLOUDAAE_API long long cloudaae_radius_outlier_workspace_bytes(int s, long long 
 {
     if (s < 1 || max_points < 0 || max_points > SEG_MAX_POINTS)
         return -1;
-    return (long long)ro_layout(s, max_points).total;
+    return (long long)ro_workspace(s, max_points, nullptr).bytes;
 }
 
 CLOUDAAE_API int cloudaae_radius_outlier(int s, const int *offsets, const float *xyz, long long max_points,
@@ -720,33 +718,27 @@ CLOUDAAE_API int cloudaae_radius_outlier(int s, const int *offsets, const float 
     CLOUDAAE_REQUIRE(radius > 0.0f && isfinite(radius), name, "radius must be a finite number > 0");
     CLOUDAAE_REQUIRE(offsets && xyz && in_offsets && in_index && in_xyz && num_valid && workspace, name,
                      "null pointer");
-    const RoLayout L = ro_layout(s, max_points);
-    CLOUDAAE_REQUIRE(workspace_bytes >= (long long)L.total, name,
+    const RoWorkspace L = ro_workspace(s, max_points, workspace);
+    CLOUDAAE_REQUIRE(workspace_bytes >= (long long)L.bytes, name,
                      "workspace smaller than cloudaae_radius_outlier_workspace_bytes");
     hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    RoGrid *grids = (RoGrid *)(ws + L.grids);
-    int *cell_start = (int *)(ws + L.cell_start), *seg = (int *)(ws + L.seg), *seg_count = (int *)(ws + L.seg_count);
-    float4 *sorted = (float4 *)(ws + L.sorted);
-    uint8_t *flags = (uint8_t *)(ws + L.flags);
-    int *blk_count = (int *)(ws + L.blk_count), *blk_off = (int *)(ws + L.blk_off);
-    const int gblk = ceil_div(max_points, SEG_BLOCK);
+    const int gblk = L.gblk;
     constexpr size_t lds = sizeof(int) * RO_CELLS;      // (the same for every launch)
     CLOUDAAE_CHECK_HIP(allow_dynamic_lds<ro_grid_kernel>(lds, lds), name);
-    CLOUDAAE_CHECK_HIP(hipMemsetAsync(seg_count, 0, sizeof(int) * (size_t)s, st), name);
-    hipLaunchKernelGGL(seg_fill_kernel, dim3(64, s), dim3(256), 0, st, offsets, max_points, seg);
-    hipLaunchKernelGGL(ro_grid_kernel, dim3(s), dim3(RO_THREADS), lds, st, offsets, max_points, xyz, radius, grids, cell_start,
-                       sorted);
-    hipLaunchKernelGGL(ro_count_kernel, dim3(gblk), dim3(SEG_BLOCK), 0, st, offsets + s, max_points, offsets, seg, xyz, grids,
-                       cell_start, sorted, nb_points, radius, flags, seg_count);
-    hipLaunchKernelGGL(ro_inlier_flags_kernel, dim3(gblk), dim3(SEG_BLOCK), 0, st, offsets + s, max_points, seg, seg_count,
-                       min_keep, flags, blk_count);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SEG_SCAN_THREADS), 0, st, blk_count, gblk, blk_off);
-    hipLaunchKernelGGL(compact_scatter_kernel, dim3(gblk), dim3(SEG_BLOCK), 0, st, offsets + s, max_points, flags, blk_off, xyz,
-                       seg, offsets, in_xyz, (int *)nullptr, in_index);
-    hipLaunchKernelGGL(compact_offsets_kernel, dim3(ceil_div(s + 1, 256)), dim3(256), 0, st, s, offsets, flags,
-                       blk_off, in_offsets);
-    hipLaunchKernelGGL(ro_num_valid_kernel, dim3(ceil_div(s, 256)), dim3(256), 0, st, s, offsets, in_offsets, flags,
+    CLOUDAAE_CHECK_HIP(hipMemsetAsync(L.seg_count, 0, sizeof(int) * (size_t)s, st), name);
+    hipLaunchKernelGGL(seg_fill_kernel, dim3(64, s), dim3(256), 0, st, offsets, max_points, L.seg);
+    hipLaunchKernelGGL(ro_grid_kernel, dim3(s), dim3(RO_THREADS), lds, st, offsets, max_points, xyz, radius, L.grids, L.cell_start,
+                       L.sorted);
+    hipLaunchKernelGGL(ro_count_kernel, dim3(gblk), dim3(SEG_BLOCK), 0, st, offsets + s, max_points, offsets, L.seg, xyz, L.grids,
+                       L.cell_start, L.sorted, nb_points, radius, L.flags, L.seg_count);
+    hipLaunchKernelGGL(ro_inlier_flags_kernel, dim3(gblk), dim3(SEG_BLOCK), 0, st, offsets + s, max_points, L.seg, L.seg_count,
+                       min_keep, L.flags, L.blk_count);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(SEG_SCAN_THREADS), 0, st, L.blk_count, gblk, L.blk_off);
+    hipLaunchKernelGGL(compact_scatter_kernel, dim3(gblk), dim3(SEG_BLOCK), 0, st, offsets + s, max_points, L.flags, L.blk_off, xyz,
+                       L.seg, offsets, in_xyz, (int *)nullptr, in_index);
+    hipLaunchKernelGGL(compact_offsets_kernel, dim3(ceil_div(s + 1, 256)), dim3(256), 0, st, s, offsets, L.flags,
+                       L.blk_off, in_offsets);
+    hipLaunchKernelGGL(ro_num_valid_kernel, dim3(ceil_div(s, 256)), dim3(256), 0, st, s, offsets, in_offsets, L.flags,
                        num_valid);
     CLOUDAAE_CHECK_LAUNCH(name);
     return 0;
@@ -756,7 +748,7 @@ CLOUDAAE_API long long cloudaae_ragged_fps_workspace_bytes(long long max_points)
 {
     if (max_points < 0 || max_points > SEG_MAX_POINTS)
         return -1;
-    return (long long)align_up(sizeof(double) * (size_t)max_points);
+    return (long long)workspace_pad(sizeof(double) * (size_t)max_points);
 }
 
 CLOUDAAE_API int cloudaae_ragged_fps(int s, const int *offsets, const float *xyz, long long max_points, int k,

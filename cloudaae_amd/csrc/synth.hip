@@ -22,6 +22,7 @@
 // scipy.spatial.ConvexHull on real object models: identical sets).
 #include "common.h"
 #include "philox.h"
+#include "workspace.h"
 #include "../../include/cloudaae_hip.h"
 
 namespace cloudaae {
@@ -1036,12 +1037,29 @@ CLOUDAAE_API int cloudaae_spherical_flip(int b, int na, const float *a, int nb, 
     return 0;
 }
 
-// flags [b*n1] bytes (padded to 16) | sorted points [b*n1*3] floats | permutation [b*n1] ints | point queues [b] ints
-CLOUDAAE_API long long cloudaae_hpr_workspace_bytes(int b, int n1)
+// The workspace of hidden point removal (null: the size alone is asked for): flags [b, n1] bytes, padded to 16; sorted
+// points [b, n1, 3]; their permutation [b, n1]; the clouds' point queues [b].
+struct HprWorkspace {
+    unsigned char *flags;
+    float *sorted;
+    int *perm, *next_point;
+    size_t bytes;
+};
+
+static HprWorkspace hpr_workspace(int b, int n1, void *workspace)
 {
-    const long long pts = (long long)b * n1;
-    return (pts + 15) / 16 * 16 + pts * 12 + pts * 4 + (long long)b * 4;
+    const size_t pts = (size_t)b * n1;
+    Carver ws(workspace);
+    HprWorkspace L;
+    L.flags = ws.take<unsigned char>(pts, 16);
+    L.sorted = ws.take<float>(3 * pts, sizeof(float));
+    L.perm = ws.take<int>(pts, sizeof(int));
+    L.next_point = ws.take<int>((size_t)b, sizeof(int));
+    L.bytes = ws.bytes();
+    return L;
 }
+
+CLOUDAAE_API long long cloudaae_hpr_workspace_bytes(int b, int n1) { return (long long)hpr_workspace(b, n1, nullptr).bytes; }
 
 CLOUDAAE_API int cloudaae_hidden_point_removal(int b, int n1, const float *flipped, const float *org,
                                                unsigned long long seed, float *visible, long long *num_vis,
@@ -1075,15 +1093,11 @@ CLOUDAAE_API int cloudaae_hidden_point_removal_rows(int b, int n1, const float *
     if (b == 0)
         return 0;
     hipStream_t s = (hipStream_t)stream;
-    unsigned char *flags = (unsigned char *)workspace;
-    const size_t pts = (size_t)b * n1;
-    float *sorted = (float *)(flags + (pts + 15) / 16 * 16);
-    int *perm = (int *)(sorted + pts * 3);
-    int *next_point = perm + pts;
+    const HprWorkspace L = hpr_workspace(b, n1, workspace);
     // spatial order of every cloud: the 3-D grid in Morton order
     constexpr size_t grid_lds = HG_CELLS * sizeof(int);      // (the same for every launch)
     CLOUDAAE_CHECK_HIP(allow_dynamic_lds<hpr_sort_grid_kernel>(grid_lds, grid_lds), name);
-    hipLaunchKernelGGL(hpr_sort_grid_kernel, dim3(b), dim3(HS_THREADS), grid_lds, s, n1, flipped, sorted, perm, next_point);
+    hipLaunchKernelGGL(hpr_sort_grid_kernel, dim3(b), dim3(HS_THREADS), grid_lds, s, n1, flipped, L.sorted, L.perm, L.next_point);
     // a cloud that leaves room for ONE workgroup per CU (more than ~5900 points) takes 16 waves instead of 8: the 8-wave form
     // never gets more than half a CU less its static LDS, the 16-wave form what the check above lets through
     const bool wide = 2 * (lds + static_lds[0]) > CU_LDS;
@@ -1102,15 +1116,15 @@ CLOUDAAE_API int cloudaae_hidden_point_removal_rows(int b, int n1, const float *
     const int cull_knob = CLOUDAAE_KNOB("CLOUDAAE_HPR_CULL", 1);
     const int culled = cull_knob <= 0 ? 0 : (cull_knob == 1 ? HPR_EXTRA + 1 : cull_knob - 1);    // 0 = off, else the cap + 1
     if (wide)
-        hipLaunchKernelGGL(hull_vertex_kernel<16>, dim3(gx, b), dim3(64 * 16), lds, s, n1, sorted, perm, hpr_stride(n1), culled,
-                           next_point, flags);
+        hipLaunchKernelGGL(hull_vertex_kernel<16>, dim3(gx, b), dim3(64 * 16), lds, s, n1, L.sorted, L.perm, hpr_stride(n1), culled,
+                           L.next_point, L.flags);
     else
-        hipLaunchKernelGGL(hull_vertex_kernel<8>, dim3(gx, b), dim3(64 * 8), lds, s, n1, sorted, perm, hpr_stride(n1), culled,
-                           next_point, flags);
+        hipLaunchKernelGGL(hull_vertex_kernel<8>, dim3(gx, b), dim3(64 * 8), lds, s, n1, L.sorted, L.perm, hpr_stride(n1), culled,
+                           L.next_point, L.flags);
     // (an int per point where the hull test keeps three floats: a third of what the check above lets through)
     const size_t gather_lds = (size_t)n1 * sizeof(int);
     CLOUDAAE_CHECK_HIP(allow_dynamic_lds<hpr_gather_kernel>(gather_lds, (CU_LDS - static_lds[1]) / 3), name);
-    hipLaunchKernelGGL(hpr_gather_kernel, dim3(b), dim3(512), gather_lds, s, n1, flags, org, seed, visible, num_vis,
+    hipLaunchKernelGGL(hpr_gather_kernel, dim3(b), dim3(512), gather_lds, s, n1, L.flags, org, seed, visible, num_vis,
                        visible_id, row_src, rows);
     CLOUDAAE_CHECK_LAUNCH(name);
     return 0;
