@@ -442,6 +442,12 @@ def lib():
         cdll.cloudaae_fc_plan.argtypes = [_I, _I, _I, _I, _I, _I, _I, _P]
         cdll.cloudaae_fc_plan.restype = ctypes.c_int
         cdll.cloudaae_edgeconv_workspace_bytes.argtypes = [_I]
+        # which kernel a call of the point-cloud ops takes (host only; the encodings are in include/cloudaae_hip.h)
+        for q, sig in (("cloudaae_farthest_point_sample_variant", [_I]),
+                       ("cloudaae_knn_variant", [_I, _I, _I, _I, _I, _I]),
+                       ("cloudaae_nn_distance_variant", [_I, _I, _I])):
+            getattr(cdll, q).argtypes = sig
+            getattr(cdll, q).restype = ctypes.c_int
         for q in ("cloudaae_set_knob", "cloudaae_unset_knob"):
             getattr(cdll, q).restype = ctypes.c_int
         cdll.cloudaae_set_knob.argtypes = [ctypes.c_char_p, _I]

@@ -1641,41 +1641,63 @@ static int knn_scan_waves(long long tiles, int n, int k)
     return tiles >= 4096 ? 1 : 2;
 }
 
+// The list length the kernels are built for: the smallest of 10 / 20 / 32 that holds k.
+static int knn_list_length(int k) { return k <= 10 ? 10 : (k <= 20 ? 20 : 32); }
+
+// Which kernel a call takes: one of CLOUDAAE_KNN_* (include/cloudaae_hip.h).  cloudaae_knn launches what this returns and
+// cloudaae_knn_variant reports it.  aligned: x sits on a 16-byte boundary (with ld % 4 == 0 the C = 64 kernels read rows as
+// float4).
+static int knn_variant(int b, int n, int c, int ld, int k, bool aligned)
+{
+    const int K = knn_list_length(k);
+    const bool vec = ld % 4 == 0 && aligned;
+    if (c == 3 && K <= 20 && n <= 6144) {
+        // the matrix-core form wherever it fits (n >= 256, the cloud and the queues in LDS); knob CLOUDAAE_KNN3_WIDE = 0
+        // / 1 forces the choice (the tests cover both).  Measured, k = 10, continuous coordinates, wide / scan: n = 1024:
+        // B = 1 23 / 39 us, B = 8 24 / 40, B = 32 24 / 47, B = 128 91 / 104, B = 256 180 / 201; n = 256: B = 16 ... 64
+        // 12 / 21; n = 512: 17 / 29; [2, 4096] 61 / 88; [32, 4096, k = 20] 354 / 639.  (Clouds made of a few distinct
+        // points overflow the queues and pay the rescan: 48 us at B = 32 -- the scan kernel's time.)
+        const bool wide = CLOUDAAE_KNOB_SET("CLOUDAAE_KNN3_WIDE") ? CLOUDAAE_KNOB("CLOUDAAE_KNN3_WIDE", 0) != 0 : true;
+        if (wide && knn3_wide_fits(n, K))
+            return CLOUDAAE_KNN_C3_WIDE;
+        // candidate ranges per query tile: as few as still give every SIMD two waves (fewer ranges = fewer lists to
+        // fill: measured, n = 1024, k = 10, ranges 4 / 2 / 1: B = 32 47 / 55 / - us, B = 64 89 / 67 / - us,
+        // B = 128 170 / 127 / 105 us, B = 256 - / 243 / 202 us)
+        if ((long long)ceil_div(n, 64) * b >= 2048)
+            return CLOUDAAE_KNN_C3_SCAN_1;
+        if ((long long)ceil_div(n, 64) * b * 2 >= 2048)
+            return CLOUDAAE_KNN_C3_SCAN_2;
+        return CLOUDAAE_KNN_C3_SCAN_4;
+    }
+    if (c == 64 && vec && K <= 20 && n <= 16384) {
+        const long long tiles = (long long)ceil_div(n, KM_TILE) * b;
+        const int mode = knn_scan_waves(tiles, n, K);
+        if (mode == 5 && knn_wide_fits(n, K))
+            return CLOUDAAE_KNN_C64_WIDE;
+        return mode == 1 ? CLOUDAAE_KNN_C64_SCAN_1 : CLOUDAAE_KNN_C64_SCAN_2;
+    }
+    // anything else (other channel counts, k above 20, clouds beyond the LDS-resident forms): one lane per query, exact, slow
+    return CLOUDAAE_KNN_GENERIC;
+}
+
 template <int K>
 static hipError_t launch_knn(int b, int n, int c, int ld, int k, const float *x, int *nn_idx, hipStream_t s)
 {
-    const bool vec = ld % 4 == 0 && ((uintptr_t)x & 15) == 0;
-    if (c == 3 && K <= 20 && n <= 6144) {
-        if constexpr (K <= 20) {
-            // the matrix-core form wherever it fits (n >= 256, the cloud and the queues in LDS); knob CLOUDAAE_KNN3_WIDE = 0
-            // / 1 forces the choice (the tests cover both).  Measured, k = 10, continuous coordinates, wide / scan: n = 1024:
-            // B = 1 23 / 39 us, B = 8 24 / 40, B = 32 24 / 47, B = 128 91 / 104, B = 256 180 / 201; n = 256: B = 16 ... 64
-            // 12 / 21; n = 512: 17 / 29; [2, 4096] 61 / 88; [32, 4096, k = 20] 354 / 639.  (Clouds made of a few distinct
-            // points overflow the queues and pay the rescan: 48 us at B = 32 -- the scan kernel's time.)
-            const bool wide = CLOUDAAE_KNOB_SET("CLOUDAAE_KNN3_WIDE") ? CLOUDAAE_KNOB("CLOUDAAE_KNN3_WIDE", 0) != 0 : true;
-            if (wide && knn3_wide_fits(n, K))
-                return launch_knn3_wide<K>(b, n, ld, k, x, nn_idx, s);
-            // candidate ranges per query tile: as few as still give every SIMD two waves (fewer ranges = fewer lists to
-            // fill: measured, n = 1024, k = 10, ranges 4 / 2 / 1: B = 32 47 / 55 / - us, B = 64 89 / 67 / - us,
-            // B = 128 170 / 127 / 105 us, B = 256 - / 243 / 202 us)
-            if ((long long)ceil_div(n, 64) * b >= 2048)
-                return launch_knn3_scan<K, 1>(b, n, ld, k, x, nn_idx, s);
-            if ((long long)ceil_div(n, 64) * b * 2 >= 2048)
-                return launch_knn3_scan<K, 2>(b, n, ld, k, x, nn_idx, s);
-            return launch_knn3_scan<K, 4>(b, n, ld, k, x, nn_idx, s);
-        }
-    } else if (c == 64 && vec && K <= 20 && n <= 16384) {
-        if constexpr (K <= 20) {
-            const long long tiles = (long long)ceil_div(n, KM_TILE) * b;
-            const int mode = knn_scan_waves(tiles, n, K);
-            if (mode == 5 && knn_wide_fits(n, K))
-                return launch_knn_wide<K>(b, n, ld, k, x, nn_idx, s);
-            if (mode == 1)
-                return launch_knn_scan<K, 4, 1>(b, n, ld, k, x, nn_idx, s);
-            return launch_knn_scan<K, 4, 2>(b, n, ld, k, x, nn_idx, s);
+    const int variant = knn_variant(b, n, c, ld, k, ((uintptr_t)x & 15) == 0);
+    if constexpr (K <= 20) {        // (knn_variant names no other kernel than the generic one for longer lists)
+        switch (variant) {
+        case CLOUDAAE_KNN_C3_WIDE: return launch_knn3_wide<K>(b, n, ld, k, x, nn_idx, s);
+        case CLOUDAAE_KNN_C3_SCAN_1: return launch_knn3_scan<K, 1>(b, n, ld, k, x, nn_idx, s);
+        case CLOUDAAE_KNN_C3_SCAN_2: return launch_knn3_scan<K, 2>(b, n, ld, k, x, nn_idx, s);
+        case CLOUDAAE_KNN_C3_SCAN_4: return launch_knn3_scan<K, 4>(b, n, ld, k, x, nn_idx, s);
+        case CLOUDAAE_KNN_C64_WIDE: return launch_knn_wide<K>(b, n, ld, k, x, nn_idx, s);
+        case CLOUDAAE_KNN_C64_SCAN_1: return launch_knn_scan<K, 4, 1>(b, n, ld, k, x, nn_idx, s);
+        case CLOUDAAE_KNN_C64_SCAN_2: return launch_knn_scan<K, 4, 2>(b, n, ld, k, x, nn_idx, s);
+        default: break;
         }
     }
-    // anything else (other channel counts, k above 20, clouds beyond the LDS-resident forms): one lane per query, exact, slow
+    if (variant != CLOUDAAE_KNN_GENERIC)
+        return hipErrorInvalidValue;
     hipLaunchKernelGGL(knn_generic_kernel<K>, dim3(ceil_div(n, KNN_THREADS), b), dim3(KNN_THREADS), 0, s, n, c, ld, k, x,
                        nn_idx);
     return hipSuccess;
@@ -1698,12 +1720,20 @@ CLOUDAAE_API int cloudaae_knn(int b, int n, int c, int ld, int k, const float *x
     hipStream_t s = (hipStream_t)stream;
     // (a failed launch preparation -- e.g. a kernel's dynamic LDS cannot be allowed on this device -- is an
     //  error of the call, never a silently skipped kernel)
-    const hipError_t e = k <= 10 ? launch_knn<10>(b, n, c, ld, k, x, nn_idx, s)
-                       : k <= 20 ? launch_knn<20>(b, n, c, ld, k, x, nn_idx, s)
+    const int K = knn_list_length(k);
+    const hipError_t e = K == 10 ? launch_knn<10>(b, n, c, ld, k, x, nn_idx, s)
+                       : K == 20 ? launch_knn<20>(b, n, c, ld, k, x, nn_idx, s)
                                  : launch_knn<32>(b, n, c, ld, k, x, nn_idx, s);
     CLOUDAAE_CHECK_HIP(e, name);
     CLOUDAAE_CHECK_LAUNCH(name);
     return 0;
+}
+
+CLOUDAAE_API int cloudaae_knn_variant(int b, int n, int c, int ld, int k, int x_aligned)
+{
+    if (b <= 0 || n <= 0 || c <= 0 || ld < c || k < 1 || k > 32 || k > n || b > 65535)
+        return -1;      // (cloudaae_knn refuses the call or launches nothing)
+    return knn_variant(b, n, c, ld, k, x_aligned != 0) | (knn_list_length(k) << 8);
 }
 
 // cloudaae_knn over 64 channels with a HINT: hint[b, n, k] = k distinct indices per point that are likely to be near it (the

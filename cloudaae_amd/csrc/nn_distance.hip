@@ -1011,6 +1011,23 @@ __global__ __launch_bounds__(256) void nn_distance_grad_ordered_kernel(
 
 using namespace cloudaae;
 
+// Which search a call takes (what nn_distance_impl launches and what cloudaae_nn_distance_variant reports):
+// CLOUDAAE_NN_FILTER_KERNEL, or the queries per lane Q = 1 / 2 / 4 of nn_distance_kernel<Q>.
+static int nn_search_variant(int b, int n, int m)
+{
+    // large clouds: the search on the matrix cores, the reference's arithmetic where it decides
+    // (CLOUDAAE_NN_FILTER=0/1 forces the choice, for tests and measurements)
+    bool filter = n >= 512 && m >= 512 && (long long)b * ((long long)n + m) >= 64 * NF_QBLOCK;
+    if (CLOUDAAE_KNOB_SET("CLOUDAAE_NN_FILTER"))
+        filter = CLOUDAAE_KNOB("CLOUDAAE_NN_FILTER", 0) != 0 && n > 0 && m > 0;
+    if (filter)
+        return CLOUDAAE_NN_FILTER_KERNEL;
+    // queries per lane: enough workgroups to fill 256 CUs first, then amortise
+    // LDS reads over more queries
+    const long long total = (long long)b * ((long long)n + m);
+    return total >= 4LL * 256 * 1024 ? 4 : (total >= 256LL * 1024 ? 2 : 1);
+}
+
 static int nn_distance_impl(const char *name, int b, int n, const float *xyz1, int m, const float *xyz2,
                             const long long *count2, const int *row_src2, float *dist1, int *idx1, float *dist2, int *idx2,
                             cloudaae_stream_t stream)
@@ -1020,13 +1037,9 @@ static int nn_distance_impl(const char *name, int b, int n, const float *xyz1, i
         return 0;
     CLOUDAAE_REQUIRE(b <= 65535, name, "batch > 65535");
     hipStream_t s = (hipStream_t)stream;
-    // large clouds: the search on the matrix cores, the reference's arithmetic where it decides
-    // (CLOUDAAE_NN_FILTER=0/1 forces the choice, for tests and measurements)
-    bool filter = n >= 512 && m >= 512 && (long long)b * ((long long)n + m) >= 64 * NF_QBLOCK;
-    if (CLOUDAAE_KNOB_SET("CLOUDAAE_NN_FILTER"))
-        filter = CLOUDAAE_KNOB("CLOUDAAE_NN_FILTER", 0) != 0 && n > 0 && m > 0;
+    const int variant = nn_search_variant(b, n, m);
     unsigned long long *keys = nullptr;     // (filter kernel, split candidates) scratch of the call, stream ordered
-    if (filter) {
+    if (variant == CLOUDAAE_NN_FILTER_KERNEL) {
         const int t1 = ceil_div(n, NF_QBLOCK), t2 = ceil_div(m, NF_QBLOCK);
         // A direction with fewer query blocks than the chip has CUs and many candidates (clouds of unequal size) is
         // cut over its candidates until it has ~4 workgroups per CU, ranges no shorter than NF_RANGE_STEP.
@@ -1063,10 +1076,7 @@ static int nn_distance_impl(const char *name, int b, int n, const float *xyz1, i
             hipLaunchKernelGGL(nn_distance_unpack_kernel, dim3(ceil_div((long long)c2, 256)), dim3(256), 0, s,
                                (long long)c2, k2, dist2, idx2);
     } else {
-        // queries per lane: enough workgroups to fill 256 CUs first, then amortise
-        // LDS reads over more queries
-        const long long total = (long long)b * ((long long)n + m);
-        int Q = total >= 4LL * 256 * 1024 ? 4 : (total >= 256LL * 1024 ? 2 : 1);
+        const int Q = variant;
         const int t1 = ceil_div(n, NN_THREADS * Q), t2 = ceil_div(m, NN_THREADS * Q);
         dim3 grid(t1 + t2, b), block(NN_THREADS);
         if (Q == 4)
@@ -1103,6 +1113,13 @@ CLOUDAAE_API int cloudaae_nn_distance(int b, int n, const float *xyz1, int m, co
                                       cloudaae_stream_t stream)
 {
     return nn_distance_impl("cloudaae_nn_distance", b, n, xyz1, m, xyz2, nullptr, nullptr, dist1, idx1, dist2, idx2, stream);
+}
+
+CLOUDAAE_API int cloudaae_nn_distance_variant(int b, int n, int m)
+{
+    if (b <= 0 || n < 0 || m < 0 || (n == 0 && m == 0) || b > 65535)
+        return -1;      // (cloudaae_nn_distance refuses the call or launches nothing)
+    return nn_search_variant(b, n, m);
 }
 
 CLOUDAAE_API int cloudaae_nn_distance_prefix(int b, int n, const float *xyz1, int m, const float *xyz2,

@@ -227,12 +227,26 @@ __global__ __launch_bounds__(256) void scatter_add_point_kernel(int n, int m,
     atomicAdd(dst + 2, src[2]);
 }
 
-template <int PPT>
-static int launch_fps_reg(int b, int n, int m, const float *inp, int *out, hipStream_t s)
+// Which kernel a cloud of n points takes (what cloudaae_farthest_point_sample launches and what
+// cloudaae_farthest_point_sample_variant reports): the smallest PPT of fps_kernel with n <= 512 * PPT, the winner's
+// coordinates from the cloud's copy in LDS while that copy fits FPS_MAX_LDS; fps_big_kernel beyond 512 * 32 points.
+constexpr size_t FPS_MAX_LDS = 144 * 1024;      // the largest cloud kept in LDS (gfx950 has 160 KiB per CU)
+constexpr int FPS_MAX_PPT = 32;
+static int fps_variant(int n)
 {
-    constexpr size_t FPS_MAX_LDS = 144 * 1024;      // the largest cloud kept in LDS (gfx950 has 160 KiB per CU)
-    const size_t lds = (size_t)n * 3 * sizeof(float);
-    if (lds <= FPS_MAX_LDS) {
+    if (n > FPS_THREADS * FPS_MAX_PPT)
+        return CLOUDAAE_FPS_BIG;
+    int ppt = 1;
+    while (n > FPS_THREADS * ppt)
+        ppt *= 2;
+    return (size_t)n * 3 * sizeof(float) <= FPS_MAX_LDS ? ppt : ppt | CLOUDAAE_FPS_XYZ_FROM_MEMORY;
+}
+
+template <int PPT>
+static int launch_fps_reg(bool lds_xyz, int b, int n, int m, const float *inp, int *out, hipStream_t s)
+{
+    if (lds_xyz) {
+        const size_t lds = (size_t)n * 3 * sizeof(float);
         constexpr auto kernel = &fps_kernel<PPT, true>;
         CLOUDAAE_CHECK_HIP(allow_dynamic_lds<kernel>(lds, FPS_MAX_LDS), "cloudaae_farthest_point_sample");
         hipLaunchKernelGGL(kernel, dim3(b), dim3(FPS_THREADS), lds, s, n, m,
@@ -343,19 +357,16 @@ CLOUDAAE_API int cloudaae_farthest_point_sample(int b, int n, int m, const float
     CLOUDAAE_REQUIRE(n > 0, name, "empty cloud");
     hipStream_t s = (hipStream_t)stream;
     int rc = 0;
-    if (n <= 512)
-        rc = launch_fps_reg<1>(b, n, m, inp, out, s);
-    else if (n <= 1024)
-        rc = launch_fps_reg<2>(b, n, m, inp, out, s);
-    else if (n <= 2048)
-        rc = launch_fps_reg<4>(b, n, m, inp, out, s);
-    else if (n <= 4096)
-        rc = launch_fps_reg<8>(b, n, m, inp, out, s);
-    else if (n <= 8192)
-        rc = launch_fps_reg<16>(b, n, m, inp, out, s);
-    else if (n <= 16384)
-        rc = launch_fps_reg<32>(b, n, m, inp, out, s);
-    else {
+    const int variant = fps_variant(n);
+    const bool lds_xyz = !(variant & CLOUDAAE_FPS_XYZ_FROM_MEMORY);
+    switch (variant & CLOUDAAE_FPS_PPT_MASK) {
+    case 1: rc = launch_fps_reg<1>(lds_xyz, b, n, m, inp, out, s); break;
+    case 2: rc = launch_fps_reg<2>(lds_xyz, b, n, m, inp, out, s); break;
+    case 4: rc = launch_fps_reg<4>(lds_xyz, b, n, m, inp, out, s); break;
+    case 8: rc = launch_fps_reg<8>(lds_xyz, b, n, m, inp, out, s); break;
+    case 16: rc = launch_fps_reg<16>(lds_xyz, b, n, m, inp, out, s); break;
+    case 32: rc = launch_fps_reg<32>(lds_xyz, b, n, m, inp, out, s); break;
+    default:    // CLOUDAAE_FPS_BIG
         CLOUDAAE_REQUIRE(temp != nullptr, name, "n > 16384 needs the 32*n float workspace");
         hipLaunchKernelGGL(fps_big_kernel, dim3(b < 32 ? b : 32), dim3(FPS_THREADS), 0, s, b, n, m,
                            inp, temp, out);
@@ -365,6 +376,8 @@ CLOUDAAE_API int cloudaae_farthest_point_sample(int b, int n, int m, const float
     CLOUDAAE_CHECK_LAUNCH(name);
     return 0;
 }
+
+CLOUDAAE_API int cloudaae_farthest_point_sample_variant(int n) { return n > 0 ? fps_variant(n) : -1; }
 
 CLOUDAAE_API int cloudaae_gather_point(int b, int n, int m, const float *inp, const int *idx,
                                        float *out, cloudaae_stream_t stream)

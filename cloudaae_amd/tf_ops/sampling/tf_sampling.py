@@ -107,6 +107,9 @@ def gather_point_grad(inp, idx, out_g):
     require(idx.dim() == 2 and idx.shape[0] == b, "GatherPointGradGpuOp expects (batch_size,num_result) idx shape")
     m = idx.shape[1]
     require(tuple(out_g.shape) == (b, m, 3), "GatherPointGradGpuOp expects (batch_size,num_result,3) out_g shape")
+    # (the kernel reads idx as int32 and out_g as float32 whatever the tensors hold: what _GatherPoint.forward refuses)
+    require(inp.dtype == torch.float32 and out_g.dtype == torch.float32 and idx.dtype == torch.int32,
+            "GatherPointGrad: inp and out_g float32, idx int32")
     inp_g = _lib.empty((b, n, 3), dtype=torch.float32, device=out_g.device)
     _lib.check(_lib.lib().cloudaae_gather_point_grad(b, n, m, ptr(out_g.contiguous()),
                                                      ptr(idx.contiguous()), ptr(inp_g), stream()),

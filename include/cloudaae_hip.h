@@ -59,7 +59,8 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * cloudaae_depth_fit_counts_window and cloudaae_detect_assign; cloudaae_depth_creases with its workspace query;
  * cloudaae_depth_align_step with its workspace query; cloudaae_depth_edge_nearest, cloudaae_depth_contour_sums with its
  * workspace query and cloudaae_depth_align_solve; cloudaae_tsdf_integrate, cloudaae_tsdf_count and cloudaae_tsdf_emit;
- * cloudaae_tsdf_raycast. */
+ * cloudaae_tsdf_raycast; cloudaae_farthest_point_sample_variant, cloudaae_knn_variant and cloudaae_nn_distance_variant
+ * (host-only queries: which kernel a call takes). */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -115,6 +116,13 @@ int cloudaae_nn_distance(int b, int n, const float *xyz1, int m, const float *xy
 int cloudaae_nn_distance_prefix(int b, int n, const float *xyz1, int m, const float *xyz2, const long long *count2,
                                 const int *row_src2, float *dist1, int *idx1, float *dist2, int *idx2,
                                 cloudaae_stream_t stream);
+/* Which search cloudaae_nn_distance / cloudaae_nn_distance_prefix run for these sizes, decided by the function the launch
+ * itself calls (same thresholds, same knob CLOUDAAE_NN_FILTER, read at the time of the query): CLOUDAAE_NN_FILTER_KERNEL
+ * (0) = the matrix-core filter with exact verification; 1, 2 or 4 = the plain search with that many queries per lane.
+ * -1: sizes the entry points refuse, or for which they launch nothing.  Host only: launches nothing, touches no device
+ * memory. */
+#define CLOUDAAE_NN_FILTER_KERNEL 0
+int cloudaae_nn_distance_variant(int b, int n, int m);
 
 /* Development / test entry: the search scores of cloudaae_nn_distance's large-cloud kernel (|b'|^2 - 2 a'.b' of coordinates
  * centred on candidates[0], as error-free three-piece bfloat16 split products on the bf16 matrix pipe) for nq <= 32 queries
@@ -164,6 +172,15 @@ int cloudaae_nn_distance_grad_uniform(int b, int n, const float *xyz1, int m, co
  *   otherwise. */
 int cloudaae_farthest_point_sample(int b, int n, int m, const float *inp, float *temp, int *out,
                                    cloudaae_stream_t stream);
+/* Which kernel cloudaae_farthest_point_sample runs for clouds of n points, decided by the function the launch itself
+ * calls.  CLOUDAAE_FPS_BIG: the kernel for clouds above 16384 points (running minima in `temp`).  Otherwise
+ * value & CLOUDAAE_FPS_PPT_MASK = the points a thread keeps in registers (1, 2, 4, 8, 16 or 32), and the bit
+ * CLOUDAAE_FPS_XYZ_FROM_MEMORY is set when the cloud is too large for a copy in LDS, so that the coordinates of a
+ * round's winner are read from memory.  -1: n <= 0.  Host only: launches nothing, touches no device memory. */
+#define CLOUDAAE_FPS_PPT_MASK 0xff
+#define CLOUDAAE_FPS_XYZ_FROM_MEMORY 0x100
+#define CLOUDAAE_FPS_BIG 0x200
+int cloudaae_farthest_point_sample_variant(int n);
 
 /* GatherPoint: out[i,j,:] = inp[i,idx[i,j],:].
  * Replaces: void gatherpointLauncher(int b,int n,int m,const float* inp,const int* idx,
@@ -198,6 +215,21 @@ int cloudaae_prob_sample(int b, int n, int m, const float *inp_p, const float *i
  * fp32 fma chain and |.|^2 a sequential un-fused sum (oracle_knn). */
 int cloudaae_knn(int b, int n, int c, int ld, int k, const float *x, int *nn_idx,
                  cloudaae_stream_t stream);
+/* Which kernel cloudaae_knn runs for these arguments, decided by the function the launch itself calls (same thresholds,
+ * same knobs CLOUDAAE_KNN3_WIDE and CLOUDAAE_KNN_SCAN, read at the time of the query).  x_aligned: whether x sits on a
+ * 16-byte boundary (the C = 64 kernels read rows as float4 and need it together with ld % 4 == 0).
+ * value & 0xff = one of CLOUDAAE_KNN_* below; value >> 8 = the list length the kernel is built for (10, 20 or 32: the
+ * smallest that holds k).  -1: arguments cloudaae_knn refuses, or for which it launches nothing.  Host only: launches
+ * nothing, touches no device memory. */
+#define CLOUDAAE_KNN_C3_WIDE 1    /* c = 3, matrix-core tiles, 16 waves per workgroup */
+#define CLOUDAAE_KNN_C3_SCAN_1 2  /* c = 3, whole-cloud scan, one candidate range per query tile (four query tiles per workgroup) */
+#define CLOUDAAE_KNN_C3_SCAN_2 3  /* ... two candidate ranges (two query tiles per workgroup) */
+#define CLOUDAAE_KNN_C3_SCAN_4 4  /* ... four candidate ranges (one query tile per workgroup) */
+#define CLOUDAAE_KNN_C64_WIDE 5   /* c = 64, bound pass + filtered scan, 16 waves per workgroup */
+#define CLOUDAAE_KNN_C64_SCAN_1 6 /* c = 64, whole-cloud scan, one wave per query tile */
+#define CLOUDAAE_KNN_C64_SCAN_2 7 /* c = 64, whole-cloud scan, two waves per query tile */
+#define CLOUDAAE_KNN_GENERIC 8    /* any c, k and n: one lane per query */
+int cloudaae_knn_variant(int b, int n, int c, int ld, int k, int x_aligned);
 /* The same with a HINT (revision 600): hint [b,n,k] int32 = k DISTINCT indices per point that are likely to be near it -- the
  * neighbour lists of the layer before (models/pointnet_ycb_23_decoder_4.py:337-404 recomputes the lists layer by layer on
  * features that change little).  Their largest distance bounds the k-th distance, so the scan needs no bound pass of its

@@ -44,7 +44,19 @@ def _clouds(kind, b, n, rng):
 @pytest.mark.parametrize("b,n,m,kind", [(1, 1, 4, "randn"), (3, 100, 100, "randn"), (2, 513, 64, "dup"), (4, 4096, 1024, "randn"),
                                         (1, 9000, 50, "dup"), (33, 2048, 128, "randn"), (1, 20000, 40, "randn"),
                                         (2, 1500, 300, "lattice"), (2, 700, 20, "same"), (5, 511, 511, "lattice"),
-                                        (40, 1024, 256, "dup"), (2, 3073, 100, "lattice")])
+                                        (40, 1024, 256, "dup"), (2, 3073, 100, "lattice"),
+                                        # either side of every size at which the launcher takes another kernel variant, the
+                                        # tie rounds past the lattice's 729 distinct points (m = 800), evaluation's call at N = 4096, the
+                                        # big kernel with more clouds than workgroups, no rounds, more rounds than points
+                                        # (tests/test_49_point_op_variants_gpu.py)
+                                        (2, 512, 96, "lattice"), (2, 513, 96, "lattice"), (2, 1024, 96, "lattice"),
+                                        (2, 1025, 96, "lattice"), (2, 2048, 96, "lattice"), (2, 2049, 96, "lattice"),
+                                        (2, 4096, 96, "lattice"), (2, 4097, 96, "lattice"), (2, 8192, 96, "lattice"),
+                                        (2, 8193, 96, "lattice"), (2, 12288, 96, "lattice"), (2, 12289, 96, "lattice"),
+                                        (2, 16384, 96, "lattice"), (2, 16385, 96, "lattice"), (2, 8192, 400, "lattice"),
+                                        (2, 16384, 400, "lattice"), (2, 8192, 800, "lattice"), (2, 16384, 800, "lattice"),
+                                        (2, 16384, 4096, "lattice"), (33, 16385, 48, "lattice"),
+                                        (70, 16500, 24, "lattice"), (3, 16385, 1, "lattice"), (2, 700, 900, "lattice")])
 def test_farthest_point_sampling_three_way(hip, refgpu, b, n, m, kind):
     from cloudaae_amd.tf_ops.sampling import tf_sampling
     p = _clouds(kind, b, n, np.random.default_rng(n * 7 + m))
@@ -94,7 +106,9 @@ def test_prob_sample_three_way(hip, refgpu, b, n, m):
 
 @pytest.mark.parametrize("b,n,m,kind", [(1, 1, 1, "randn"), (2, 3, 1000, "randn"), (3, 257, 255, "dup"), (2, 4096, 4096, "randn"),
                                         (2, 5000, 17, "lattice"), (5, 2100, 2049, "dup"), (32, 1024, 4096, "randn"),
-                                        (2, 600, 600, "same")])
+                                        (2, 600, 600, "same"),
+                                        # two and four queries per lane of the plain search, by the launcher's own choice
+                                        (257, 511, 511, "dup"), (600, 430, 7, "dup"), (2052, 256, 256, "dup")])
 def test_chamfer_search_three_way(hip, refgpu, b, n, m, kind):
     """NmDistanceKernel (tf_nndistance_g.cu:5-127, un-fused) == the reference's CPU lines (tf_nndistance.cpp:21-43) == ours:
     squared distances and first-wins indices, ties included"""

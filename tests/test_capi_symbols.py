@@ -23,6 +23,9 @@ def test_library_exports_every_declared_symbol():
     declared = _declared()
     assert len(declared) >= 8
     assert "cloudaae_fc_plan" in declared       # the path query tests/test_35_fc_paths_gpu.py states its coverage with
+    # the variant queries tests/test_49_point_op_variants_gpu.py names its cases with
+    for query in ("cloudaae_farthest_point_sample_variant", "cloudaae_knn_variant", "cloudaae_nn_distance_variant"):
+        assert query in declared
     missing = [n for n in declared if not hasattr(lib, n)]
     assert not missing, missing
     # one ABI revision: the header's, the library's and the Python host's signature table (cloudaae_amd/_lib.py)
