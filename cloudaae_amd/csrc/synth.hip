@@ -299,7 +299,7 @@ __device__ __forceinline__ int hpr_seq(int pos, int self, int n1, int stride, in
 constexpr double HPR_EPS = 1e-12;   // relative separation margin (qhull-like coplanarity tolerance)
 
 struct Cons {
-    double a, b, c;
+    double a, b, c, n;   // a s + b t <= c; n = |g|_1, the scale of a, b and c
 };
 
 // Frame of one candidate vertex p: r = unit vector from the cloud's centroid to p, (u, w) a unit
@@ -324,7 +324,50 @@ __device__ __forceinline__ Cons hpr_constraint(const float *__restrict__ pts, in
     k.a = (f.ux * gx + f.uy * gy) + f.uz * gz;
     k.b = (f.wx * gx + f.wy * gy) + f.wz * gz;
     k.c = -((f.rx * gx + f.ry * gy) + f.rz * gz) - HPR_EPS * nrm;
+    k.n = nrm;
     return k;
+}
+
+// The 1-D problem of a re-solve: the optimum moves onto the line p0 + t u of the violated constraint k, and every earlier
+// constraint m bounds t there: den t <= num.  Two cases are decided beyond the rounding error of num and den (HPR_ROUND, relative
+// to the constraints' scales), not at zero:
+//   * m PARALLEL to the line bounds nothing; it holds along the whole line or nowhere (bad).  The points of a straight row
+//     through p (g, 2g, 3g, ...: a lattice, an edge of a box sampled evenly) give the SAME half-plane scaled, for which num and
+//     den are both rounding noise around zero -- their quotient used to be a bound at a random place, and hull vertices were
+//     rejected (found with the corners of a 5 x 5 x 5 lattice);
+//   * lines that meet in ONE point of the (s, t) plane (the margin is eps |g|_1 and |.|_1 is additive inside an orthant: once
+//     d.g1 and d.g2 bind, d.(i g1 + j g2) binds too -- every point of the two faces at a box corner) give bounds that agree up
+//     to rounding, and `hi < lo` by round-off used to read as infeasible.  Every bound is therefore relaxed by its own
+//     rounding allowance, at most half the constraint's margin: an accepted plane still has d.g <= -eps |g|_1 / 2 < 0.
+constexpr double HPR_ROUND = 64.0 * 2.220446049250313e-16;
+struct HprLine {
+    double p0x, p0y, ux, uy;
+    double par;   // HPR_ROUND x the scale of k: |den| <= par * m.n reads as parallel
+    double p0n;   // |p0|_1
+};
+__device__ __forceinline__ HprLine hpr_line_of(const Cons &k, double nn)
+{
+    HprLine l;
+    l.p0x = k.a * k.c / nn;
+    l.p0y = k.b * k.c / nn;
+    l.ux = -k.b;
+    l.uy = k.a;
+    l.par = HPR_ROUND * k.n;
+    l.p0n = fabs(l.p0x) + fabs(l.p0y);
+    return l;
+}
+// false: m bounds nothing on the line (bad is raised if it holds nowhere on it); true: den t <= num, den != 0
+__device__ __forceinline__ bool hpr_line_bound(const Cons &m, const HprLine &l, double &num, double &den, bool &bad)
+{
+    den = m.a * l.ux + m.b * l.uy;
+    num = m.c - (m.a * l.p0x + m.b * l.p0y);
+    const double tol = fmin(HPR_ROUND * (fabs(m.c) + m.n * l.p0n), (0.5 * HPR_EPS) * m.n);
+    if (fabs(den) <= l.par * m.n) {
+        bad = bad || num < -tol;
+        return false;
+    }
+    num += tol;
+    return true;
 }
 
 // Seidel's incremental 2-variable LP on [-HPR_TAN, HPR_TAN]^2, objective x + y/2; returns feasibility.
@@ -422,37 +465,36 @@ __device__ bool hpr_lp2d_wave(const float *__restrict__ pts, int n1, int self, i
         }
         const int first = __ffsll((long long)mask) - 1;
         const Cons kf = hpr_constraint(pts, __shfl(q, first, 64), fr);     // 2-D form of the violated one only
-        const double ka = kf.a, kb = kf.b, kc = kf.c;
-        const double nn = ka * ka + kb * kb;
+        const double nn = kf.a * kf.a + kf.b * kf.b;
         if (nn == 0.0)
             return false;
-        const double p0x = ka * kc / nn, p0y = kb * kc / nn, ux = -kb, uy = ka;
+        const HprLine line = hpr_line_of(kf, nn);
+        const double p0x = line.p0x, p0y = line.p0y, ux = line.ux, uy = line.uy;
         // t in [lo, hi] with lo = max num/den over den<0 (stored with den > 0 after sign flip)
         Frac lo = {-1e300, 1.0}, hi = {1e300, 1.0};
         bool bad = false;
-        auto add = [&](double ca, double cb, double cc) {
-            const double den = ca * ux + cb * uy, num = cc - (ca * p0x + cb * p0y);
+        auto add = [&](const Cons &m) {
+            double num, den;
+            if (!hpr_line_bound(m, line, num, den, bad))
+                return;
             if (den > 0.0) {
                 const Frac f = {num, den};
                 if (frac_less(f, hi))
                     hi = f;
-            } else if (den < 0.0) {
+            } else {
                 const Frac f = {-num, -den};
                 if (frac_less(lo, f))
                     lo = f;
-            } else if (num < 0.0) {
-                bad = true;
             }
         };
         if (lane < 4)      // the box |x| <= HPR_TAN, |y| <= HPR_TAN
-            add(lane == 0 ? 1.0 : (lane == 1 ? -1.0 : 0.0), lane == 2 ? 1.0 : (lane == 3 ? -1.0 : 0.0), HPR_TAN);
+            add(Cons{lane == 0 ? 1.0 : (lane == 1 ? -1.0 : 0.0), lane == 2 ? 1.0 : (lane == 3 ? -1.0 : 0.0), HPR_TAN, 1.0});
         const int upto = i + first;            // sequence positions [0, upto) were already accepted
         for (int jpos = lane; jpos < upto; jpos += 64) {
             const int r = hpr_seq(jpos, self, n1, stride, near);
             if (r >= n1 || r == self)
                 continue;
-            const Cons m = hpr_constraint(pts, r, fr);
-            add(m.a, m.b, m.c);
+            add(hpr_constraint(pts, r, fr));
         }
         // wave reduction of lo (max) and hi (min) as fractions.  Inside a row of 16 lanes the partner
         // comes through DPP (quad swaps, then the half-row and row mirrors: after the quad steps a quad
@@ -623,35 +665,34 @@ __device__ int hpr_lp2d_wave_culled(const float *__restrict__ pts, const HprGrou
     // first `upto` members of the working set; false = infeasible
     auto resolve = [&](int qv, int upto) {
         const Cons kf = hpr_constraint(pts, qv, fr);
-        const double ka = kf.a, kb = kf.b, kc = kf.c;
-        const double nn = ka * ka + kb * kb;
+        const double nn = kf.a * kf.a + kf.b * kf.b;
         if (nn == 0.0)
             return false;
-        const double p0x = ka * kc / nn, p0y = kb * kc / nn, ux = -kb, uy = ka;
+        const HprLine line = hpr_line_of(kf, nn);
+        const double p0x = line.p0x, p0y = line.p0y, ux = line.ux, uy = line.uy;
         Frac lo = {-1e300, 1.0}, hi = {1e300, 1.0};
         bool bad = false;
-        auto add = [&](double ca, double cb, double cc) {
-            const double den = ca * ux + cb * uy, num = cc - (ca * p0x + cb * p0y);
+        auto add = [&](const Cons &m) {
+            double num, den;
+            if (!hpr_line_bound(m, line, num, den, bad))
+                return;
             if (den > 0.0) {
                 const Frac f = {num, den};
                 if (frac_less(f, hi))
                     hi = f;
-            } else if (den < 0.0) {
+            } else {
                 const Frac f = {-num, -den};
                 if (frac_less(lo, f))
                     lo = f;
-            } else if (num < 0.0) {
-                bad = true;
             }
         };
         if (lane < 4)      // the box |x| <= HPR_TAN, |y| <= HPR_TAN
-            add(lane == 0 ? 1.0 : (lane == 1 ? -1.0 : 0.0), lane == 2 ? 1.0 : (lane == 3 ? -1.0 : 0.0), HPR_TAN);
+            add(Cons{lane == 0 ? 1.0 : (lane == 1 ? -1.0 : 0.0), lane == 2 ? 1.0 : (lane == 3 ? -1.0 : 0.0), HPR_TAN, 1.0});
         for (int jpos = lane; jpos < upto; jpos += 64) {
             const int r = member(jpos);
             if (r >= n1 || r == self)
                 continue;
-            const Cons m = hpr_constraint(pts, r, fr);
-            add(m.a, m.b, m.c);
+            add(hpr_constraint(pts, r, fr));
         }
         // the wave's lo (max) and hi (min): every lane's pair as quotients (one division each -- the lanes' own lists were
         // compared as fractions, without one), then a min / max butterfly: DPP inside a row of 16 lanes (quad swaps, then the

@@ -1,8 +1,9 @@
 """CPU restatement of the reference's on-line synthesis -- TEST INFRASTRUCTURE ONLY.
 numpy fp32 arithmetic in the reference's op order + scipy.spatial.ConvexHull (the qhull the
-reference itself calls, utils/hidden_point_removal.py:4,32).  Random parts (occluder draws, the
-padding re-draws) are NOT restated: tests feed explicit occluders and check the padded rows by
-membership."""
+reference itself calls, utils/hidden_point_removal.py:4,32).  The random parts (occluder draws, the
+padding re-draws) are counter-based Philox on the GPU and have no counterpart in the reference's
+generator: they are restated in tests/synth_reference.py (spherical_occluder, gather), which builds
+on this file and on tests/pose_sampling_reference.py's Philox."""
 import math
 
 import numpy as np

@@ -124,7 +124,9 @@ def test_hull_vertices_random_clouds(hip):
     rng = np.random.default_rng(5)
     blob = rng.standard_normal((500, 3))
     sph = rng.standard_normal((300, 3)); sph /= np.linalg.norm(sph, axis=1, keepdims=True)
-    for pts in (blob, sph * 3 + [0, 0, 10]):
+    i = np.arange(5)                    # 5 x 5 x 5 integer lattice: 8 corners, 116 points exactly in a face, on an edge or inside
+    lattice = np.stack(np.meshgrid(i, i, i, indexing="ij"), -1).reshape(-1, 3) + [3, -2, 7]
+    for pts in (blob, sph * 3 + [0, 0, 10], lattice):
         P = np.concatenate([pts, np.zeros((1, 3))], 0).astype(np.float32)
         hull = ConvexHull(P.astype(np.float64))
         vis, num, ids = hpr.convexHull(torch.from_numpy(P[None]).cuda(), torch.from_numpy(P[None]).cuda(),
