@@ -168,6 +168,8 @@ _SIGNATURES = {
     "cloudaae_tsdf_count": [_I, _I, _I, _P, _I, _P, _P],
     "cloudaae_tsdf_emit": [_I, _I, _I, _D, _D, _D, _D, _P, _I, _P, _L, _P, _P, _P],
     "cloudaae_tsdf_raycast": [_I, _I, _I, _D, _D, _D, _D, _P, _I, _I, _I, _I, _P, _P, _D, _D, _P, _P],
+    "cloudaae_tsdf_align_step": [_I, _I, _I, _D, _D, _D, _D, _P, _I, _D, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P,
+                                 _P, _P, _P, _L, _P],
     "cloudaae_mesh_cluster_keys": [_I, _P, _D, _D, _D, _D, _I, _I, _I, _P, _P],
     "cloudaae_mesh_cluster_sums": [_I, _I, _P, _P, _I, _P, _P, _D, _D, _D, _D, _P, _L, _P, _P, _L, _P, _P, _P, _P],
     "cloudaae_mesh_cluster_place": [_I, _P, _P, _P, _D, _D, _D, _D, _D, _P, _P, _P, _P],
@@ -400,7 +402,8 @@ def lib():
                        ("cloudaae_component_labels_workspace_bytes", [_I, _I, _I]),
                        ("cloudaae_depth_creases_workspace_bytes", [_I, _I, _I]),
                        ("cloudaae_depth_align_step_workspace_bytes", [_I, _I, _I]),
-                       ("cloudaae_depth_contour_sums_workspace_bytes", [_I, _I, _I])):
+                       ("cloudaae_depth_contour_sums_workspace_bytes", [_I, _I, _I]),
+                       ("cloudaae_tsdf_align_step_workspace", [_I, _I, _I])):
             getattr(cdll, q).argtypes = sig
             getattr(cdll, q).restype = ctypes.c_longlong
         cdll.cloudaae_gemm_f32_splits.argtypes = [_I, _I, _I]

@@ -3,14 +3,18 @@ Each new frame is aligned against the volume fused so far -- the volume is rayca
 (cloudaae_tsdf_raycast; csrc/tsdf.hip), track.align_step solves a point-to-plane step between that window and the frame, that
 is repeated -- the result is judged by the windowed counts of "Detections" under the silhouette rule, and a frame that is not
 lost is summed into the volume at its pose (fuse.integrate).  Frame 0 defines the object's frame.  The definition is in
-DESIGN.md ("Scanning").
+DESIGN.md ("Scanning").  align='sdf' (experimental, opt-in) takes the steps on the volume's signed distance field instead:
+every observed pixel reads the field's value as its residual and its gradient as its normal (cloudaae_tsdf_align_step;
+csrc/tsdf_align.hip; DESIGN.md, "Scanning on the field"), with no raycast inside the iterations.
 
     s = scan_object(depth, intrinsics, 0.002)                       # Scan; s.poses [F,4,4], s.lost [F], s.volume
     vertices, triangles = s.mesh()                                  # what mesh_models.pack_meshes takes as a mesh
     d = raycast(volume, poses, intr_win, wh, ww)                    # [B,wh,ww]: the volume seen from B poses
+    s = scan_object(depth, intrinsics, 0.002, align='sdf')          # the steps on the field, no raycast inside them
+    pose, x, n, st = align_volume_step(volume, depth, intr_win, poses, frame_of, origin, wh, ww)    # one such step
 
     python -m cloudaae_amd.utils.scan --files REC_pcnn.tfrecord --target_cls C --voxel 0.002 --out model.ply [--every N]
-        [--motion velocity] [--simplify METRES]
+        [--motion velocity] [--simplify METRES] [--align sdf]
 """
 import argparse
 
@@ -20,7 +24,7 @@ import torch
 from .. import _lib
 from .._lib import ptr, require, stream
 from . import fuse, render, track
-from .frame_inputs import depth_frames, host, intrinsics_per_frame, on_device
+from .frame_inputs import check_int32, check_poses, depth_frames, host, intrinsics_per_frame, on_device
 from .pose_verify import tau_units
 
 # a choice, not a measurement
@@ -52,6 +56,48 @@ def raycast(volume, poses, intr_win, wh, ww, step=None, min_count=1, z_near=rend
     return out
 
 
+def align_volume_step(volume, depth, intr_win, poses, frame_of, origin, wh, ww, label=None, want=None, front=None, min_count=1):
+    """cloudaae_tsdf_align_step: one Gauss-Newton step of B poses on the volume's signed distance field.  volume a
+    fuse.Volume; depth [F,H,W]: an int16 tensor holding the uint16 bits, or uint16 (numpy is uploaded); intr_win [B,5] float32:
+    the windows' rows (fx, fy, cx - u0, cy - v0, factor_depth) and poses [B,4,4] float64, model -> camera, device tensors (or
+    numpy, uploaded); frame_of [B] int32 (an entry outside [0, F) gives status 4 and reads nothing) and origin [B,2] int32 =
+    (u0, v0), any values, device tensors; one wh, ww per call; label [F,H,W] uint8 with want [F] int32 on the device, or
+    neither, as fuse.integrate takes them; front in metres: what the field's 4096 stands for, the front the volume was
+    integrated with (default 4 voxels).  -> (pose_out [B,4,4] float64, x [B,6] float64, n_pairs [B] int32, status [B] int32)
+    on the device; status as track.align_step's.  No read-back."""
+    require(isinstance(volume, fuse.Volume), "volume must be a Volume")
+    dev = volume.device
+    dt = depth_frames(depth, dev)
+    require(dt.device == dev, "all inputs must be on the volume's device")
+    F, H, W = (int(v) for v in dt.shape)
+    pose = on_device(poses, torch.float64, dev)
+    require(pose.dim() == 3 and int(pose.shape[0]) >= 1, "poses must be [B, 4, 4], B >= 1")
+    B, wh, ww = int(pose.shape[0]), int(wh), int(ww)
+    pose = check_poses(pose, "poses", (3,), B, dev)
+    rows = on_device(intr_win, torch.float32, dev, (B, 5), "intr_win")
+    frame_of, origin = check_int32(frame_of, "frame_of", (B,), dev), check_int32(origin, "origin", (B, 2), dev)
+    require((label is None) == (want is None), "label and want come together")
+    if label is not None:
+        require(isinstance(label, torch.Tensor) and label.dtype == torch.uint8 and tuple(label.shape) == (F, H, W) and
+                label.device == dev, "label must be a uint8 [F, H, W] tensor on the volume's device")
+        label, want = label.contiguous(), check_int32(want, "want", (F,), dev)
+    front = fuse.FRONT_VOXELS * volume.voxel if front is None else float(front)
+    L = _lib.lib()
+    nbytes = int(L.cloudaae_tsdf_align_step_workspace(B, wh, ww))
+    require(nbytes > 0, "outside the limits: wh, ww >= 1, wh ww <= 2^24, B wh ww <= 2^28")
+    pose_out, x = _lib.empty((B, 4, 4), dtype=torch.float64, device=dev), _lib.empty((B, 6), dtype=torch.float64, device=dev)
+    n_pairs, status = _lib.empty((B,), dtype=torch.int32, device=dev), _lib.empty((B,), dtype=torch.int32, device=dev)
+    ws = _lib.empty((nbytes,), dtype=torch.uint8, device=dev)
+    nx, ny, nz = volume.dims
+    ox, oy, oz = volume.origin
+    with torch.cuda.device(dev):
+        _lib.check(L.cloudaae_tsdf_align_step(nx, ny, nz, ox, oy, oz, volume.voxel, ptr(volume.state), int(min_count), front, F, H, W,
+                                              ptr(dt), ptr(label), ptr(want), B, ptr(frame_of), ptr(origin), wh, ww, ptr(rows),
+                                              ptr(pose), ptr(n_pairs), ptr(x), ptr(status), ptr(pose_out), ptr(ws), nbytes,
+                                              stream()), "cloudaae_tsdf_align_step")
+    return pose_out, x, n_pairs, status
+
+
 # ---- the loop ---------------------------------------------------------------------------------------------------------------
 class Scan(object):
     """The result of scan_object.  poses [F,4,4] float64: the object's pose in every frame, model -> camera (a lost frame
@@ -75,7 +121,8 @@ def _first_pose(dt, lab, intr, want):
 
 def scan_object(depth, intrinsics, voxel, label=None, want=None, first_pose=None, aabb=None, grow=GROW, motion="constant",
                 iterations=track.ITERATIONS, gate=track.GATE, jump=track.JUMP, cos_min=track.COS_MIN, margin=track.MARGIN,
-                min_score=track.MIN_SCORE, tau=track.TAU, min_count=1, front=None, behind=None, step=None, on_frame=None, on_step=None):
+                min_score=track.MIN_SCORE, tau=track.TAU, min_count=1, front=None, behind=None, step=None, on_frame=None, on_step=None,
+                align="raycast"):
     """An unknown object followed through depth [F,H,W] uint16 (numpy, or a device tensor holding the bits as int16) with
     intrinsics [F,5] (or [5]) float32, and fused into a volume of `voxel` metres.  label [F,H,W] uint8 with want [F] (or one
     number) restricts the integration as in fuse.integrate and is handed to the counts.  Frame 0 defines the object's frame:
@@ -90,8 +137,13 @@ def scan_object(depth, intrinsics, voxel, label=None, want=None, first_pose=None
     a lost one is not, the pose stays at the last good one and the next frame starts from it at rest.  Nothing is read back
     inside the iterations; one read-back per frame.  step: the raycast's, metres (default 0.5 voxel).  Two hooks for tests and
     tools: on_step(f, dict(pose_in, depth_hyp, pose_out, n_pairs, status: device tensors; origin, wh, ww, rows, frame_of:
-    host)) after every step and on_frame(f, pose, volume) after every frame.  -> Scan."""
+    host)) after every step and on_frame(f, pose, volume) after every frame.
+    align='sdf' (experimental; DESIGN.md, "Scanning on the field"): the `iterations` steps of a frame are align_volume_step
+    calls in the window of the start pose, on the field of the volume fused so far, with the label filter of the integration
+    and its front; gate, jump and cos_min have no part in them and on_step's dict has no depth_hyp.  The raycast at the final
+    pose, the counts, the rule for `lost` and the integration are the same.  -> Scan."""
     require(motion in ("constant", "velocity"), "motion must be 'constant' or 'velocity'")
+    require(align in ("raycast", "sdf"), "align must be 'raycast' or 'sdf'")
     num_min, den_min = int(min_score[0]), int(min_score[1])
     require(0 <= num_min <= den_min and den_min >= 1, "min_score must be (num, den) with 0 <= num <= den, den >= 1")
     require(int(iterations) >= 0 and int(min_count) >= 1, "iterations must be >= 0 and min_count >= 1")
@@ -124,6 +176,20 @@ def scan_object(depth, intrinsics, voxel, label=None, want=None, first_pose=None
     def cast(pose, rows, wh, ww):
         return raycast(volume, pose, rows, wh, ww, step, min_count)
 
+    def field_attempt(f, start, tau_u):
+        """track.frame_attempt with the steps taken on the field: the window of the start (align_windows without a step),
+        `iterations` times align_volume_step, then track.score_attempt."""
+        a = track.align_windows(dev, dt, intr, np.full(1, f), aabb[None], start[None], cast, iterations=0, margin=margin)
+        dv = a["device"]
+        for _ in range(int(iterations)):
+            pose_in = a["poses"]
+            a["poses"], _, a["n_pairs"], a["status"] = align_volume_step(volume, dt, dv["rows"], pose_in, dv["frame_of"], dv["origin"],
+                                                                         a["wh"], a["ww"], lab, wnt, front, min_count)
+            if on_step is not None:
+                on_step(f, dict(pose_in=pose_in, pose_out=a["poses"], n_pairs=a["n_pairs"], status=a["status"], origin=a["origin"],
+                                wh=a["wh"], ww=a["ww"], rows=dv["rows"].cpu().numpy(), frame_of=int(f if a["ok"][0] else -1)))
+        return track.score_attempt(dev, dt, a, cast, tau_u, (num_min, den_min), lab, None if lab is None else wnt[f:f + 1])
+
     s = Scan()
     s.volume, s.min_count, s.aabb = volume, int(min_count), aabb
     s.poses = np.zeros((F, 4, 4))
@@ -137,10 +203,13 @@ def scan_object(depth, intrinsics, voxel, label=None, want=None, first_pose=None
     for f in range(1, F):
         start = track.predict(last, before, motion)
         tau_u = tau_units(np.array([tau], np.float64), intr[f:f + 1, 4].astype(np.float64))[0]
-        pose, num, den, n_pairs, status, lost, pose_dev = track.frame_attempt(
-            dev, dt, intr, f, aabb[None], start[None], cast, tau_u, (num_min, den_min), lab, None if lab is None else wnt[f:f + 1],
-            iterations=iterations, gate=gate, jump=jump, cos_min=cos_min, margin=margin,
-            on_step=None if on_step is None else lambda info: on_step(f, dict(info, frame_of=int(info["frame_of"][0]))))
+        if align == "sdf":
+            pose, num, den, n_pairs, status, lost, pose_dev = field_attempt(f, start, tau_u)
+        else:
+            pose, num, den, n_pairs, status, lost, pose_dev = track.frame_attempt(
+                dev, dt, intr, f, aabb[None], start[None], cast, tau_u, (num_min, den_min), lab, None if lab is None else wnt[f:f + 1],
+                iterations=iterations, gate=gate, jump=jump, cos_min=cos_min, margin=margin,
+                on_step=None if on_step is None else lambda info: on_step(f, dict(info, frame_of=int(info["frame_of"][0]))))
         if lost[0]:
             before = None
         else:
@@ -162,6 +231,8 @@ def main(argv=None):
     parser.add_argument("--every", type=int, default=1, help="take every N-th frame")
     parser.add_argument("--motion", choices=["constant", "velocity"], default="constant")
     parser.add_argument("--simplify", type=float, default=None, metavar="METRES", help="simplify the mesh on cells of this side")
+    parser.add_argument("--align", choices=["raycast", "sdf"], default="raycast",
+                        help="sdf: align on the volume's signed distance field (experimental)")
     parser.add_argument("--gpu", type=int, default=0)
     args = parser.parse_args(argv)
     from . import mesh_models
@@ -170,7 +241,7 @@ def main(argv=None):
     depth, label, intr, truth, frames = fuse.class_frames(args.files, c, args.every)
     # only the first pose is used; the others are what the printed errors are measured against
     s = scan_object(depth, intr, args.voxel, label=label, want=np.full(len(frames), c + 1, np.int32), first_pose=truth[0],
-                    motion=args.motion)
+                    motion=args.motion, align=args.align)
     vertices, triangles = s.mesh(args.simplify)
     mesh_models.write_ply(args.out, vertices, triangles)
     for f, fr in enumerate(frames):

@@ -346,8 +346,14 @@ def frame_attempt(dev, dt, intr_host, f, aabb, start, hypothesis, tau_u, min_sco
     counters, the last step's pairs and status -- and the silhouette rule: (num, den) = (consistent, consistent + in_front +
     behind), 0 / 1 for den = 0; lost when num min_den < min_num den in integers, min_score = (min_num, min_den), or without
     a window.  -> (pose [n,4,4], num, den, n_pairs, status, lost [n] on the host, the poses on the device)."""
-    n = len(start)
-    a = align_windows(dev, dt, intr_host, np.full(n, f), aabb, start, hypothesis, **align)
+    a = align_windows(dev, dt, intr_host, np.full(len(start), f), aabb, start, hypothesis, **align)
+    return score_attempt(dev, dt, a, hypothesis, tau_u, min_score, label, want)
+
+
+def score_attempt(dev, dt, a, hypothesis, tau_u, min_score, label=None, want=None):
+    """The second half of frame_attempt, for a loop that takes its steps otherwise (scan.scan_object with align='sdf'): a is
+    what align_windows returned, with poses, n_pairs and status those of the steps taken.  -> what frame_attempt returns."""
+    n = int(a["poses"].shape[0])
     dv = a["device"]
     d = hypothesis(a["poses"], dv["rows"], a["wh"], a["ww"])
     tau_dev = torch.full((n,), int(tau_u), dtype=torch.int32, device=dev)

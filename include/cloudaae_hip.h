@@ -60,7 +60,7 @@ typedef void *cloudaae_stream_t; /* hipStream_t */
  * cloudaae_depth_align_step with its workspace query; cloudaae_depth_edge_nearest, cloudaae_depth_contour_sums with its
  * workspace query and cloudaae_depth_align_solve; cloudaae_tsdf_integrate, cloudaae_tsdf_count and cloudaae_tsdf_emit;
  * cloudaae_tsdf_raycast; cloudaae_farthest_point_sample_variant, cloudaae_knn_variant and cloudaae_nn_distance_variant
- * (host-only queries: which kernel a call takes). */
+ * (host-only queries: which kernel a call takes); cloudaae_tsdf_align_step with its workspace query. */
 #define CLOUDAAE_ABI_VERSION 602
 int cloudaae_version(void);
 const char *cloudaae_last_error(void);
@@ -1580,6 +1580,40 @@ int cloudaae_tsdf_emit(int nx, int ny, int nz, double ox, double oy, double oz, 
 int cloudaae_tsdf_raycast(int nx, int ny, int nz, double ox, double oy, double oz, double voxel, const int *state, int min_count,
                           int B, int wh, int ww, const float *intr_win, const double *poses, double step, double z_near,
                           uint16_t *depth_out, cloudaae_stream_t stream);
+
+/* One Gauss-Newton step that aligns depth frames on the volume's signed distance field ("Scanning on the field"):
+ * no raycast, no second normal map.  The volume, state and min_count as above; front > 0, metres: what a field value of 4096
+ * stands for (the front of the integration that made the state).  depth [f,h,w] uint16, label [f,h,w] uint8 and want [f] int
+ * (both or neither) as in cloudaae_tsdf_integrate.  b samples: frame_of [b] int, origin [b,2] int = (u0, v0), any values, one
+ * window size wh x ww, intr_win [b,5] float = (fx, fy, cx - u0, cy - v0, factor_depth) and pose_in [b,16] double (row-major 4 x
+ * 4, model -> camera, R and t) as in cloudaae_depth_align_step.  float64 on exactly widened values, un-fused, in the order
+ * written; comparisons in float64 before any conversion.  Window pixel (x, y) of sample s with fr = frame_of[s]: d = the depth
+ * of frame fr at (u0 + x, v0 + y), 0 outside the frame; no row when d = 0, or when label and want are given, want[fr] != 0 and
+ * the label at that pixel differs.  p = P(x, y, d) of cloudaae_depth_align_step; e = p - t; q_a = (R0a e0 + R1a e1) + R2a e2;
+ * g_a = (q_a - origin_a) / voxel - 0.5; no row unless 0 <= g_a <= n_a - 1 on every axis (a NaN fails).  The cell i_a =
+ * clamp(floor g_a, 0, n_a - 2), f_a = g_a - i_a and its eight corner values v0..v7 are cloudaae_tsdf_raycast's; no row when a
+ * corner is unknown.  c00 = v0 + (v1 - v0) f_x, c10 on (2,3), c01 on (4,5), c11 on (6,7); c0 = c00 + (c10 - c00) f_y, c1 = c01
+ * + (c11 - c01) f_y; val = c0 + (c1 - c0) f_z.  The gradient by (f_x, f_y, f_z): with d00 = v1 - v0, d10 = v3 - v2, d01 = v5 -
+ * v4, d11 = v7 - v6: gx0 = d00 + (d10 - d00) f_y, gx1 = d01 + (d11 - d01) f_y, G_x = gx0 + (gx1 - gx0) f_z; e0 = c10 - c00, e1 =
+ * c11 - c01, G_y = e0 + (e1 - e0) f_z; G_z = c1 - c0.  No row when val >= 4096 or (G_x G_x + G_y G_y) + G_z G_z is 0 or not
+ * finite.  r = (val / 4096) front; o = G ((front / 4096) / voxel); n_i = (Ri0 o_0 + Ri1 o_1) + Ri2 o_2; a = p x n formed as in
+ * cloudaae_depth_align_step; J = (-a, -n).  The sums, A x = -b by LDL^T, U and pose_out = U pose_in are
+ * cloudaae_depth_align_step's.
+ * Outputs, all written: n_pairs [b] int: the rows; x [b,6] double (zeros unless status is 0); status [b] int: 0 updated, 1
+ * fewer than six rows, 2 a pivot that is not a finite number > 0, 3 a solution that is not finite, 4 frame_of outside [0, f)
+ * (nothing of that sample is read; n_pairs is 0); pose_out [b,16] double, for every status but 0 pose_in bit for bit.
+ * Two launches, runs of 2048 window pixels, as cloudaae_depth_align_step: no floating-point atomics and no workgroup waits
+ * for another, the same bits run to run and whatever else is in the batch.  workspace:
+ * cloudaae_tsdf_align_step_workspace(b, wh, ww) bytes, 8-byte aligned (0: outside the limits).  Limits: the volume's;
+ * min_count >= 1; front finite and > 0; f, h, w, b, wh, ww >= 1; h * w <= 2^24; wh * ww <= 2^24; b * wh * ww <= 2^28; outside
+ * them, with a null required pointer, a state that is not 16-byte aligned or a workspace too small the call returns an error,
+ * launches nothing and leaves its outputs untouched. */
+long long cloudaae_tsdf_align_step_workspace(int b, int wh, int ww);
+int cloudaae_tsdf_align_step(int nx, int ny, int nz, double ox, double oy, double oz, double voxel, const int *state, int min_count,
+                             double front, int f, int h, int w, const uint16_t *depth, const uint8_t *label, const int *want,
+                             int b, const int *frame_of, const int *origin, int wh, int ww, const float *intr_win,
+                             const double *pose_in, int *n_pairs, double *x, int *status, double *pose_out, void *workspace,
+                             long long workspace_size, cloudaae_stream_t stream);
 
 /* ---- simplified meshes: uniform vertex clustering with quadric-error placement ("Simplified meshes") ---- */
 

@@ -5,12 +5,14 @@ of the size track.pose_windows gives).  Device events around every iteration; wa
 the versions alternate.  The two routes' images are compared before anything is timed: they cut the same field in two ways,
 so the pixels set in both and the ones more than a voxel apart along the ray are counted, not asserted.
 
-    python tools/bench_scan.py [--n 128] [--frames 16] [--window 200] [--iters 20] [--warmup 3] [--out FILE.json]
+    python tools/bench_scan.py [--n 128] [--frames 16] [--window 200] [--iters 20] [--warmup 3] [--align raycast|sdf] [--out FILE.json]
 
 Prints one JSON line.  The kernel's three other forms (a wave as 64 pixels of a row; the cell's values reloaded at every
 sample) are timed beside the product's through the development knobs CLOUDAAE_RAYCAST_ROWS and CLOUDAAE_RAYCAST_RELOAD, their
 images compared for equality first.  samples: the samples the rays take, estimated in torch from the slab interval and the
-image (a ray that hits stops at its hit, any other runs to the interval's end)."""
+image (a ray that hits stops at its hit, any other runs to the interval's end).  --align chooses how the scan_object frame
+aligns ("Scanning on the field"); either way one step of each method is timed in the loop's own window: the raycast
+plus track.align_step against scan.align_volume_step."""
 import argparse
 import json
 import os
@@ -59,6 +61,7 @@ def main(argv=None):
     parser.add_argument("--width", type=int, default=640)
     parser.add_argument("--iters", type=int, default=20)
     parser.add_argument("--warmup", type=int, default=3)
+    parser.add_argument("--align", choices=["raycast", "sdf"], default="raycast", help="how the scan_object frame aligns")
     parser.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = parser.parse_args(argv)
     if not torch.cuda.is_available():
@@ -136,7 +139,7 @@ def main(argv=None):
     result = None
     for _ in range(2):                                                   # the first run warms up
         del stamps[:]
-        result = scan.scan_object(frames, intr, s, first_pose=orbit[0], aabb=aabb, on_frame=on_frame)
+        result = scan.scan_object(frames, intr, s, first_pose=orbit[0], aabb=aabb, on_frame=on_frame, align=args.align)
     per_frame = np.diff(np.array(stamps)) * 1e3
     err = np.abs(result.poses - orbit).reshape(F, -1).max(axis=1)
 
@@ -161,6 +164,21 @@ def main(argv=None):
     t_loop = timed([loop_raycast, loop_mesh, loop_rasterise], args.iters, args.warmup)
     l_rays, l_samples = sample_count(lvol, lpose, lrow, lh, lw, scan.STEP_VOXELS * s, loop_raycast(), render.Z_NEAR)
 
+    # ---- one alignment step of either method in that window, against the last frame -----------------------------------------
+    def ints(values):
+        return torch.tensor(values, dtype=torch.int32, device=dev)
+    lframe, lorigin = ints([F - 1]), ints(o2.tolist())
+    gate, jump = ints([int(round(track.GATE * 10000.0))]), ints([int(round(track.JUMP * 10000.0))])
+
+    def step_raycast():
+        return track.align_step(frames, lframe, lorigin, loop_raycast(), lrow, gate, jump, track.COS_MIN, lpose)["pose_out"]
+
+    def step_field():
+        return scan.align_volume_step(lvol, frames, lrow, lpose, lframe, lorigin, lh, lw)[0]
+    t_step = timed([step_raycast, step_field], args.iters, args.warmup)
+    step_pairs = [int(track.align_step(frames, lframe, lorigin, loop_raycast(), lrow, gate, jump, track.COS_MIN, lpose)["n_pairs"][0]),
+                  int(scan.align_volume_step(lvol, frames, lrow, lpose, lframe, lorigin, lh, lw)[2][0])]
+
     med = t_routes[0]['median'] * 1e-3
     out = dict(voxels=[n, n, n], window=[B, win, win], mesh_triangles=int(packed.num_triangles[0]), pixels_either=int(either.sum()),
                pixels_both=int(both.sum()), pixels_more_than_a_voxel_apart=int(apart.sum()), largest_difference_units=int(np.abs(a - b)[both].max()),
@@ -170,7 +188,9 @@ def main(argv=None):
                scan_frame_ms=dict(min=float(per_frame.min()), median=float(np.median(per_frame)), max=float(per_frame.max())),
                loop_window=[1, lh, lw], loop_live_rays=l_rays, loop_samples=l_samples, loop_mesh_triangles=int(lpacked.num_triangles[0]),
                loop_raycast_ms=t_loop[0], loop_mesh_route_ms=t_loop[1], loop_rasterise_only_ms=t_loop[2],
-               scan_pose_error_last=float(err[-1]), scan_pose_error_max=float(err.max()), iters=args.iters, warmup=args.warmup)
+               scan_pose_error_last=float(err[-1]), scan_pose_error_max=float(err.max()), align=args.align,
+               step_raycast_ms=t_step[0], step_field_ms=t_step[1], step_rows=dict(raycast=step_pairs[0], field=step_pairs[1]),
+               iters=args.iters, warmup=args.warmup)
     line = json.dumps(out)
     print(line)
     if args.out:
