@@ -5,6 +5,7 @@ shared object is missing, or a tensor is not on the GPU, the call fails loudly.
 """
 import ctypes
 import os
+import re
 import subprocess
 
 import torch
@@ -13,204 +14,116 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CLOUDAAE_HIP_LIB", os.path.join(_HERE, "libcloudaae_hip.so"))   # env: kernel A/B builds
 CSRC = os.path.join(_HERE, "csrc")
 
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "cloudaae_hip.h")   # the one csrc/Makefile compiles against
+
 _lib = None
-
-_P, _I, _L, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
-_D = ctypes.c_double
-_U = ctypes.c_ulonglong
-# argument types of every entry point of include/cloudaae_hip.h (stream last)
-_SIGNATURES = {
-    "cloudaae_nn_distance": [_I, _I, _P, _I, _P, _P, _P, _P, _P, _P],
-    "cloudaae_nn_distance_prefix": [_I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
-    "cloudaae_nn_distance_grad": [_I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
-    "cloudaae_nn_distance_grad_ordered": [_I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P],
-    "cloudaae_farthest_point_sample": [_I, _I, _I, _P, _P, _P, _P],
-    "cloudaae_gather_point": [_I, _I, _I, _P, _P, _P, _P],
-    "cloudaae_gather_point_grad": [_I, _I, _I, _P, _P, _P, _P],
-    "cloudaae_prob_sample": [_I, _I, _I, _P, _P, _P, _P, _P],
-    "cloudaae_knn": [_I, _I, _I, _I, _I, _P, _P, _P],
-    "cloudaae_knn_hinted": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    "cloudaae_selftest_div_by": [_F, _I, _P, _P],
-    "cloudaae_gemm_f32": [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P],
-    "cloudaae_gemm_bf16": [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P],
-    "cloudaae_gemm_f32_ordered": [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _L, _P],
-    "cloudaae_gemm_bf16_ordered": [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _L, _P],
-    "cloudaae_gemm_f32_ordered_fold": [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _L, _P],
-    "cloudaae_gemm_f32_tn_group": [_I, _P, _P],
-    "cloudaae_dev_gemm_folded": [_I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _P],
-    "cloudaae_bn_forward": [_I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P,
-                            _P, _P, _P],
-    "cloudaae_bn_backward": [_I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I,
-                             _P, _P, _P, _I, _P, _P, _P],
-    "cloudaae_colsum_f32": [_I, _I, _P, _I, _P, _I, _P, _P],
-    # SyncBN variants: the plain argument lists + (colstats, parts for the forward) + cloudaae_bn_sync* + stream(s)
-    "cloudaae_bn_forward_sync": [_I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P,
-                                 _P, _P, _I, _P, _P],
-    "cloudaae_bn_backward_sync": [_I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P, _I,
-                                  _P, _P, _P, _I, _P, _P, _P, _P],
-    "cloudaae_edgeconv_forward_sync": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P,
-                                       _P, _P, _P, _I, _P, _P, _I, _P, _P, _P],
-    "cloudaae_edgeconv_backward_sync": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P,
-                                        _P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P,
-                                        _P, _P],
-    "cloudaae_gemm_f32_colstats": [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P],
-    "cloudaae_gemm_bf16_colstats": [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P],
-    "cloudaae_gemm_b16": [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _I, _P, _P],
-    "cloudaae_to_bf16": [ctypes.c_longlong, _P, _P, _P],
-    "cloudaae_gemm_bf16x3": [_I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P],
-    "cloudaae_x3_split": [_I, _I, _P, _I, _I, _P, _P],
-    "cloudaae_x3_split_weight": [_I, _I, _P, _I, _P, _P, _P],
-    "cloudaae_gemm_bf16x3p": [_I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P],
-    "cloudaae_bn_backward_dx_bf16x3": [_I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P,
-                                       _I, _P, _P, _I, _P],
-    "cloudaae_bn_meanpool_forward16": [_I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P],
-    "cloudaae_bn_meanpool_backward16": [_I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P],
-    "cloudaae_bn_forward_colstats": [_I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P,
-                                     _P, _P, _I, _P],
-    "cloudaae_fc_forward": [_I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P],
-    "cloudaae_fc_backward": [_I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P,
-                             _P, _I, _P],
-    "cloudaae_stream_wait": [_P, _P],
-    "cloudaae_fc_forward_group": [_I, _I, _P, _I, _P, _P],
-    "cloudaae_fc_backward_group": [_I, _I, _P, _I, _P],
-    "cloudaae_edgeconv_forward": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P,
-                                  _P, _P, _P, _I, _P, _P, _I, _P, _P],
-    "cloudaae_edgeconv_forward_b16out": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P,
-                                         _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _P],
-    "cloudaae_edgeconv_backward": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P,
-                                   _P, _I, _P, _P, _I, _P, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P],
-    "cloudaae_edgeconv_revlists": [_I, _I, _I, _I, _P, _P, _P],
-    "cloudaae_input_assemble": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    "cloudaae_input_assemble_noise": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _F, _U, _P, _P],
-    "cloudaae_zero_buffers": [_I, _P, _P, _P],
-    "cloudaae_loss_tail": [_L, _P, _P, _P, _P, _I, _P, _P, _P, _P, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                           _P, _P, _P],
-    "cloudaae_add_rowvec": [_I, _I, _I, _P, _P, _P, _P],
-    "cloudaae_add_f32": [_L, _P, _P, _P, _P],
-    "cloudaae_fill_scaled": [_L, _P, _F, _P, _P, _P],
-    "cloudaae_mul_add_f32": [_L, _P, _P, _P, _P, _P],
-    "cloudaae_edge_feature": [_I, _I, _I, _I, _I, _P, _I, _P, _P, _P],
-    "cloudaae_edge_feature_grad": [_I, _I, _I, _I, _I, _P, _P, _P, _P],
-    "cloudaae_pool_rows": [_I, _I, _I, _I, _P, _P, _P, _P],
-    "cloudaae_pool_rows_grad": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "cloudaae_mean_f32": [_L, _P, _P, _P, _P],
-    "cloudaae_add_mean_f32": [_L, _P, _P, _P, _P, _P, _P],
-    "cloudaae_nn_distance_grad_uniform": [_I, _I, _P, _I, _P, _P, _F, _P, _P, _P, _P, _I, _P],
-    "cloudaae_trans_error": [_I, _P, _P, _P, _P],
-    "cloudaae_trans_error_grad": [_I, _P, _P, _P, _P, _P, _P],
-    "cloudaae_rotation_error": [_I, _P, _P, _P, _P, _P, _P],
-    "cloudaae_rotation_error_grad": [_I, _P, _P, _P, _P],
-    "cloudaae_exponential_map": [_I, _P, _P, _P],
-    "cloudaae_pose_losses": [_I, _P, _P, _P, _P, _P, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P],
-    "cloudaae_pose_losses_grad": [_I, _P, _P, _P, _P, _P, _F, _F, _F, _P, _P, _P, _P],
-    "cloudaae_loss_mix": [_P, _P, _P, _F, _F, _F, _P, _P],
-    "cloudaae_loss_mix_grad": [_P, _F, _F, _F, _P, _P, _P, _P],
-    "cloudaae_adam_tf": [_L, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _F, _I, _P],
-    "cloudaae_adam_tf_step": [_L, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _F, _P, _F, _F, _F, _F, _F, _F, _P, _P, _P],
-    "cloudaae_sgd": [_L, _P, _P, _F, _F, _P],
-    "cloudaae_bn_decay_schedule": [_P, _F, _F, _F, _F, _F, _P, _P],
-    "cloudaae_increment": [_P, _F, _P],
-    "cloudaae_transform_object_model": [_I, _I, _I, _P, _P, _P, _P, _P, _P],
-    "cloudaae_random_spherical_occluder": [_I, _I, _P, _F, _F, _F, _F, _U, _P, _P],
-    "cloudaae_sample_poses": [_I, _U, _U, _I, _P, _I, _F, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P,
-                              _P, _P],
-    "cloudaae_random_object_occluder": [_I, _U, _U, _I, _I, _P, _I, _P, _P, _P, _I, _F, _F, _F, _P, _P, _P, _P],
-    "cloudaae_spherical_flip": [_I, _I, _P, _I, _P, _P, _F, _P, _P, _P],
-    "cloudaae_hidden_point_removal": [_I, _I, _P, _P, _U, _P, _P, _P, _P, _P],
-    "cloudaae_hidden_point_removal_rows": [_I, _I, _P, _P, _U, _I, _P, _P, _P, _P, _P, _P],
-    "cloudaae_icp_point_to_point": [_I, _I, _P, _I, _L, _I, _P, _I, _L, _P, _P, _D, _D, _I, _I, _D, _D, _P, _P, _P,
-                                    _P, _P, _P, _P],
-    "cloudaae_icp_point_to_plane": [_I, _I, _P, _I, _L, _I, _P, _I, _L, _P, _I, _P, _P, _D, _D, _I, _I, _D, _D, _P, _P,
-                                    _P, _P, _P, _P, _P],
-    "cloudaae_estimate_normals": [_I, _P, _P, _I, _L, _I, _P, _I, _L, _F, _I, _P, _P, _P, _P, _P, _L, _P],
-    "cloudaae_f64_to_f32": [_L, _P, _P, _P],
-    "cloudaae_pose_score": [_I, _I, _I, _P, _I, _L, _P, _P, _P, _P, _P, _P, _P],
-    "cloudaae_pose_matrix": [_I, _P, _I, _P, _P, _P],
-    "cloudaae_pose_stack": [_I, _P, _P, _P, _P],
-    "cloudaae_cloud_diameter": [_I, _I, _P, _I, _L, _P, _P, _P],
-    "cloudaae_frame_segments": [_I, _I, _I, _P, _P, _P, _I, _P, _P, _F, _P, _P, _P, _P, _L, _P],
-    "cloudaae_radius_outlier": [_I, _P, _P, _L, _I, _F, _I, _P, _P, _P, _P, _P, _L, _P],
-    "cloudaae_ragged_fps": [_I, _P, _P, _L, _I, _P, _P, _P, _P, _L, _P],
-    "cloudaae_mesh_weights": [_I, _P, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _L, _P],
-    "cloudaae_mesh_sample": [_I, _P, _P, _L, _L, _P, _P, _P, _P, _P, _I, _U, _U, _P, _P, _P, _P],
-    "cloudaae_mesh_gather_rows": [_I, _I, _P, _L, _P, _L, _I, _I, _P, _L, _P],
-    "cloudaae_render_frames": [_I, _P, _P, _L, _L, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _L, _L, _D, _P, _P, _P,
-                               _P, _P, _P, _L, _P],
-    "cloudaae_vsd_counts": [_I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _D, _I, _P, _P, _P, _P, _P, _P],
-    "cloudaae_pose_max_dist": [_I, _I, _I, _P, _I, _L, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
-    "cloudaae_depth_normals": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
-    "cloudaae_depth_sensor_noise": [_I, _I, _I, _P, _P, _P, _U, _U, _D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P, _P],
-    "cloudaae_frame_clouds": [_I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _U, _P, _P, _P, _P, _P, _L, _P],
-    "cloudaae_rendered_scene": [_I, _U, _U, _I, _I, _P, _P, _P, _P, _P, _F, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P,
-                                _P],
-    "cloudaae_transform_hausdorff": [_I, _I, _P, _I, _I, _P, _I, _P, _D, _P, _P, _P],
-    "cloudaae_nearest_equivalent_pose": [_I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
-    "cloudaae_pose_compose": [_I, _P, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P],
-    "cloudaae_depth_fit_counts": [_I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
-    "cloudaae_select_pose": [_I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
-    "cloudaae_ppf_model_pairs": [_I, _P, _P, _I, _L, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
-    "cloudaae_ppf_vote": [_I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _L, _P, _P,
-                          _P, _P, _P, _P, _P, _P],
-    "cloudaae_ppf_cluster": [_I, _I, _P, _P, _P, _I, _P, _D, _I, _P, _P, _P, _P, _P, _P],
-    "cloudaae_depth_plane": [_I, _I, _I, _P, _P, _U, _L, _I, _I, _D, _I, _P, _P, _P, _P, _P],
-    "cloudaae_depth_foreground": [_I, _I, _I, _P, _P, _P, _P, _D, _D, _P, _P],
-    "cloudaae_depth_components": [_I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P],
-    "cloudaae_component_labels": [_I, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P],
-    "cloudaae_depth_creases": [_I, _I, _I, _P, _P, _P, _P, _I, _I, _D, _P, _P, _P, _P, _P, _L, _P],
-    "cloudaae_depth_fit_counts_window": [_I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P],
-    "cloudaae_detect_assign": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
-                               _P, _P, _P, _P, _P],
-    "cloudaae_depth_align_step": [_I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P, _P, _P, _L, _P],
-    "cloudaae_depth_edge_nearest": [_I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _I, _P, _P],
-    "cloudaae_depth_contour_sums": [_I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P],
-    "cloudaae_depth_align_solve": [_I, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P],
-    "cloudaae_tsdf_integrate": [_I, _I, _I, _D, _D, _D, _D, _P, _I, _I, _I, _P, _P, _P, _P, _P, _D, _D, _D, _P],
-    "cloudaae_tsdf_count": [_I, _I, _I, _P, _I, _P, _P],
-    "cloudaae_tsdf_emit": [_I, _I, _I, _D, _D, _D, _D, _P, _I, _P, _L, _P, _P, _P],
-    "cloudaae_tsdf_raycast": [_I, _I, _I, _D, _D, _D, _D, _P, _I, _I, _I, _I, _P, _P, _D, _D, _P, _P],
-    "cloudaae_tsdf_align_step": [_I, _I, _I, _D, _D, _D, _D, _P, _I, _D, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P,
-                                 _P, _P, _P, _L, _P],
-    "cloudaae_mesh_cluster_keys": [_I, _P, _D, _D, _D, _D, _I, _I, _I, _P, _P],
-    "cloudaae_mesh_cluster_sums": [_I, _I, _P, _P, _I, _P, _P, _D, _D, _D, _D, _P, _L, _P, _P, _L, _P, _P, _P, _P],
-    "cloudaae_mesh_cluster_place": [_I, _P, _P, _P, _D, _D, _D, _D, _D, _P, _P, _P, _P],
-    "cloudaae_mesh_cluster_triangles": [_I, _I, _P, _P, _I, _P, _P],
-}
-
-
-class GemmTnJob(ctypes.Structure):
-    """struct cloudaae_gemm_tn_job (include/cloudaae_hip.h): one product of a grouped weight-gradient launch."""
-    _fields_ = [("M", _I), ("N", _I), ("K", _I), ("A", _P), ("lda", _I), ("B", _P), ("ldb", _I), ("C", _P), ("ldc", _I),
-                ("fold_c", _I), ("zeroed", _I)]
-
-
-class FcLayer(ctypes.Structure):
-    """struct cloudaae_fc_layer (include/cloudaae_hip.h): one layer of a grouped fully connected launch."""
-    _fields_ = [("K", _I), ("N", _I), ("x", _P), ("ldx", _I), ("w", _P), ("bias", _P), ("gamma", _P), ("beta", _P),
-                ("ema_mean", _P), ("ema_var", _P), ("save_mean", _P), ("save_var", _P), ("relu", _I), ("y", _P),
-                ("out", _P), ("tickets", _P), ("dout", _P), ("lddo", _I), ("dx", _P), ("lddx", _I), ("dw", _P),
-                ("accumulate_dw", _I), ("dgamma", _P), ("dbeta", _P), ("dbias", _P), ("accumulate_param_grads", _I),
-                ("partials", _P), ("partials_floats", _L), ("out_rowvec", _P), ("out_rowvec_d", _I)]
-
-
-# int (*cloudaae_allreduce_fn)(void *ctx, double *buf, int count, cloudaae_stream_t stream)
-ALLREDUCE_FN = ctypes.CFUNCTYPE(_I, _P, _P, _I, _P)
-
-
-class BnSyncStruct(ctypes.Structure):
-    """struct cloudaae_bn_sync (include/cloudaae_hip.h): the host's all-reduce for batch-norm sums."""
-    _fields_ = [("allreduce", ALLREDUCE_FN), ("ctx", _P), ("world", _I), ("buf", _P)]
-
-
-_LONGLONG_RESULTS = ["cloudaae_x3_planes_bytes", "cloudaae_bn_backward_dx_bf16x3_consts_bytes", "cloudaae_loss_tail_workspace_bytes", "cloudaae_bn_workspace_bytes", "cloudaae_edgeconv_workspace_bytes",
-                     "cloudaae_mean_workspace_bytes", "cloudaae_gemm_f32_ordered_workspace",
-                     "cloudaae_gemm_bf16_ordered_workspace"]
-
-
-ABI_VERSION = 602     # CLOUDAAE_ABI_VERSION of include/cloudaae_hip.h (tests/test_capi_symbols.py compares the two)
 
 
 class HipLibraryError(RuntimeError):
     pass
+
+
+# ---- the C ABI, read from the header: argument types, struct layouts and the revision are stated there only ----
+
+# int (*cloudaae_allreduce_fn)(void *ctx, double *buf, int count, cloudaae_stream_t stream): the header's one
+# function-pointer typedef, the one type the reader takes from here
+ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p)
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong,
+            "unsigned": ctypes.c_uint, "unsigned long long": ctypes.c_ulonglong}
+
+
+def _ctype(ctype, pointees, where):
+    """The ctypes type of a C type as the header spells it ('const float *', 'long long', 'cloudaae_stream_t').
+    Every pointer is a c_void_p (callers pass data_ptr() integers, None and ctypes arrays), const char * a c_char_p."""
+    words = [w for w in ctype.replace("*", " * ").split() if w != "const"]
+    base = " ".join(w for w in words if w != "*")
+    if words.count("*") == 1 and base == "char" and "const" in ctype.split():
+        return ctypes.c_char_p
+    if ("*" in words and base in pointees) or base == "cloudaae_stream_t":
+        return ctypes.c_void_p
+    if "*" not in words and base in _SCALARS:
+        return _SCALARS[base]
+    if "*" not in words and base == "cloudaae_allreduce_fn":
+        return ALLREDUCE_FN
+    raise HipLibraryError("%s: no ctypes type for '%s'" % (where, " ".join(ctype.split())))
+
+
+def _parts(pattern, text, where):
+    m = re.fullmatch(pattern, text.strip(), flags=re.S)
+    if m is None:
+        raise HipLibraryError("%s: cannot read '%s'" % (where, " ".join(text.split())))
+    return m.groups()
+
+
+def read_header(text):
+    """What the text of include/cloudaae_hip.h declares: (ABI revision, {struct: [(field, ctype)]},
+    {function: (restype, [argtypes])}, the names of the functions that take a cloudaae_stream_t).  It knows the forms
+    that header uses -- `typedef struct NAME { fields } NAME;`, `ret cloudaae_name(args);` -- and is no C parser:
+    whatever else mentions a cloudaae_ function, and every type it has no ctypes type for, raises."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    abi = re.search(r"^#define\s+CLOUDAAE_ABI_VERSION\s+(\d+)\s*$", text, flags=re.M)
+    if abi is None:
+        raise HipLibraryError("the header does not define CLOUDAAE_ABI_VERSION")
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    structs, prototypes, launching = {}, {}, set()
+    pointees = set(_SCALARS) | {"void", "unsigned char", "uint8_t", "uint16_t"}      # (+ the structs, as they are read)
+
+    def struct(m):
+        where, fields = "struct " + m.group(1), []
+        for decl in filter(None, (d.strip() for d in m.group(2).split(";"))):       # `const float *w, *bias`
+            first, *more = decl.split(",")
+            base, stars, name = _parts(r"(.*?)([\s*]*)(\w+)", first, where)
+            for stars, name in [(stars, name)] + [_parts(r"([\s*]*)(\w+)", d, where) for d in more]:
+                fields.append((name, _ctype(base + stars, pointees, "%s, field %s" % (where, name))))
+        structs[m.group(1)] = fields
+        pointees.add(m.group(1))
+        return ""
+
+    def arguments(params, where):
+        params = [] if params.strip() == "void" else [" ".join(p.split()) for p in params.split(",")]
+        return [_ctype(_parts(r"(.*?)\w+", p, where)[0], pointees, "%s(%s)" % (where, p)) for p in params]
+
+    def callback(m):
+        if tuple(arguments(m.group(1), "cloudaae_allreduce_fn")) != ALLREDUCE_FN._argtypes_:
+            raise HipLibraryError("cloudaae_allreduce_fn no longer takes what ALLREDUCE_FN (cloudaae_amd/_lib.py) states")
+        return ""
+
+    def prototype(m):
+        ret, name, params = m.groups()
+        prototypes[name] = (_ctype(ret, (), "result of " + name), arguments(params, name))
+        if re.search(r"\bcloudaae_stream_t\b", params):
+            launching.add(name)
+        return ""
+
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;", struct, text, flags=re.S)
+    text = re.sub(r"typedef\s+int\s*\(\s*\*\s*cloudaae_allreduce_fn\s*\)\s*\(([^()]*)\)\s*;", callback, text)
+    text = re.sub(r"([\w\s*]+?)\b(cloudaae_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", prototype, text)
+    stray = re.search(r"(cloudaae_[a-z0-9_]+)\s*\(", text)
+    if stray is not None:
+        raise HipLibraryError("the header mentions %s in a form its reader (cloudaae_amd/_lib.py) does not know"
+                              % stray.group(1))
+    return int(abi.group(1)), structs, prototypes, launching
+
+
+with open(HEADER) as _f:
+    ABI_VERSION, _STRUCTS, _PROTOTYPES, _LAUNCHING = read_header(_f.read())
+# argument types of every launching entry point (the ones that take a stream): what a StepPlan records
+_SIGNATURES = {name: _PROTOTYPES[name][1] for name in _LAUNCHING}
+
+
+class GemmTnJob(ctypes.Structure):
+    """struct cloudaae_gemm_tn_job (include/cloudaae_hip.h): one product of a grouped weight-gradient launch."""
+    _fields_ = _STRUCTS["cloudaae_gemm_tn_job"]
+
+
+class FcLayer(ctypes.Structure):
+    """struct cloudaae_fc_layer (include/cloudaae_hip.h): one layer of a grouped fully connected launch."""
+    _fields_ = _STRUCTS["cloudaae_fc_layer"]
+
+
+class BnSyncStruct(ctypes.Structure):
+    """struct cloudaae_bn_sync (include/cloudaae_hip.h): the host's all-reduce for batch-norm sums."""
+    _fields_ = _STRUCTS["cloudaae_bn_sync"]
 
 
 def build(verbose=False):
@@ -346,17 +259,30 @@ class _Entry(object):
         return rc
 
 
+def _typed(cdll, name):
+    """cdll's function `name` with the argument and result types the header declares for it."""
+    try:
+        fn = getattr(cdll, name)
+    except AttributeError:
+        raise HipLibraryError("%s does not export %s, which %s declares: rebuild it (`make -C cloudaae_amd/csrc`)"
+                              % (LIB_PATH, name, HEADER)) from None
+    fn.restype, fn.argtypes = _PROTOTYPES[name]
+    return fn
+
+
 class _Library(object):
-    """What lib() returns: attribute access gives the ctypes function (non-launching queries) or
-    its recording wrapper (everything in _SIGNATURES)."""
+    """What lib() returns: every function the header declares, typed from it -- the ctypes function itself
+    (non-launching queries) or its recording wrapper (everything in _SIGNATURES).  `_cdll` holds the same typed
+    functions without the wrapper."""
 
     def __init__(self, cdll):
         self._cdll = cdll
-        for fn in _SIGNATURES:
-            setattr(self, fn, _Entry(getattr(cdll, fn), fn))
+        for name in _PROTOTYPES:
+            fn = _typed(cdll, name)
+            setattr(self, name, _Entry(fn, name) if name in _SIGNATURES else fn)
 
-    def __getattr__(self, name):          # only reached for names not set above
-        return getattr(self._cdll, name)
+    def __getattr__(self, name):          # only reached for names not set above: never an untyped ctypes function
+        raise AttributeError("%s is not declared in %s" % (name, HEADER))
 
 
 def lib():
@@ -370,91 +296,12 @@ def lib():
                 "%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C cloudaae_amd/csrc` (there is no CPU fallback)" % LIB_PATH)
         cdll = ctypes.CDLL(LIB_PATH)
-        cdll.cloudaae_last_error.restype = ctypes.c_char_p
-        # the signature table below describes ONE revision of the C ABI (CLOUDAAE_ABI_VERSION of include/cloudaae_hip.h):
-        # a library of another revision would take these calls with shifted arguments and corrupt memory
-        cdll.cloudaae_version.argtypes = []
-        cdll.cloudaae_version.restype = ctypes.c_int
-        have = int(cdll.cloudaae_version())
+        # the header describes ONE revision of the C ABI (CLOUDAAE_ABI_VERSION): a library of another revision would take
+        # calls typed from it with shifted arguments and corrupt memory
+        have = int(_typed(cdll, "cloudaae_version")())
         if have != ABI_VERSION:
             raise HipLibraryError("%s speaks ABI revision %d, this package expects %d: rebuild it (`make -C cloudaae_amd/csrc`)"
                                   % (LIB_PATH, have, ABI_VERSION))
-        for fn, sig in _SIGNATURES.items():
-            f = getattr(cdll, fn)
-            f.argtypes = sig
-            f.restype = ctypes.c_int
-        for fn in _LONGLONG_RESULTS:
-            getattr(cdll, fn).restype = ctypes.c_longlong
-        cdll.cloudaae_hpr_workspace_bytes.restype = ctypes.c_longlong
-        cdll.cloudaae_hpr_workspace_bytes.argtypes = [_I, _I]
-        for q, sig in (("cloudaae_frame_segments_workspace_bytes", [_I, _I, _I, _I]),
-                       ("cloudaae_radius_outlier_workspace_bytes", [_I, _L]),
-                       ("cloudaae_ragged_fps_workspace_bytes", [_L]),
-                       ("cloudaae_mesh_weights_workspace_bytes", [_L]),
-                       ("cloudaae_render_workspace_bytes", [_I, _I, _I, _I, _L, _L]),
-                       ("cloudaae_frame_clouds_workspace_bytes", [_I, _I, _I, _I, _I]),
-                       ("cloudaae_pose_score_workspace_bytes", [_I, _I, _I]),
-                       ("cloudaae_pose_max_dist_workspace_bytes", [_I, _I, _I]),
-                       ("cloudaae_transform_hausdorff_workspace_bytes", [_I]),
-                       ("cloudaae_estimate_normals_workspace_bytes", [_I, _L]),
-                       ("cloudaae_cloud_diameter_workspace_bytes", [_I, _I]),
-                       ("cloudaae_depth_components_workspace_bytes", [_I, _I, _I]),
-                       ("cloudaae_component_labels_workspace_bytes", [_I, _I, _I]),
-                       ("cloudaae_depth_creases_workspace_bytes", [_I, _I, _I]),
-                       ("cloudaae_depth_align_step_workspace_bytes", [_I, _I, _I]),
-                       ("cloudaae_depth_contour_sums_workspace_bytes", [_I, _I, _I]),
-                       ("cloudaae_tsdf_align_step_workspace", [_I, _I, _I])):
-            getattr(cdll, q).argtypes = sig
-            getattr(cdll, q).restype = ctypes.c_longlong
-        cdll.cloudaae_gemm_f32_splits.argtypes = [_I, _I, _I]
-        cdll.cloudaae_gemm_f32_splits.restype = ctypes.c_int
-        cdll.cloudaae_gemm_bf16_splits.argtypes = [_I, _I, _I]
-        cdll.cloudaae_gemm_bf16_splits.restype = ctypes.c_int
-        cdll.cloudaae_gemm_f32_ordered_workspace.argtypes = [_I, _I, _I]
-        cdll.cloudaae_gemm_bf16_ordered_workspace.argtypes = [_I, _I, _I]
-        cdll.cloudaae_bn_workspace_bytes.argtypes = [_I]
-        cdll.cloudaae_gemm_f32_colstats_parts.argtypes = [_I, _I, _I]
-        cdll.cloudaae_gemm_f32_colstats_parts.restype = ctypes.c_int
-        cdll.cloudaae_gemm_bf16_colstats_parts.argtypes = [_I, _I, _I]
-        cdll.cloudaae_gemm_bf16_colstats_parts.restype = ctypes.c_int
-        cdll.cloudaae_gemm_b16_colstats_parts.argtypes = [_I, _I, _I]
-        cdll.cloudaae_gemm_b16_colstats_parts.restype = ctypes.c_int
-        cdll.cloudaae_gemm_b16_supported.argtypes = [_I, _I, _I, _I, _I]
-        cdll.cloudaae_gemm_b16_supported.restype = ctypes.c_int
-        cdll.cloudaae_gemm_bf16x3_colstats_parts.argtypes = [_I, _I, _I]
-        cdll.cloudaae_gemm_bf16x3_colstats_parts.restype = ctypes.c_int
-        cdll.cloudaae_gemm_bf16x3_supported.argtypes = [_I, _I, _I, _I, _I]
-        cdll.cloudaae_gemm_bf16x3_supported.restype = ctypes.c_int
-        for q in ("cloudaae_gemm_bf16x3p_supported", "cloudaae_gemm_bf16x3p_colstats_parts"):
-            getattr(cdll, q).argtypes = [_I, _I, _I]
-            getattr(cdll, q).restype = ctypes.c_int
-        cdll.cloudaae_x3_planes_bytes.argtypes = [_I, _I]
-        cdll.cloudaae_bn_backward_dx_bf16x3_supported.argtypes = [_I, _I, _I, _I]
-        cdll.cloudaae_bn_backward_dx_bf16x3_supported.restype = ctypes.c_int
-        cdll.cloudaae_bn_backward_dx_bf16x3_consts_bytes.argtypes = [_I, _I, _I]
-        for q in ("cloudaae_fc_max_rows", "cloudaae_fc_max_group"):
-            getattr(cdll, q).argtypes = []
-            getattr(cdll, q).restype = ctypes.c_int
-        cdll.cloudaae_side_stream.argtypes = []
-        cdll.cloudaae_side_stream.restype = ctypes.c_void_p
-        cdll.cloudaae_fc_forward_tickets.argtypes = [_I, _I]
-        cdll.cloudaae_fc_forward_tickets.restype = ctypes.c_int
-        cdll.cloudaae_loss_tail_workspace_bytes.argtypes = []
-        cdll.cloudaae_fc_forward_partials.argtypes = [_I, _I, _I, _I]
-        cdll.cloudaae_fc_forward_partials.restype = ctypes.c_longlong
-        cdll.cloudaae_fc_plan.argtypes = [_I, _I, _I, _I, _I, _I, _I, _P]
-        cdll.cloudaae_fc_plan.restype = ctypes.c_int
-        cdll.cloudaae_edgeconv_workspace_bytes.argtypes = [_I]
-        # which kernel a call of the point-cloud ops takes (host only; the encodings are in include/cloudaae_hip.h)
-        for q, sig in (("cloudaae_farthest_point_sample_variant", [_I]),
-                       ("cloudaae_knn_variant", [_I, _I, _I, _I, _I, _I]),
-                       ("cloudaae_nn_distance_variant", [_I, _I, _I])):
-            getattr(cdll, q).argtypes = sig
-            getattr(cdll, q).restype = ctypes.c_int
-        for q in ("cloudaae_set_knob", "cloudaae_unset_knob"):
-            getattr(cdll, q).restype = ctypes.c_int
-        cdll.cloudaae_set_knob.argtypes = [ctypes.c_char_p, _I]
-        cdll.cloudaae_unset_knob.argtypes = [ctypes.c_char_p]
         _lib = _Library(cdll)
     return _lib
 

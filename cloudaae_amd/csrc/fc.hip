@@ -1011,9 +1011,9 @@ static FcBwdPlan fc_bwd_plan(int M, int K, int N)
 
 using namespace cloudaae;
 
-#ifdef CLOUDAAE_FC_PROFILE
 CLOUDAAE_API int cloudaae_fc_profile_read(unsigned long long *host, int clear)
 {
+#ifdef CLOUDAAE_FC_PROFILE
     if (host && hipMemcpyFromSymbol(host, HIP_SYMBOL(g_fc_prof), sizeof(unsigned long long) * 8192 * 8) != hipSuccess)
         return 1;
     if (clear) {
@@ -1022,8 +1022,12 @@ CLOUDAAE_API int cloudaae_fc_profile_read(unsigned long long *host, int clear)
             return 1;
     }
     return 0;
-}
+#else
+    (void)host, (void)clear;
+    set_error("cloudaae_fc_profile_read: this library was built without -DCLOUDAAE_FC_PROFILE (make prof builds one with)");
+    return (int)hipErrorNotSupported;
 #endif
+}
 
 CLOUDAAE_API int cloudaae_fc_max_rows(void) { return FC_ROWS * FC_MAX_RT; }
 CLOUDAAE_API int cloudaae_fc_max_group(void) { return FC_MAX_GROUP; }

@@ -1026,9 +1026,9 @@ static int hpr_stride(int n)
 
 using namespace cloudaae;
 
-#ifdef CLOUDAAE_HPR_STATS
 CLOUDAAE_API int cloudaae_hpr_stats_read(unsigned long long *out, int reset)
 {
+#ifdef CLOUDAAE_HPR_STATS
     hipDeviceSynchronize();
     hipMemcpyFromSymbol(out, HIP_SYMBOL(hpr_stats), sizeof(hpr_stats));
     if (reset) {
@@ -1036,8 +1036,12 @@ CLOUDAAE_API int cloudaae_hpr_stats_read(unsigned long long *out, int reset)
         hipMemcpyToSymbol(HIP_SYMBOL(hpr_stats), z, sizeof(z));
     }
     return 0;
-}
+#else
+    (void)out, (void)reset;
+    set_error("cloudaae_hpr_stats_read: this library was built without -DCLOUDAAE_HPR_STATS (make prof builds one with)");
+    return (int)hipErrorNotSupported;
 #endif
+}
 
 CLOUDAAE_API int cloudaae_transform_object_model(int b, int npts, int nmodels, const float *models,
                                                  const long long *class_id, const double *rot, const float *trans,

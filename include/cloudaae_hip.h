@@ -75,6 +75,15 @@ const char *cloudaae_last_error(void);
  * the reference's sequential CPU path is. */
 int cloudaae_set_knob(const char *name, int value);
 int cloudaae_unset_knob(const char *name);
+/* Development helpers: what the instrumented library (`make prof`, a second shared object built with
+ * -DCLOUDAAE_FC_PROFILE and -DCLOUDAAE_HPR_STATS) gathered, copied to HOST memory; the library as shipped carries no
+ * instrumentation and both fail with hipErrorNotSupported.  They synchronise the device.
+ * cloudaae_fc_profile_read: host[8192][8], the 100 MHz wall clock of the first 8192 workgroups at eight points of the
+ *   fully connected kernels (tools/dev/fc_phases.py names the points); host NULL: no copy; clear != 0: zeroed afterwards.
+ * cloudaae_hpr_stats_read: out[16], counters of cloudaae_hidden_point_removal (points, local re-solves, passes, box
+ *   iterations, groups scanned, joined, fallbacks, vertices); reset != 0: zeroed afterwards. */
+int cloudaae_fc_profile_read(unsigned long long *host, int clear);
+int cloudaae_hpr_stats_read(unsigned long long *out, int reset);
 /* HOST helper: CRC-32C (Castagnoli, reflected, init/final xor 0xffffffff) of n bytes of host memory -- the
  * checksum of the TFRecord framing (train_cloudAAE_ycbv.py:80-135) and of tf.train.Saver checkpoints
  * (:276, :418-430).  crc = 0 for a whole buffer, or the previous result to continue over the next piece. */
@@ -654,6 +663,10 @@ int cloudaae_input_assemble(int b, int p, int n, int num_class, const float *vis
 int cloudaae_input_assemble_noise(int b, int p, int n, int num_class, const float *visible, const long long *class_id,
                                   float *pc, float *mean, float *noisy, float noise_std, unsigned long long seed,
                                   unsigned long long *draws, cloudaae_stream_t stream);
+/* `count` buffers cleared to zero, eight per launch (a launch per buffer costs the stream ~5 us whatever it moves): the
+ * zero zones of a recorded step and the gradient slots its split-K products add into.  buffers[i] (a HOST array of
+ * device pointers, as bytes is a host array) is 16-byte aligned and bytes[i] a multiple of 16. */
+int cloudaae_zero_buffers(int count, void *const *buffers, const long long *bytes, cloudaae_stream_t stream);
 /* :232-233  out[b,r,:] = x[b,r,:] + v[b,:] */
 int cloudaae_add_rowvec(int b, int r, int d, const float *x, const float *v, float *out,
                         cloudaae_stream_t stream);
@@ -707,6 +720,18 @@ int cloudaae_pose_losses_grad(int b, const float *trans_pred, const float *trans
                               const double *rot_jac, const float *g_total, float w_xyz, float w_trans,
                               float w_rot, float *d_xyz_loss, float *d_trans_pred, float *d_rot_pred,
                               cloudaae_stream_t stream);
+/* The WHOLE loss tail in one launch: cloudaae_add_mean_f32 (per[n] = dist1 + dist2, xyz_loss = its mean, partial sums
+ * in fixed order), then, in the workgroup that finishes last, cloudaae_pose_losses and -- g_total != NULL: the step's
+ * upstream d(total) is known now -- cloudaae_pose_losses_grad; same arithmetic as those three.  g_total NULL: the three
+ * gradient outputs are not touched and may be NULL.  workspace: cloudaae_loss_tail_workspace_bytes() bytes; ticket:
+ * one int holding zero, left zero. */
+long long cloudaae_loss_tail_workspace_bytes(void);
+int cloudaae_loss_tail(long long n, const float *dist1, const float *dist2, float *per, float *xyz_loss, int b,
+                       const float *trans_pred, const float *trans_label, const float *rot_pred,
+                       const double *rot_label, float w_xyz, float w_trans, float w_rot, float *trans_per,
+                       float *trans_loss, double *rot_per, double *rot_jac, float *rot_loss, float *total,
+                       const float *g_total, float *d_xyz_loss, float *d_trans_pred, float *d_rot_pred,
+                       void *workspace, int *ticket, cloudaae_stream_t stream);
 /* :268  total = w0*a + w1*b + w2*c on device scalars */
 int cloudaae_loss_mix(const float *a, const float *b, const float *c, float w0, float w1, float w2,
                       float *out, cloudaae_stream_t stream);

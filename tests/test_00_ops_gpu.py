@@ -1,7 +1,6 @@
 """GPU: tf_ops custom operators and kNN grouping through the C-ABI vs the oracle."""
 import os
 
-import ctypes
 
 import numpy as np
 import pytest
@@ -627,7 +626,6 @@ def test_nn_distance_split_score_error(hip, scale, offset):
     the centred fp32 coordinates: the hardware must stay inside that charge -- it stays far inside (a few units)."""
     from cloudaae_amd import _lib
     L = _lib.lib()
-    L._cdll.cloudaae_dev_nn_split_scores.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5
     rng = np.random.default_rng(int(scale * 1000) % 997)
     worst = 0.0
     for rep in range(40):

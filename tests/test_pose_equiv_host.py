@@ -3,7 +3,6 @@ depend on it -- the minimum of the plain geodesic distance over the members, the
 angle between the axes of an axially symmetric object -- and utils/pose_equiv.py's table: what it makes of find_symmetries
 results, its round trip through a save_symmetries file and what it refuses.  The entry point of the C ABI is exported and
 rejects bad arguments before it touches memory."""
-import ctypes
 import math
 import os
 import re
@@ -213,12 +212,7 @@ def test_table_refuses_what_the_kernel_cannot_take(tmp_path):
 def cdll():
     from cloudaae_amd import _lib
     assert os.path.exists(_lib.LIB_PATH), "build the library first (__graft_entry__.build())"
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    lib.cloudaae_last_error.restype = ctypes.c_char_p
-    fn = lib.cloudaae_nearest_equivalent_pose
-    fn.argtypes = _lib._SIGNATURES["cloudaae_nearest_equivalent_pose"]
-    fn.restype = ctypes.c_int
-    return lib
+    return _lib.lib()._cdll             # typed from the header, without the recording wrapper
 
 
 def test_entry_point_is_declared_and_rejects_bad_arguments(cdll):

@@ -47,7 +47,6 @@ def main():
     ap.add_argument("--knob", action="append", default=[])
     args = ap.parse_args()
     L = _lib.lib()
-    L._cdll.cloudaae_fc_profile_read.argtypes = [ctypes.c_void_p, ctypes.c_int]
     for kv in args.knob:
         k, v = kv.split("=")
         _lib.set_knob(k, int(v))
